@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- frames/s of the splat hot path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one frame: preprocess -> level-1 binning (count, scan, scatter) -> per-bin depth order + tile
@@ -9,16 +9,22 @@ lists -> blend, over the synthetic scene S(1e6) at 1920x1080 (BASELINE configs[1
 HBM before the timed region and the RGBA32F frame stays in HBM.  The blend runs in the library's DEFAULT mode -- exp mode 3:
 the hardware's v_exp_f32 with the reference's decisions (render.comp:78 decided on the alpha cut, render.comp:82 guarded,
 ambiguous breaks resolved with the reference's arithmetic): within rounding noise of the reference's render.comp compiled for
-the CPU on any scene, BASELINE.json's bar being 1e-4.  The bit-identical mode (exp mode 2) and the opt-in fast modes are timed
-beside it as diagnostics (`frames_per_s_exact`, `frames_per_s_fast_blend`, `frames_per_s_hw_exp`) and the measured distance of
-each from the reference text on the benched frame is in `parity`.  `--ply FILE` (or GS_SCENE=FILE) benches a trained scene
-instead of the synthetic one (BASELINE configs[2]).  After the headline measurement the line also carries `other_configs`:
-configs[4] (S(6e6) at 3840x2160) and the trained-like T(6e6) at full size, time-boxed.  With N > 1 the scene blob is
-broadcast once over RCCL/xGMI and every rank renders its own camera pose (configs[3]): no per-frame collective, weak
-scaling, value = N*K frames / max-over-ranks time; the line's `rccl` block proves what the collective saw.
+the CPU on any scene, BASELINE.json's bar being 1e-4.  `--ply FILE` (or GS_SCENE=FILE) benches a trained scene instead of the
+synthetic one (BASELINE configs[2]).  With N > 1 the scene blob is broadcast once over RCCL/xGMI and every rank renders its
+own camera pose (configs[3]): no per-frame collective, weak scaling, value = N*K frames / max-over-ranks time.
 
-Rank 0 prints ONE JSON line (contract in the task statement) with `roofline` for the dominant pass
-and `cpu_baseline` (the oracle -- CPU restatement of the reference shaders -- on the host cores).
+A plain run sets up, runs the W warm-up steps (then untimed K-step batches until the clocks and the blend tuner have settled,
+within a wall-time cap), times EXACTLY K steps once and prints the line: `value` = frames/s of that region, `ms_per_step` =
+its wall time / K.  `--dump-outputs DIR` saves what the last timed step computed (the frame, float32) as DIR/<name>.npy.
+
+`--full` adds every diagnostic beside the headline: the bit-identical mode (exp mode 2) and the opt-in fast modes timed
+(`frames_per_s_exact`, `frames_per_s_fast_blend`, `frames_per_s_hw_exp`), one frame in flight (`passes_serial_ms`),
+`roofline` for the dominant pass, the guard's work on the benched frame, the measured distance of each mode from the
+reference text in `parity`, `cpu_baseline` (the oracle -- CPU restatement of the reference shaders -- on the host cores),
+`other_configs` (configs[4] = S(6e6) at 3840x2160 and the trained-like T(6e6) at full size, time-boxed) and, with N > 1,
+the `rccl` block that proves what the collective saw.
+
+Rank 0 prints ONE JSON line (contract in the task statement).
 """
 import argparse
 import ctypes
@@ -42,7 +48,8 @@ HBM_PEAK_GBS = 8000.0  # MI355X spec (MI355X_MICROARCH.md); ~6300 GB/s achievabl
 VALU_PEAK = 1024 * 2.4e9 / 2
 VALU_SUSTAINED = 1024 / 1.09e-9
 MIN_WARM_SECONDS = 0.3   # untimed K-step batches run at least this long (the clocks of the driver's fresh box ramp for ~50 ms: BENCH_r05's first batches)
-MIN_TIMED_SECONDS = 0.5  # a timed region shorter than this is repeated and the median batch reported
+MAX_WARM_SECONDS = 10.0  # ... and at most this long, whatever K is (a large K or a box that never settles must not stretch the run)
+DUMP_BYTES = 60_000_000  # --dump-outputs: at most this much array data per run (larger outputs are written as a fixed, seeded sample)
 # the blend's modes (gs_set_exp_mode, gs_set_blend_contraction).  "default" is the library's: the guarded v_exp_f32
 MODES = {"default": (3, False), "exact": (2, False), "fast": (0, True), "hw_exp": (1, True)}
 BLEND_TEXT = {"default": "library default (exp mode 3): v_exp_f32 with the reference's decisions -- render.comp:78 decided on the alpha cut, "
@@ -146,6 +153,11 @@ def main():
                     help="bench this PLY (a trained scene, BASELINE configs[2]) instead of the synthetic one; also GS_SCENE=FILE")
     ap.add_argument("--no-other-configs", action="store_true", help="skip the `other_configs` block (configs[4] and T(6e6) after the headline)")
     ap.add_argument("--dump-frames", default="", help="directory: every rank saves the frame of its pose (frame_rank<r>.npy) after the timed region")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="save what the last timed step computed as DIR/<name>.npy (float32; a fixed, seeded sample beyond 60 MB)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the diagnostics beside the headline: other blend modes, one frame in flight, roofline, guard, parity, "
+                         "cpu_baseline, other_configs, rccl evidence")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", 0))
@@ -197,7 +209,7 @@ def main():
     pkg.dist.broadcast_blob(blob, src=0)  # RCCL over xGMI; no-op at world == 1
     torch.cuda.synchronize()
     broadcast_ms = 1e3 * (time.perf_counter() - t_bc)
-    rccl = rccl_evidence(torch, dist, dev, blob, rank, world, broadcast_ms) if world > 1 else None
+    rccl = rccl_evidence(torch, dist, dev, blob, rank, world, broadcast_ms) if world > 1 and args.full else None
     scene = pkg.Scene.from_device_blob(blob.data_ptr(), n, device=local_rank, keepalive=blob)
     if args.sh16:
         scene.quantize_sh()
@@ -236,7 +248,7 @@ def main():
     # schedules over its first ~130 frames, so untimed K-step batches follow until (a) three consecutive ones lie within 3 % of
     # the RUNNING MINIMUM without improving on it -- round 5 compared neighbours, which a smooth ramp satisfies: the driver's first
     # five timed batches were 5-19 % slow -- (b) the tuner has settled, (c) MIN_WARM_SECONDS have passed (every rank runs the same
-    # count: decided on the max over ranks)
+    # count: decided on the max over ranks); or MAX_WARM_SECONDS have passed, whatever (a) and (b) say
     # The harness must not stall the frame loop it times: rounds 2-4 lost one 35-45 ms batch per run to Python's full garbage
     # collection (cyclic garbage from numpy's `ctypes.data_as` in the binding, 170 000 objects to walk once torch is imported;
     # profiles/r05_stall_hunt.txt).  The binding no longer produces garbage; what setup left behind is collected now and the
@@ -265,7 +277,7 @@ def main():
         stable = stable + 1 if best is not None and 0.99 * best <= dtw <= 1.03 * best else 0
         best = dtw if best is None else min(best, dtw)
         tuner_settled = settled > 0
-        if stable >= 4 and tuner_settled and warm_s >= MIN_WARM_SECONDS:
+        if (stable >= 4 and tuner_settled and warm_s >= MIN_WARM_SECONDS) or warm_s >= MAX_WARM_SECONDS:
             break
     sync_all()
     rend.timing_totals(reset=True)
@@ -287,62 +299,67 @@ def main():
             dist.barrier()
         return dt
 
-    # K frames of this workload take a few milliseconds: one such region is at the mercy of a single scheduling
-    # hiccup.  The K-frame batch is therefore repeated until >= MIN_TIMED_SECONDS have been timed (every rank takes
-    # the same count: it is derived from the max-over-ranks time of the first batch) and the MEDIAN batch is reported.
+    # The timed region is EXACTLY the K steps of --steps, once: the caller chooses K from ms_per_step so that the region is as
+    # long as the precision it needs (the warm-up above has waited out the clock ramp and the blend tuner).
     own_s = []
     batch_s = [timed_batch()]
-    repeats = max(1, min(200, int(math.ceil(MIN_TIMED_SECONDS / max(batch_s[0], 1e-6)))))
-    for _ in range(repeats - 1):
-        batch_s.append(timed_batch())
-    elapsed = float(np.median(batch_s))
+    elapsed = batch_s[0]
 
     sums, frames = rend.timing_totals(reset=True)
     intervals = rend.frame_intervals(reset=True)  # completion-to-completion, GPU timestamps, this rank's K frames
     st = rend.stats()
     lockstep = rend.blend_lockstep()  # what the renderer's own measurement chose for this workload (gs_set_blend_lockstep)
+    if args.dump_outputs:  # the frame of the LAST timed step, before anything else renders into the targets
+        last = (args.steps - 1) % fif
+        got = {}
+        if outs[last] is not None:
+            got["image"] = outs[last].cpu().numpy()
+        if outs8[last] is not None:
+            got["image_bgra8"] = outs8[last].cpu().numpy()
+        dump_outputs(args.dump_outputs, got, "" if world == 1 else f"_rank{rank}", DUMP_BYTES // world)
 
-    # diagnostic only: the same frame with ONE frame in flight, so that per-pass spans are not stretched by
-    # the other streams' kernels (the timed region above overlaps frames; its spans include that contention)
-    rend.set_frames_in_flight(1)
-    ts = time.perf_counter()
-    for i in range(100):
-        submit(i)
-    rend.synchronize()
-    serial_fps = 100 / (time.perf_counter() - ts)
-    ssum, sframes = rend.timing_totals(reset=True)
-    # diagnostic only: the same region with the blend in the other modes (this rank) -- what the opt-in relaxations are
-    # worth on this box, and what the reference-exact default costs
-    def mode_fps(m):
-        rend.set_frames_in_flight(args.frames_in_flight)
-        set_mode(m)
-        for i in range(2 * args.steps):
+    frames_for_parity, guard = {}, None
+    if args.full:
+        # diagnostic only: the same frame with ONE frame in flight, so that per-pass spans are not stretched by
+        # the other streams' kernels (the timed region above overlaps frames; its spans include that contention)
+        rend.set_frames_in_flight(1)
+        ts = time.perf_counter()
+        for i in range(100):
             submit(i)
         rend.synchronize()
-        best = []
-        for _ in range(5):
-            ta = time.perf_counter()
-            for i in range(args.steps):
+        serial_fps = 100 / (time.perf_counter() - ts)
+        ssum, sframes = rend.timing_totals(reset=True)
+        # diagnostic only: the same region with the blend in the other modes (this rank) -- what the opt-in relaxations are
+        # worth on this box, and what the reference-exact default costs
+        def mode_fps(m):
+            rend.set_frames_in_flight(args.frames_in_flight)
+            set_mode(m)
+            for i in range(2 * args.steps):
                 submit(i)
             rend.synchronize()
-            best.append(args.steps / (time.perf_counter() - ta))
-        return float(np.median(best))
-    alt = {m: (mode_fps(m) if m != mode else None) for m in MODES}
-    # the benched frame in every mode, for the parity block (compared with the reference text in the cpu_baseline leg, where
-    # that image exists anyway), and what the guard of the default mode did on it
-    frames_for_parity = {}
-    set_mode("default")
-    rend.set_frames_in_flight(1)
-    rend.render_host(u)
-    gst = rend.stats()
-    guard = {"break_decisions_resolved_exactly": int(gst.blend_resolved), "quadrants_rerendered_exactly": int(gst.blend_redo),
-             "quadrants": ((w + 7) // 8) * ((h + 7) // 8),
-             "what": "render.comp:83 decisions that fell inside the guard's proven window around 1e-4 and were taken from an exact "
-                     "per-pixel replay; 8x8-pixel quadrants the fast pass abandoned and re-rendered with exp mode 2's arithmetic"}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        for m in MODES:
-            set_mode(m)
-            frames_for_parity[m] = rend.render_host(u)[0]
+            best = []
+            for _ in range(5):
+                ta = time.perf_counter()
+                for i in range(args.steps):
+                    submit(i)
+                rend.synchronize()
+                best.append(args.steps / (time.perf_counter() - ta))
+            return float(np.median(best))
+        alt = {m: (mode_fps(m) if m != mode else None) for m in MODES}
+        # the benched frame in every mode, for the parity block (compared with the reference text in the cpu_baseline leg, where
+        # that image exists anyway), and what the guard of the default mode did on it
+        set_mode("default")
+        rend.set_frames_in_flight(1)
+        rend.render_host(u)
+        gst = rend.stats()
+        guard = {"break_decisions_resolved_exactly": int(gst.blend_resolved), "quadrants_rerendered_exactly": int(gst.blend_redo),
+                 "quadrants": ((w + 7) // 8) * ((h + 7) // 8),
+                 "what": "render.comp:83 decisions that fell inside the guard's proven window around 1e-4 and were taken from an exact "
+                         "per-pixel replay; 8x8-pixel quadrants the fast pass abandoned and re-rendered with exp mode 2's arithmetic"}
+        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+            for m in MODES:
+                set_mode(m)
+                frames_for_parity[m] = rend.render_host(u)[0]
     set_mode(mode)
     rend.set_frames_in_flight(args.frames_in_flight)
     if args.dump_frames:  # tests: every rank's pose against the checker (tests/test_gpu_dist.py)
@@ -350,7 +367,7 @@ def main():
         np.save(os.path.join(args.dump_frames, f"frame_rank{rank}.npy"), rend.render_host(u)[0])
     # every rank's own rate over the timed batches (its frames / its own wall time, before the max over ranks)
     rank_fps = None
-    if world > 1:
+    if world > 1 and args.full:
         mine = torch.tensor([args.steps / float(np.median(own_s))], dtype=torch.float64, device=dev)
         allr = [torch.zeros_like(mine) for _ in range(world)]
         dist.all_gather(allr, mine)
@@ -366,10 +383,6 @@ def main():
         ms = {k: getattr(sums, "ms_" + k) / max(frames, 1) for k in names}
         per_pass = {k: {"ms": round(ms[k], 4), "alg_MB": round(nbytes[k] / 1e6, 2),
                         "GBps": round(nbytes[k] / 1e9 / (ms[k] * 1e-3), 1) if ms[k] > 0 else None} for k in names}
-        # dominant kernel = largest share of a frame's GPU time when frames run one at a time (k_blend here);
-        # its duration for the roofline is the span measured inside the timed (overlapped) region
-        serial = {k: getattr(ssum, "ms_" + k) / max(sframes, 1) for k in names}
-        dom = max(names, key=lambda k: serial[k])
         # run-to-run spread of the batches: interquartile range over the median (a single slow batch -- typically the
         # first one, while the clocks come up -- shows in batch_ms.max, not here)
         spread = (float(np.percentile(batch_s, 75) - np.percentile(batch_s, 25)) / elapsed) if len(batch_s) > 1 else None
@@ -383,7 +396,7 @@ def main():
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": head["ms_per_step"],
-            # every timed frame over every timed second (value is the MEDIAN batch): what a consumer that runs for minutes gets
+            # every timed frame over every timed second (one timed region of K steps: the same figure as `value`)
             "sustained_frames_per_s": round(world * args.steps * len(batch_s) / float(np.sum(batch_s)), 2),
             "higher_is_better": True,
             "scaling": "weak",
@@ -391,7 +404,7 @@ def main():
             "dtype": "f32",
             "data": "synthetic",
             "config": {"workload": workload_name(n, w, h, world, args.scene, args.ply), "scene": "ply" if args.ply else args.scene,
-                       "blend": BLEND_TEXT[mode], "blend_guard": guard,
+                       "blend": BLEND_TEXT[mode],
                        "blend_lockstep": {"on": bool(lockstep[0]), "settled": bool(lockstep[1]),
                                           "what": "a tile's four waves take every chunk of its list together (their record gathers meet in L1); "
                                                   "automatic: the renderer measures both settings and keeps the faster -- frames are bit-identical either way"},
@@ -401,12 +414,12 @@ def main():
                        "depth_order_path": {1: "global", 2: "bin-local"}.get(int(st.sort_path), "?"),
                        "max_bin_entries": int(st.max_bin_entries), "bins": bins, "bin_tiles": bin_edge,
                        "sort_level": int(st.sort_level)},
-            # the K-step region is timed `batches` times (each bracketed by barrier + synchronize); value / ms_per_step
-            # are the median batch, spread = interquartile range / median over the batches
+            # the K-step region, timed once (bracketed by barrier + synchronize): value / ms_per_step are that batch
             "timed": {"batches": len(batch_s), "seconds": round(float(np.sum(batch_s)), 6),
                       # what the untimed warm-up did before the first timed batch: K-step batches until three in a row lay within
-                      # 3 % of the running minimum AND the blend tuner had made its choice (a ramp cannot pass; verdict r5 item 7)
-                      "warmup_batches": warm_batches, "tuner_settled_before_first_batch": bool(tuner_settled),
+                      # 3 % of the running minimum AND the blend tuner had made its choice (a ramp cannot pass; verdict r5 item 7),
+                      # or MAX_WARM_SECONDS
+                      "warmup_batches": warm_batches, "warmup_seconds": round(warm_s, 3), "tuner_settled_before_first_batch": bool(tuner_settled),
                       "first_batch_over_median": round(batch_s[0] / elapsed, 4),
                       "batch_ms": {"min": round(1e3 * min(batch_s), 4), "median": round(1e3 * elapsed, 4),
                                    "max": round(1e3 * max(batch_s), 4), "each": [round(1e3 * b, 2) for b in batch_s]},
@@ -420,26 +433,35 @@ def main():
                                         "p95": round(float(np.percentile(intervals, 95)), 4), "n": int(len(intervals))}
                                        if len(intervals) else None),
             "gpu_ms_per_frame": round(sums.ms_total / max(frames, 1), 4),
-            "frames_per_s_one_in_flight": round(serial_fps, 2),  # diagnostic: one frame at a time (latency-bound)
-            # diagnostics, this rank: the same region in the other blend modes (None = the benched one)
-            "frames_per_s_default": round(alt["default"], 2) if alt["default"] else None,
-            "frames_per_s_exact": round(alt["exact"], 2) if alt["exact"] else None,   # the bit-identical mode (round 3's default)
-            "frames_per_s_fast_blend": round(alt["fast"], 2) if alt["fast"] else None,
-            "frames_per_s_hw_exp": round(alt["hw_exp"], 2) if alt["hw_exp"] else None,
             "passes": per_pass,
-            "passes_serial_ms": {k: round(getattr(ssum, "ms_" + k) / max(sframes, 1), 4) for k in names + ["total"]},
-            "roofline": roofline(pkg, dom, workload_key(n, w, h, "ply" if args.ply else args.scene), MODES[mode], nbytes[dom], ms[dom],
-                                 serial[dom], 1e3 * elapsed / args.steps),
         }
-        if world > 1:
+        if args.full:
+            # dominant kernel = largest share of a frame's GPU time when frames run one at a time (k_blend here);
+            # its duration for the roofline is the span measured inside the timed (overlapped) region
+            serial = {k: getattr(ssum, "ms_" + k) / max(sframes, 1) for k in names}
+            dom = max(names, key=lambda k: serial[k])
+            result["config"]["blend_guard"] = guard
+            result.update({
+                "frames_per_s_one_in_flight": round(serial_fps, 2),  # diagnostic: one frame at a time (latency-bound)
+                # diagnostics, this rank: the same region in the other blend modes (None = the benched one)
+                "frames_per_s_default": round(alt["default"], 2) if alt["default"] else None,
+                "frames_per_s_exact": round(alt["exact"], 2) if alt["exact"] else None,   # the bit-identical mode (round 3's default)
+                "frames_per_s_fast_blend": round(alt["fast"], 2) if alt["fast"] else None,
+                "frames_per_s_hw_exp": round(alt["hw_exp"], 2) if alt["hw_exp"] else None,
+                "passes_serial_ms": {k: round(getattr(ssum, "ms_" + k) / max(sframes, 1), 4) for k in names + ["total"]},
+                "roofline": roofline(pkg, dom, workload_key(n, w, h, "ply" if args.ply else args.scene), MODES[mode], nbytes[dom], ms[dom],
+                                     serial[dom], 1e3 * elapsed / args.steps),
+            })
+        if world > 1 and args.full:
             result["rccl"] = dict(rccl or {}, per_rank_frames_per_s=rank_fps,
                                   slowest_rank=int(np.argmin(rank_fps)) if rank_fps else None)
         if args.bgra8_only:
             result["passes"]["render"]["alg_MB"] = round((nbytes["render"] - 12 * w * h) / 1e6, 2)  # 4 B per pixel out, not 16
-        if not args.no_cpu_baseline and world == 1:  # reported baseline: rank 0 at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:  # reported baseline: rank 0 at N = 1 only
             result["cpu_baseline"], result["parity"] = cpu_baseline(n, w, h, args.scene, frames_for_parity, ply=args.ply)
         # the other BASELINE configs a single command can show (verdict r3 item 8): after the headline, its renderer released
-        if world == 1 and not args.no_other_configs and not args.ply and (n, w, h, args.scene) == (1_000_000, 1920, 1080, "S"):
+        if (args.full and world == 1 and not args.no_other_configs and not args.ply
+                and (n, w, h, args.scene) == (1_000_000, 1920, 1080, "S")):
             rend.close()
             scene.close()
             del blob, outs, outs8
@@ -449,6 +471,20 @@ def main():
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def dump_outputs(out_dir, arrays, suffix, budget):
+    """--dump-outputs: every array as out_dir/<name><suffix>.npy in float32.  When together they exceed `budget` bytes, each is
+    written as a fixed, seeded sample of its flattened elements (sorted indices; its share of the budget by size), the same
+    sample on every run with the same arguments, so that two builds can be compared output for output."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(4 * a.size for a in arrays.values())
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if total > budget:
+            keep = max(1, budget * a.size // total)  # elements: its share of the budget in bytes, over 4 bytes each
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))]
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), a)
 
 
 FP32_PEAK_TFLOPS = 157.3  # MI355X_MICROARCH.md: peak FP32 (vector)

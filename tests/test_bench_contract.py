@@ -211,3 +211,29 @@ def test_rocprof_summary_agrees_with_the_bench_line():
     # ... and the flop view follows from that duration and the committed pair count alone
     assert abs(r["one_in_flight"]["frac"] - 22 * r["walked_pairs"] / (live_ms * 1e-3) / 157.3e12) < 2e-3
     assert abs(b["passes_serial_ms"]["render"] - live_ms) < 1e-3
+
+
+def test_dump_outputs_writes_float32_within_budget_and_samples_the_same_way(tmp_path):
+    """--dump-outputs: every array as <name><suffix>.npy in float32; beyond the budget, a fixed, seeded sample of each array
+    (its share of the budget by size) -- the same elements on every run, so that two builds can be compared output for output."""
+    import numpy as np
+    m = _bench_module()
+    rng = np.random.default_rng(5)
+    img = np.arange(90 * 160 * 4, dtype=np.float32).reshape(90, 160, 4)  # element k holds k: the sample shows which it took
+    img8 = rng.integers(0, 256, (90, 160, 4), dtype=np.uint8)
+    m.dump_outputs(str(tmp_path / "whole"), {"image": img, "image_bgra8": img8}, "", 10 ** 6)
+    got = np.load(tmp_path / "whole" / "image.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, img)
+    got8 = np.load(tmp_path / "whole" / "image_bgra8.npy")
+    assert got8.dtype == np.float32 and np.array_equal(got8, img8.astype(np.float32))
+    budget = 100_000
+    for run in ("a", "b"):
+        m.dump_outputs(str(tmp_path / run), {"image": img, "image_bgra8": img8}, "_rank1", budget)
+    sizes = 0
+    for name in ("image_rank1.npy", "image_bgra8_rank1.npy"):
+        a, b = np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name)
+        assert a.dtype == np.float32 and a.ndim == 1 and np.array_equal(a, b)
+        sizes += a.nbytes
+    assert 0.99 * budget <= sizes <= budget
+    sample = np.load(tmp_path / "a" / "image_rank1.npy")
+    assert sample[0] >= 0 and sample[-1] < img.size and (np.diff(sample) > 0).all()  # distinct elements, in their order

@@ -113,7 +113,7 @@ def test_bench_two_ranks_on_one_gpu(pkg, oracle, gpu, tmp_path):
     port = 29600 + os.getpid() % 300
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5",
-           "--gaussians", str(n), "--width", str(w), "--height", str(h), "--dump-frames", str(tmp_path), "--exact"]
+           "--gaussians", str(n), "--width", str(w), "--height", str(h), "--dump-frames", str(tmp_path), "--exact", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=500, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:] + out.stdout[-500:]
     line = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])

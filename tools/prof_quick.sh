@@ -3,7 +3,7 @@
 TAG=$1; shift
 R=$(pwd); O=$R/gpurun_out/pq_$TAG; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-env "$@" timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O -o q -- python $R/bench.py --steps 60 --warmup 10 --no-cpu-baseline --frames-in-flight 1 > $O/bench.json 2>/dev/null
+env "$@" timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O -o q -- python $R/bench.py --full --steps 60 --warmup 10 --no-cpu-baseline --frames-in-flight 1 > $O/bench.json 2>/dev/null
 rm -f $O/*_kernel_trace.csv
 cd $R
 python - $O <<'PY'

@@ -2,7 +2,7 @@
 # the bench lines of the library as shipped (the counter files they quote are the committed profiles/r05_pmc_hbm_traffic.json: same kernel sources)
 set -u; exec < /dev/null
 R=$(pwd); O=$R/gpurun_out/r05_final; mkdir -p "$O"; export TMPDIR=/tmp
-B="timeout 240 python bench.py"
+B="timeout 240 python bench.py --full"
 $B --steps 20 --warmup 5 > "$O/r05_bench_driver_command.json" 2> /dev/null
 $B --steps 200 --warmup 20 > "$O/r05_bench_default.json" 2> "$O/bench_default.err"
 $B --steps 200 --warmup 20 --no-cpu-baseline --no-other-configs --exact > "$O/r05_bench_default_exact.json" 2> /dev/null

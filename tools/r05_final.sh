@@ -9,7 +9,7 @@ R=$(pwd); O=$R/gpurun_out/r05_final; mkdir -p "$O"
 bash tools/profile_lite.sh r05 B C T E > "$O/profile_lite.log" 2>&1
 python tools/profile_summary.py r05 > "$O/profile_summary.log" 2>&1
 export TMPDIR=/tmp
-B="timeout 240 python bench.py"
+B="timeout 240 python bench.py --full"
 $B --steps 20 --warmup 5 > "$O/r05_bench_driver_command.json" 2> /dev/null
 $B --steps 200 --warmup 20 > "$O/r05_bench_default.json" 2> "$O/bench_default.err"
 $B --steps 200 --warmup 20 --no-cpu-baseline --no-other-configs --exact > "$O/r05_bench_default_exact.json" 2> /dev/null

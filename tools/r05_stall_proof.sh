@@ -9,7 +9,7 @@ $P --frames 8000 --torch --legacy-pointers --label "torch imported, round-4 bind
 $P --frames 42000 --torch --label "torch imported, round-5 binding, 10 s" > $O/proof_fixed_10s.json 2> $O/proof_fixed_10s.err
 $P --frames 42000 --label "no torch, round-5 binding, 10 s" > $O/proof_notorch_10s.json 2> $O/proof_notorch_10s.err
 for f in proof_legacy proof_fixed_10s proof_notorch_10s; do echo "== $f: $(cat $O/$f.json)"; grep -c "stall:" $O/$f.err; done
-python bench.py --steps 20 --warmup 5 --no-other-configs > $O/bench_20.json 2> $O/bench_20.err
+python bench.py --full --steps 20 --warmup 5 --no-other-configs > $O/bench_20.json 2> $O/bench_20.err
 python - <<'PY'
 import json
 b = json.load(open("gpurun_out/stall/bench_20.json"))
