@@ -57,8 +57,8 @@ SYMBOLS = ["gs_last_error", "gs_device_count", "gs_read_ply", "gs_activate_recor
            "gs_scene_num_vertices", "gs_scene_quantize_sh", "gs_scene_sh_bits", "gs_scene_download_vertex_range",
            "gs_scene_download_vertices", "gs_scene_download_cov3d",
            "gs_scene_destroy", "gs_renderer_create", "gs_renderer_destroy", "gs_camera_uniforms",
-           "gs_render", "gs_render_host", "gs_synchronize", "gs_set_timing", "gs_set_frames_in_flight", "gs_set_sort_path", "gs_set_exp_mode", "gs_set_graph_mode", "gs_set_blend_lockstep", "gs_get_blend_lockstep", "gs_set_blend_contraction", "gs_get_timing_totals",
-           "gs_get_frame_intervals", "gs_get_stats", "gs_poll_stats", "gs_debug_download", "gs_debug_expf_scan", "gs_renderer_stream",
+           "gs_render", "gs_render_host", "gs_synchronize", "gs_set_timing", "gs_set_frames_in_flight", "gs_set_sort_path", "gs_set_exp_mode", "gs_set_graph_mode", "gs_set_blend_lockstep", "gs_get_blend_lockstep", "gs_set_blend_contraction", "gs_set_antialiased", "gs_get_antialiased", "gs_get_timing_totals",
+           "gs_get_frame_intervals", "gs_get_stats", "gs_poll_stats", "gs_debug_download", "gs_debug_expf_scan", "gs_debug_alpha_cut_scan", "gs_renderer_stream",
            "gs_dist_unique_id", "gs_dist_create", "gs_dist_rank", "gs_dist_world", "gs_dist_pose_count",
            "gs_dist_broadcast_scene", "gs_dist_broadcast_scene_ex", "gs_dist_verify", "gs_dist_destroy"]
 
@@ -73,6 +73,14 @@ class FrameStats(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+def debug_alpha_cut_scan(first_bits, count, device=0):
+    """Test hook gs_debug_alpha_cut_scan: (mismatches, first mismatching pattern or None) of the antialiased mode's per-frame
+    alpha cut against the load-time bisection, over the opacities with bit patterns [first_bits, first_bits + count)."""
+    bad, first = C.c_uint64(0), C.c_uint32(0)
+    _check(lib().gs_debug_alpha_cut_scan(C.c_int(device), C.c_uint32(first_bits), C.c_uint64(count), C.byref(bad), C.byref(first)))
+    return int(bad.value), (None if bad.value == 0 else int(first.value))
 
 
 def debug_expf_scan(first_bits, count, device=0):
@@ -289,6 +297,18 @@ class Renderer:
     def set_blend_contraction(self, enabled):
         """False (default): render.comp:66,87 as written; True: the three FMA contractions GLSL permits (gs_set_blend_contraction)."""
         _check(lib().gs_set_blend_contraction(self._h, C.c_int(int(bool(enabled)))))
+
+    def set_antialiased(self, enabled):
+        """True: the antialiased mode -- each splat's opacity scaled by sqrt(det(cov2D) / det(cov2D + 0.3 I)), as scenes trained
+        with antialiased rasterisation expect; False (default): the reference's pipeline (gs_set_antialiased)."""
+        _check(lib().gs_set_antialiased(self._h, C.c_int(int(bool(enabled)))))
+
+    @property
+    def antialiased(self):
+        """Whether the antialiased mode is on (gs_get_antialiased)."""
+        rc = lib().gs_get_antialiased(self._h)
+        _check(min(rc, 0))
+        return bool(rc)
 
     def set_fast_blend(self, fast):
         """True: both opt-in relaxations (polynomial exp, contractions); False: exp mode 2 as written, bit-identical to the reference text."""

@@ -179,4 +179,41 @@ __device__ __forceinline__ float alpha_cut(float o, const uint2* __restrict__ ta
     return __uint_as_float(lo);
 }
 
+// alpha_cut(o) -- the same bits for every o -- from a float32 estimate instead of the whole range: the antialiased mode
+// (gs_set_antialiased) scales the opacity per frame, so its cut is taken per frame and per visible Gaussian.  The cut sits
+// where o exp(power) = 1/255, i.e. near -log(255 o) (the 0.99 clamp never decides it: 0.99 > 1/255).  From the estimate's
+// bit pattern the search gallops outward (steps 1, 2, 4, ...) to a bracket [kept, not kept] and bisects it: by the
+// monotonicity above the boundary is unique, so ANY seed gives alpha_cut's answer, and a seed within d patterns of it costs
+// about 2 log2(d) + 2 evaluations instead of 31-33.  Where 255 o is close to 1 the estimate is many patterns off (the cut is
+// near -0, where patterns are dense); the gallop then takes longer, never a wrong turn.  The ends: a search that reaches -0
+// without a kept power returns +inf, one that reaches -inf still kept returns -inf, as alpha_cut does.
+__device__ __forceinline__ float alpha_cut_seeded(float o, const uint2* __restrict__ tab) {
+    const float est = -logf(255.0f * o);  // NaN (o < 0 or NaN), +inf (o = 0) or >= 0: start at -0; -inf (255 o = inf): start at -inf
+    const uint32_t seed = est < 0.0f ? __float_as_uint(est) : 0x80000000u;
+    constexpr uint32_t kNegZero = 0x80000000u, kNegInf = 0xFF800000u;
+    uint32_t lo, hi;  // kept at lo, not kept at hi; more negative = larger pattern
+    if (alpha_kept(o, __uint_as_float(seed), tab)) {
+        lo = seed;
+        for (uint32_t step = 1;; step <<= 1) {
+            if (lo == kNegInf) return __uint_as_float(kNegInf);
+            const uint32_t t = kNegInf - lo > step ? lo + step : kNegInf;
+            if (!alpha_kept(o, __uint_as_float(t), tab)) { hi = t; break; }
+            lo = t;
+        }
+    } else {
+        hi = seed;
+        for (uint32_t step = 1;; step <<= 1) {
+            if (hi == kNegZero) return __uint_as_float(0x7F800000u);
+            const uint32_t t = hi - kNegZero > step ? hi - step : kNegZero;
+            if (alpha_kept(o, __uint_as_float(t), tab)) { lo = t; break; }
+            hi = t;
+        }
+    }
+    while (hi - lo > 1u) {
+        const uint32_t mid = lo + (hi - lo) / 2u;
+        if (alpha_kept(o, __uint_as_float(mid), tab)) lo = mid; else hi = mid;
+    }
+    return __uint_as_float(lo);
+}
+
 }  // namespace gs

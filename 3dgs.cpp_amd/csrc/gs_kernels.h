@@ -122,8 +122,10 @@ void launch_sh_to_half(const float* blob, uint16_t* sh16, uint32_t n, uint32_t s
 // counters (nullable): the kernel clears the frame's counters, so that a frame needs no memset node.
 // fp (nullable, device memory): read the uniforms / output pointers from it instead of the arguments (graph replay)
 // stamps (nullable, device memory, [ST_COUNT]): the frame's timeline, see FrameStamp
+// antialiased: the records carry opacity * sqrt(det(cov2D) / det(cov2D + 0.3 I)) and that opacity's alpha cut, taken per
+// frame (gs_set_antialiased); sv.acut is not read.  Everything else the kernel writes is the same either way.
 void launch_preprocess(const SceneView& sv, const gs_uniforms& u, const AttrView& av, Counters* counters,
-                       const FrameParams* fp, uint64_t* stamps, hipStream_t s);
+                       const FrameParams* fp, uint64_t* stamps, bool antialiased, hipStream_t s);
 // behind the frame's last kernel: stamps[ST_END] = now, the stamps copied to host_stamps (pinned; fp non-null: fp->host_stamps)
 void launch_frame_end(uint64_t* stamps, uint64_t* host_stamps, const FrameParams* fp, hipStream_t s);
 

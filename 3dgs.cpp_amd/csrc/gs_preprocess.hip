@@ -8,6 +8,10 @@
 
 namespace gs {
 
+#ifndef GS_PRE_AA_BISECT
+#define GS_PRE_AA_BISECT 0  // 1: the antialiased variant takes its per-frame cut by alpha_cut's full bisection (the A/B of DESIGN.md)
+#endif
+
 #ifndef GS_PRE_SH_LDS
 #define GS_PRE_SH_LDS 1  // k_preprocess fetches the SH blocks of a wave's visible Gaussians with LDS-DMA, whole lines at a time
 #endif
@@ -114,6 +118,9 @@ struct ShFromLds16 {
 
 // One Gaussian per lane; `valid` = the lane has one (the last wave of the grid is ragged: every lane takes part in the
 // wave-cooperative parts).  stage: this wave's kPreStage float4 of LDS.
+// AA: the antialiased mode (gs_set_antialiased) -- the record carries the opacity scaled by the view-dependent factor that pays
+// for the 0.3 dilation, and that opacity's own alpha cut; nothing else of the frame changes.
+template <bool AA>
 __device__ __forceinline__ void preprocess_one(const SceneView& sv, const gs_uniforms& u, const AttrView& av, uint32_t i,
                                                bool valid, float4* __restrict__ stage) {
     const size_t N = sv.stride, NC = sv.n;
@@ -228,7 +235,20 @@ __device__ __forceinline__ void preprocess_one(const SceneView& sv, const gs_uni
         if (nt == 0) break;
         depth = p_view[2];
         opacity = blob[(size_t)P_OPACITY * N + i];
-        acut = sv.acut[i];  // render.comp:78 as a bound on `power` (computed at load from the opacity; the blend's cut)
+        if (AA) {
+            // comp = sqrt(det(cov2D) / det(cov2D + 0.3 I)), det_raw in det's operation order; <= 1 but for rounding, clamped so
+            // that an opacity <= 1 stays <= 1 (exp mode 3's premise).  det_raw <= 0: comp = 0, the splat stays in the lists and
+            // never contributes.  The cut is then the scaled opacity's, taken here (the load-time plane holds the unscaled one's).
+            const float det_raw = cov.c[0][0] * cov.c[1][1] - cov.c[1][0] * cov.c[0][1];
+            opacity = opacity * fminf(1.0f, sqrtf(fmaxf(0.0f, det_raw / det)));
+#if GS_PRE_AA_BISECT
+            acut = alpha_cut(opacity, reinterpret_cast<const uint2*>(kExpfTab));
+#else
+            acut = alpha_cut_seeded(opacity, reinterpret_cast<const uint2*>(kExpfTab));
+#endif
+        } else {
+            acut = sv.acut[i];  // render.comp:78 as a bound on `power` (computed at load from the opacity; the blend's cut)
+        }
         num_tiles = nt;
     } while (false);
     const bool vis = num_tiles != 0;
@@ -382,6 +402,7 @@ __device__ __forceinline__ void preprocess_one(const SceneView& sv, const gs_uni
     }
 }
 
+template <bool AA>
 __global__ __launch_bounds__(BLOCK) void k_preprocess(SceneView sv, PreUniforms pu, AttrView av) {
     __shared__ float4 s_stage[BLOCK / WAVE][kPreWaveLds];
     const gs_uniforms& u = pu.fp ? pu.fp->u : pu.u;  // uniform either way: scalar loads
@@ -399,17 +420,20 @@ __global__ __launch_bounds__(BLOCK) void k_preprocess(SceneView sv, PreUniforms 
         pu.counters->q_head = 0;
         pu.counters->q_bins_done = 0;
     }
-    preprocess_one(sv, u, av, i, i < sv.n, s_stage[threadIdx.x / WAVE]);
+    preprocess_one<AA>(sv, u, av, i, i < sv.n, s_stage[threadIdx.x / WAVE]);
 }
 
 void launch_preprocess(const SceneView& sv, const gs_uniforms& u, const AttrView& av, Counters* counters,
-                       const FrameParams* fp, uint64_t* stamps, hipStream_t s) {
+                       const FrameParams* fp, uint64_t* stamps, bool antialiased, hipStream_t s) {
     if (sv.n == 0) return;
     PreUniforms pu;
     pu.u = u;
     pu.counters = counters;
     pu.fp = fp;
     pu.stamps = stamps;
-    hipLaunchKernelGGL(k_preprocess, dim3((sv.n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, sv, pu, av);
+    if (antialiased)
+        hipLaunchKernelGGL(k_preprocess<true>, dim3((sv.n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, sv, pu, av);
+    else
+        hipLaunchKernelGGL(k_preprocess<false>, dim3((sv.n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, sv, pu, av);
 }
 }  // namespace gs

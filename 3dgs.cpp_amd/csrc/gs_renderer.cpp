@@ -67,9 +67,9 @@ struct FrameBuffers {
         int level = -1, hw_exp = 0, contract = 1, bin_shift = -1;
         uint32_t width = 0, height = 0, capacity = 0, cand_capacity = 0;
         const void *tile_order = nullptr, *ranges = nullptr, *sh16 = nullptr;
-        bool lockstep = false;
+        bool lockstep = false, antialiased = false;
         bool operator==(const GraphKey& o) const {
-            return lockstep == o.lockstep && level == o.level && hw_exp == o.hw_exp && contract == o.contract && bin_shift == o.bin_shift && width == o.width && height == o.height &&
+            return lockstep == o.lockstep && antialiased == o.antialiased && level == o.level && hw_exp == o.hw_exp && contract == o.contract && bin_shift == o.bin_shift && width == o.width && height == o.height &&
                    capacity == o.capacity && cand_capacity == o.cand_capacity && tile_order == o.tile_order && ranges == o.ranges && sh16 == o.sh16;
         }
     } graph_keys[2];
@@ -217,6 +217,7 @@ struct gs_renderer {
     // (with the contractions on, mode 3 runs as mode 1 whatever the scene holds: there is nothing to guard -- gs3d_hip.h)
     int blend_exp_mode() const { return exp_mode == 3 && !contract && !scene->unit_opacity ? 2 : exp_mode; }
     bool contract = false;       // the three FMA contractions GLSL permits in render.comp:66,87 (gs_set_blend_contraction); default: as written
+    bool antialiased = false;    // opacity scaled by the 0.3 dilation's compensation factor in k_preprocess (gs_set_antialiased)
     // The blend's LOCKSTEP (gs_blend.hip): the four waves of a tile take every chunk of its list together, so that their gathers of the
     // same records meet in L1.  Worth +25 % of the blend on trained-like scenes (L1-miss-bound: T(6e6) 505 -> 378 us; T(1e6) with three
     // frames in flight 2 675 -> 3 575 frames/s), -9 % on the S scenes (pair-loop-bound).  Nothing the renderer knows up front tells the
@@ -472,7 +473,7 @@ struct gs_renderer {
         // the frame's launches; `fp` non-null = replayable form (per-frame values read from fb.params), no span events
         uint64_t* const stamps = fb.stamps.p;
         auto passes = [&](const gs::FrameParams* fp, hipStream_t bstream) {
-            gs::launch_preprocess(sv, u, av, cnt, fp, stamps, stream);
+            gs::launch_preprocess(sv, u, av, cnt, fp, stamps, antialiased, stream);
             lap(3);
             if (!bin_local && n != 0) {
                 // ---- global depth order of the visible Gaussians: 4 x 8-bit stable passes on bits(depth) ----
@@ -568,6 +569,7 @@ struct gs_renderer {
             key.bin_shift = geo.bin_shift;
             key.hw_exp = blend_exp_mode();
             key.contract = contract ? 1 : 0;
+            key.antialiased = antialiased;
             key.width = u.width;
             key.height = u.height;
             key.capacity = capacity;
@@ -822,6 +824,7 @@ int gs_renderer_create(gs_scene* scene, gs_renderer** out) {
         if (const char* e = std::getenv("GS_GRAPH")) r->graph_mode = std::atoi(e) != 0;  // initial gs_set_graph_mode
         if (const char* e = std::getenv("GS_EXP_MODE")) r->exp_mode = std::min(3, std::max(0, std::atoi(e)));  // initial gs_set_exp_mode
         if (const char* e = std::getenv("GS_BLEND_CONTRACTION")) r->contract = std::atoi(e) != 0;  // initial gs_set_blend_contraction
+        if (const char* e = std::getenv("GS_ANTIALIASED")) r->antialiased = std::atoi(e) != 0;  // initial gs_set_antialiased
         if (const char* e = std::getenv("GS_BIN_SHIFT")) r->min_bin_shift = std::min(5, std::max(2, std::atoi(e)));  // default bin edge
         if (const char* e = std::getenv("GS_SORT_PATH")) {  // initial gs_set_sort_path, for hosts that cannot call it (the viewer)
             const int mode = std::atoi(e);
@@ -999,6 +1002,23 @@ int gs_set_blend_contraction(gs_renderer* r, int enabled) {
         r->drain();
         r->contract = enabled != 0;
     });
+}
+
+int gs_set_antialiased(gs_renderer* r, int enabled) {
+    return guarded([&] {
+        if (!r) throw Error(GS_ERR_INVALID, "renderer is null");
+        r->drain();
+        r->antialiased = enabled != 0;
+    });
+}
+
+int gs_get_antialiased(gs_renderer* r) {
+    int on = 0;
+    const int rc = guarded([&] {
+        if (!r) throw Error(GS_ERR_INVALID, "renderer is null");
+        on = r->antialiased ? 1 : 0;
+    });
+    return rc != 0 ? rc : on;
 }
 
 int gs_set_blend_lockstep(gs_renderer* r, int mode) {

@@ -75,6 +75,50 @@ void launch_alpha_cut(const float* blob, float* cut, uint32_t n, uint32_t stride
     hipLaunchKernelGGL(k_alpha_cut, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, blob + (size_t)P_OPACITY * stride, cut, n, beyond_unit);
 }
 
+// ---- test hook: the antialiased mode's per-frame cut (alpha_cut_seeded) against the load-time bisection, pattern by pattern
+__global__ __launch_bounds__(BLOCK) void k_alpha_cut_scan(uint32_t first_bits, uint64_t count, unsigned long long* __restrict__ mismatches,
+                                                          uint32_t* __restrict__ first_mismatch) {
+    const uint2* tab = reinterpret_cast<const uint2*>(kExpfTab);
+    unsigned long long bad = 0;
+    uint32_t first = 0xFFFFFFFFu;
+    for (uint64_t at = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; at < count; at += (uint64_t)gridDim.x * BLOCK) {
+        const uint32_t ob = first_bits + (uint32_t)at;
+        const float o = __uint_as_float(ob);
+        if (__float_as_uint(alpha_cut_seeded(o, tab)) != __float_as_uint(alpha_cut(o, tab))) {
+            ++bad;
+            first = min(first, ob);
+        }
+    }
+    if (bad) {
+        atomicAdd(mismatches, bad);
+        atomicMin(first_mismatch, first);
+    }
+}
+
+extern "C" int gs_debug_alpha_cut_scan(int device, uint32_t first_bits, uint64_t count, uint64_t* mismatches, uint32_t* first_mismatch) {
+    if (!mismatches || !first_mismatch || count == 0 || count > (1ull << 32)) return GS_ERR_INVALID;
+    if (hipSetDevice(device) != hipSuccess) return GS_ERR_DEVICE;
+    unsigned long long* d = nullptr;
+    if (hipMalloc(reinterpret_cast<void**>(&d), 2 * sizeof(unsigned long long)) != hipSuccess) return GS_ERR_NOMEM;
+    const unsigned long long init[2] = {0ull, 0xFFFFFFFFull};  // [0] count, [1] low word: the first mismatching pattern
+    int rc = GS_OK;
+    if (hipMemcpy(d, init, sizeof init, hipMemcpyHostToDevice) != hipSuccess) rc = GS_ERR_DEVICE;
+    if (rc == GS_OK) {
+        const uint64_t blocks = std::min<uint64_t>(65536, (count + BLOCK - 1) / BLOCK);
+        hipLaunchKernelGGL(k_alpha_cut_scan, dim3((uint32_t)blocks), dim3(BLOCK), 0, nullptr, first_bits, count, d,
+                           reinterpret_cast<uint32_t*>(d + 1));
+        if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) rc = GS_ERR_DEVICE;
+    }
+    unsigned long long out[2] = {0, 0};
+    if (rc == GS_OK && hipMemcpy(out, d, sizeof out, hipMemcpyDeviceToHost) != hipSuccess) rc = GS_ERR_DEVICE;
+    (void)hipFree(d);
+    if (rc == GS_OK) {
+        *mismatches = out[0];
+        *first_mismatch = (uint32_t)(out[1] & 0xFFFFFFFFull);
+    }
+    return rc;
+}
+
 // The scene's second copy in spatial order (gs_scene::make_spatial_copy): one thread per (Gaussian, 16-byte chunk of its 59 floats).
 __global__ __launch_bounds__(BLOCK) void k_permute_blob(const float* __restrict__ src, const uint32_t* __restrict__ perm,
                                                         float* __restrict__ dst, uint32_t n, uint32_t stride) {

@@ -235,6 +235,23 @@ int gs_set_exp_mode(gs_renderer* r, int mode);
  * long splats, where `power` is a difference of much larger terms.
  * GS_BLEND_CONTRACTION sets the initial mode. */
 int gs_set_blend_contraction(gs_renderer* r, int enabled);
+/* gs_set_antialiased -- scenes trained with ANTIALIASED rasterisation (gsplat rasterize_mode="antialiased", splatfacto's
+ * antialiased mode, Mip-Splatting's 2D filter) pay for the 0.3 px^2 that preprocess.comp:63-64 adds to the 2D covariance's
+ * diagonal by scaling each splat's opacity with a view-dependent factor:
+ *     comp = min(1, sqrt(max(0, det(cov2D) / det(cov2D + 0.3 I))))      opacity' = opacity * comp
+ * (binary32, det(cov2D) in the same operation order as the dilated determinant; the min only catches rounding past 1, so an
+ * opacity <= 1 stays <= 1).  0 (default): off, the reference's pipeline; 1: on.  No reference counterpart: the reference is
+ * the non-antialiased pipeline.  Opacity enters neither the cull, the radius, the tile box nor the depth order, so the
+ * per-tile lists, the ranges and the depth order are the same as with the mode off; only the record's opacity and alpha cut
+ * change (the cut is then taken per frame from opacity', GS_STAGE_ALPHA_CUT shows it).  A frame of scene S with the mode on
+ * is bit-identical to the frame, with the mode off, of the scene S' whose opacities are the opacity' values
+ * (GS_STAGE_CONIC_OPACITY .w) of that view.  det(cov2D) <= 0 gives comp = 0: the splat stays in the lists and never
+ * contributes.  Mip-Splatting's 3D filter (the filter_3D PLY property) and other 2D kernel sizes are out of scope: they
+ * change the box and the lists.  Frames already queued finish with the previous setting.  GS_ANTIALIASED=1 sets the initial
+ * value at renderer creation (the viewer, pose_shard_host). */
+int gs_set_antialiased(gs_renderer* r, int enabled);
+/* 1 if the antialiased mode is on, 0 if off, a negative gs_status on error. */
+int gs_get_antialiased(gs_renderer* r);
 /* Replay frames as ONE captured HIP graph each (answers VulkanContext.h:6 / Renderer.cpp:391-395, 532-717: the
  * reference re-records its render command buffer every frame because dispatch sizes depend on D; here every grid is
  * data-independent, so a frame's launches are captured once per configuration -- resolution, depth-order level,
@@ -280,6 +297,10 @@ int gs_debug_download(gs_renderer* r, int stage, void* dst, uint64_t bytes);
  * [0] max over x in [-16, 0] of |v_exp_f32(fl(x log2e)) - expf(x)| / expf(x) - E1 |x|, [1] the same ratio's max over [-1, 0],
  * [2] the guard's E0 (must exceed [0] + 2^-23), [3] its E1. */
 int gs_debug_expf_scan(int device, uint32_t first_bits, uint64_t count, uint64_t* block_sums, uint64_t blocks_capacity, double* guard);
+/* Test hook (tests/test_gpu_antialiased.py): for every opacity with bit pattern in [first_bits, first_bits + count), compare ON
+ * THE DEVICE the per-frame alpha cut of the antialiased mode with the load-time one (the full bisection); *mismatches = how
+ * many differ, *first_mismatch = the lowest such pattern (0xFFFFFFFF if none). */
+int gs_debug_alpha_cut_scan(int device, uint32_t first_bits, uint64_t count, uint64_t* mismatches, uint32_t* first_mismatch);
 /* The hipStream_t the renderer enqueues on (for HIP-event timing by the caller). */
 void* gs_renderer_stream(gs_renderer* r);
 
