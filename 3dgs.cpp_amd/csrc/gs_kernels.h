@@ -5,10 +5,10 @@
 #include <stdint.h>
 
 #include "../../include/gs3d_hip.h"
+#include "gs_levels.h"  // kTile, kBinSortLevels, kBinSlabLevel, kBinSortLimit
 
 namespace gs {
 
-constexpr int kTile = 16;             // TILE_WIDTH == TILE_HEIGHT, common.glsl:1-2
 constexpr int kSortTileKeys = 2048;   // keys per radix tile (256 threads x 8)
 constexpr int kSortMaxBlocks = 1024;  // fixed sort grid (data-dependent sizes stay on the device)
 
@@ -100,12 +100,7 @@ struct FrameParams {
     uint64_t* host_stamps;  // pinned, [ST_COUNT]
 };
 
-// candidates per bin that k_bin_fast orders in LDS at depth-order level 0 .. 3 (8 bytes of LDS each); level 4: k_bin_slabs,
-// bins of up to 65535 taken in depth slabs of <= 12288; level 5 = the global path
-constexpr int kBinSortLevels = 5;
-constexpr int kBinSlabLevel = 4;
-constexpr uint32_t kBinSortLimit[kBinSortLevels] = {4096, 8192, 12288, 16384, 65535};
-constexpr int kBinSortMax = 16384;
+constexpr int kBinSortMax = 16384;  // the largest in-LDS order (gs_levels.h: kBinSortLimit[3])
 constexpr uint32_t kSlabDescBytes = 288, kSlabCapacity = 8192, kSlabWorkGroups = 512, kQueueWorkGroups = 256;
 
 void launch_cov3d(const float* blob, float* cov3d, uint32_t n, uint32_t stride, hipStream_t s);

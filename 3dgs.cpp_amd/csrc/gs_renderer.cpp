@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "gs_blend_tuner.h"
+#include "gs_depth_policy.h"
 #include "gs_internal.h"
 
 using namespace gs_host;
@@ -63,14 +64,17 @@ struct FrameBuffers {
     // ... one per setting of the blend's lockstep: the tuner flips it several times per measurement, and re-capturing the frame on every
     // flip would make the measurement weigh the capture (round-5 advisor finding)
     hipGraphExec_t graph_execs[2] = {nullptr, nullptr};
+    // (an aggregate: enqueue initialises the fields positionally, in the order they are declared and compared here)
     struct GraphKey {
-        int level = -1, hw_exp = 0, contract = 1, bin_shift = -1;
+        int level = -1, bin_shift = -1, hw_exp = 0, contract = 1;
+        bool antialiased = false, lockstep = false;
         uint32_t width = 0, height = 0, capacity = 0, cand_capacity = 0;
         const void *tile_order = nullptr, *ranges = nullptr, *sh16 = nullptr;
-        bool lockstep = false, antialiased = false;
         bool operator==(const GraphKey& o) const {
-            return lockstep == o.lockstep && antialiased == o.antialiased && level == o.level && hw_exp == o.hw_exp && contract == o.contract && bin_shift == o.bin_shift && width == o.width && height == o.height &&
-                   capacity == o.capacity && cand_capacity == o.cand_capacity && tile_order == o.tile_order && ranges == o.ranges && sh16 == o.sh16;
+            return level == o.level && bin_shift == o.bin_shift && hw_exp == o.hw_exp && contract == o.contract &&
+                   antialiased == o.antialiased && lockstep == o.lockstep &&
+                   width == o.width && height == o.height && capacity == o.capacity && cand_capacity == o.cand_capacity &&
+                   tile_order == o.tile_order && ranges == o.ranges && sh16 == o.sh16;
         }
     } graph_keys[2];
     void drop_graph(int which) {
@@ -142,6 +146,10 @@ struct FrameBuffers {
         HIP_CHECK(hipStreamSynchronize(stream));
         if (blend_stream) HIP_CHECK(hipStreamSynchronize(blend_stream));
     }
+    void sync_nothrow() const {  // (the destructor's path)
+        (void)hipStreamSynchronize(stream);
+        if (blend_stream) (void)hipStreamSynchronize(blend_stream);
+    }
     ~FrameBuffers() {
         drop_graph();
         if (stream) (void)hipStreamDestroy(stream);
@@ -160,7 +168,7 @@ struct FrameSlot {
     uint64_t* h_stamps = nullptr;        // pinned [ST_COUNT]: the frame's timeline, written by its kernels and copied here by k_frame_end
     gs::FrameParams* h_params = nullptr;  // pinned staging of the frame's parameter block (graph replay)
     bool timed = false;
-    int level = 0;  // the depth-order level this frame ran at (gs_renderer::level)
+    int level = 0;  // the depth-order level this frame ran at (DepthPolicy::frame_level)
     int bin_shift = 3;
     bool lockstep = false;      // the blend's lockstep setting this frame ran with
     uint32_t tune_round = 0;    // ... and the tuner's round it belongs to (samples of an earlier round are ignored)
@@ -192,23 +200,11 @@ struct gs_renderer {
 
     gs_frame_stats last{};  // stats of the most recently retired frame
 
-    // How a frame's per-tile lists get their depth order.  level 0 .. 4: bin-local -- the
-    // workgroup that builds a bin's lists orders its candidates in LDS first (up to 4096 / 8192 / 12288 / 16384 per bin, or,
-    // level 4, up to 65535 in depth slabs of <= 12288; 6 kernels per frame); level 5: global -- the V visible Gaussians are ordered first (12 more kernels; any bin size).
-    // sort_mode 0 = automatic: start at level 0; a bin that does not fit re-runs the frame at the level its size asks
-    // for; after 32 frames that would have fitted the level below, go back down.
-    int sort_mode = 0;           // 0 auto, 1 global depth order, 2 bin-local (forced: a bin beyond 16384 is an error)
-    int level = 0;
-    uint32_t frames_since_fallback = 0;
-    // Depth slabs (level 4) can fail for reasons that have nothing to do with the bin's size -- one depth bucket beyond a slab, a
-    // run of more than 64 exactly equal depths inside one, more slabs than descriptors: the frame then goes to the global path,
-    // and since `max_bin` still fits level 4 the step-down below would send it straight back into the same failure every 32
-    // frames, for ever (round-3 advisor finding).  Each such failure doubles the frames the renderer stays on the global path
-    // before it tries the slabs again (32 .. 8192); 64 clean frames at level 4 reset it.
-    uint32_t slab_hold = 32, slab_clean_frames = 0;
-    static constexpr int kGlobalLevel = gs::kBinSortLevels;
-    static uint32_t level_limit(int lv) { return gs::kBinSortLimit[lv]; }
-    int frame_level() const { return sort_mode == 1 ? kGlobalLevel : level; }
+    // How a frame's per-tile lists get their depth order, and the bin grid it runs with: the level of
+    // the next frame, what an overflowed frame asks for, when to step back down -- all of it in gs_depth_policy.h.
+    // GS_BIN_SHIFT sets its min_bin_shift, GS_SORT_PATH / gs_set_sort_path its sort_mode.
+    DepthPolicy policy;
+    static constexpr int kGlobalLevel = DepthPolicy::kGlobalLevel;
     bool graph_mode = false;     // replay each frame as one captured HIP graph (gs_set_graph_mode)
     // the blend's exp() (gs_set_exp_mode): 3 (default) the hardware's v_exp_f32 under the guard of render.comp:82 -- the reference's
     // decisions, its pixels to rounding noise; 2 libm's expf restated in binary64 -- the reference's bits; 0 pipeline polynomial, 1 v_exp_f32
@@ -225,7 +221,6 @@ struct gs_renderer {
     // lockstep where it wins by 3 %, and looks again every 4096 frames or when the frame's shape changes.  GS_BLEND_LOCKSTEP=0 / 1 (or gs_set_blend_lockstep)
     // pins it; the tuner then rests.  One tuner per frame shape (BlendTunerBank): alternating resolutions do not restart each other.
     BlendTunerBank tuners;
-    int min_bin_shift = 3;       // GS_BIN_SHIFT: log2 of the default bin edge in tiles (8 x 8 tiles)
     // GS_L1_DENSE_MIN: scenes of at least this many Gaussians hand level 1 the dense lists of visible Gaussians (measured
     // A/B, profiles/r03_l1_dense_lists_ab.txt: 6 M Gaussians +2 % one frame at a time, +2..7 % with three in flight --
     // level 1 is several rounds of workgroups there; 1 M: -0.5 %, level 1 is one round of workgroups bound by its round
@@ -251,8 +246,6 @@ struct gs_renderer {
                              "level2 %.3f, blend %.3f, closing events %.3f\n", (unsigned long long)(frames_enqueued - 1), ms(0, 9), ms(0, 1), ms(1, 2), ms(2, 3),
                      ms(3, 4), ms(4, 5), ms(5, 6), ms(6, 7), ms(7, 9));
     }
-    bool refined = false;        // bins of half that edge: taken when a bin outgrows the largest in-LDS order
-    bool settle_level = false;   // the next clean frame at the level a refinement jumped to tells which level its bins really need
     bool have_frame = false;
     uint32_t retries = 0;        // lifetime count of re-run frames (statistics only)
     uint32_t redo_chain = 0;     // consecutive re-runs since a frame last retired cleanly: the runaway guard
@@ -382,34 +375,10 @@ struct gs_renderer {
         order_ty = ty;
     }
 
-    // The bin grid of a frame: bins of S x S tiles, at most 32 x 32 of them, padded to a 16- or 32-wide grid.
-    struct BinGeometry {
-        int bin_shift, grid_shift;
-        uint32_t bins_x, bins_y;
-    };
-    static bool grid_fits(uint32_t tx, uint32_t ty, int s) { return (((tx - 1) >> s) + 1) <= 32 && (((ty - 1) >> s) + 1) <= 32; }
-    // the coarsest-allowed choice: bins of 8 x 8 tiles (or GS_BIN_SHIFT), larger only to keep the grid within 32 x 32
-    static int base_shift(uint32_t tx, uint32_t ty, int min_shift) {
-        int s = std::max(2, min_shift);
-        while (!grid_fits(tx, ty, s)) ++s;
-        return s;
-    }
     BinGeometry bin_geometry(uint32_t tx, uint32_t ty) const {
-        int s = base_shift(tx, ty, min_bin_shift);
-        if (s > 5) throw Error(GS_ERR_INVALID, "resolution too large for the tile binning (max 16384 x 16384)");
-        // `refined`: a bin outgrew the largest in-LDS order -> bins of half the edge (a quarter of the candidates or so)
-        if (refined && s > 2 && grid_fits(tx, ty, s - 1)) --s;
         BinGeometry g;
-        g.bin_shift = s;
-        g.bins_x = ((tx - 1) >> s) + 1;
-        g.bins_y = ((ty - 1) >> s) + 1;
-        g.grid_shift = (g.bins_x <= 16 && g.bins_y <= 16) ? 4 : 5;
+        if (!policy.bin_geometry(tx, ty, &g)) throw Error(GS_ERR_INVALID, "resolution too large for the tile binning (max 16384 x 16384)");
         return g;
-    }
-    bool can_refine(const gs_uniforms& u) const {
-        const uint32_t tx = (u.width + gs::kTile - 1) / gs::kTile, ty = (u.height + gs::kTile - 1) / gs::kTile;
-        const int s = base_shift(tx, ty, min_bin_shift);
-        return !refined && s > 2 && s <= 5 && grid_fits(tx, ty, s - 1);
     }
 
     void enqueue(const gs_uniforms& u, float* d_rgba, uint8_t* d_bgra) {
@@ -418,19 +387,19 @@ struct gs_renderer {
         FrameBuffers& fb = sets[frames_enqueued % num_sets];
         hipStream_t stream = fb.stream;
         const uint32_t n = static_cast<uint32_t>(scene->n);
-        const uint32_t tx = (u.width + gs::kTile - 1) / gs::kTile, ty = (u.height + gs::kTile - 1) / gs::kTile;
+        const uint32_t tx = tiles_across(u.width), ty = tiles_across(u.height);
         if (tx > 65535 || ty > 65535) throw Error(GS_ERR_INVALID, "resolution too large (tile box is 16-bit)");
         const uint64_t nt = static_cast<uint64_t>(tx) * ty;
         auto lacks_buffers = [&](int at_level) {
             return 2 * nt > fb.ranges.n || (at_level >= kGlobalLevel && !fb.dkeys[0].p) || (at_level == gs::kBinSlabLevel && !fb.slabs.p);
         };
-        if (lacks_buffers(frame_level())) {
+        if (lacks_buffers(policy.frame_level())) {
             // (re)allocation: wait for queued frames that still use the old buffers.  Retiring them may re-run a frame at another
             // depth-order level or bin size (retire_oldest): what THIS frame runs with is decided after the wait, not before
             // -- a frame queued with the level of before the wait fails at once and, being judged as a failure of the new
             // level, used to push the renderer onto the global path for slab_hold frames
             drain();
-            const int at_level = frame_level();
+            const int at_level = policy.frame_level();
             fb.ranges.ensure(2 * nt);
             if (at_level >= kGlobalLevel) fb.ensure_depth_order();
             if (at_level == gs::kBinSlabLevel && !fb.slabs.p) {
@@ -444,7 +413,7 @@ struct gs_renderer {
         const BlendTuner& tuner = tuners.current();
         const bool lockstep = tuner.current();
         const BinGeometry geo = bin_geometry(tx, ty);
-        const int lv = frame_level();
+        const int lv = policy.frame_level();
         const bool bin_local = lv < kGlobalLevel;
         num_tiles = nt;
         ensure_tile_order(tx, ty);
@@ -564,20 +533,10 @@ struct gs_renderer {
         if (replay) {
             *sl.h_params = gs::FrameParams{u, d_rgba, d_bgra, sl.h_counters, sl.h_stamps};
             HIP_CHECK(hipMemcpyAsync(fb.params.p, sl.h_params, sizeof(gs::FrameParams), hipMemcpyHostToDevice, stream));
-            FrameBuffers::GraphKey key;
-            key.level = lv;
-            key.bin_shift = geo.bin_shift;
-            key.hw_exp = blend_exp_mode();
-            key.contract = contract ? 1 : 0;
-            key.antialiased = antialiased;
-            key.width = u.width;
-            key.height = u.height;
-            key.capacity = capacity;
-            key.cand_capacity = cand_capacity;
-            key.tile_order = tile_order.p;
-            key.ranges = fb.ranges.p;
-            key.sh16 = sv.sh16;
-            key.lockstep = lockstep;
+            const FrameBuffers::GraphKey key{lv, geo.bin_shift, blend_exp_mode(), contract ? 1 : 0,
+                                             antialiased, lockstep,
+                                             u.width, u.height, capacity, cand_capacity,
+                                             tile_order.p, fb.ranges.p, sv.sh16};
             const int gi = lockstep ? 1 : 0;
             if (!fb.graph_execs[gi] || !(key == fb.graph_keys[gi])) {  // first frame of this configuration: capture its launches
                 fb.drop_graph(gi);
@@ -623,124 +582,97 @@ struct gs_renderer {
     }
 
     FrameSlot& oldest() { return slots[(frames_enqueued - pending) % kSlots]; }
+    FrameSlot& queued(int k) { return slots[(frames_enqueued - pending + k) % kSlots]; }
 
-    // Wait for the oldest queued frame; record its stats; on instance-buffer overflow grow the
-    // buffers and re-run it and every frame queued behind it (Renderer.cpp:541-563 retries too).
+    // Wait for the oldest queued frame and record its stats; if it overflowed -- the instance or candidate buffers
+    // (Renderer.cpp:541-563 grows and retries too) or a bin its depth-order level -- re-run it and every frame queued behind it.
     void retire_oldest() {
         FrameSlot& sl = oldest();
         HIP_CHECK(hipEventSynchronize(sl.done));
         if (sl.h_counters->overflow) {
-            for (auto& fb : sets)
-                if (fb.ready) fb.sync();
-            struct Redo {
-                gs_uniforms u;
-                float* rgba;
-                uint8_t* bgra;
-            };
-            std::vector<Redo> redo;
-            uint64_t need = 0, need_cand = 0;
-            uint32_t fullest = 0;
-            bool grow = false, bin_too_big = false;
-            for (int k = 0; k < pending; ++k) {
-                FrameSlot& q = slots[(frames_enqueued - pending + k) % kSlots];
-                redo.push_back({q.u, q.rgba, q.bgra});
-                if (q.h_counters->overflow & 1u) {
-                    grow = true;
-                    // which of the two ran over: the level-1 candidates (E1: the frame's instance count then means nothing -- its
-                    // bins were skipped) or the per-tile lists (D)
-                    if (q.h_counters->bin_entries > cand_capacity) need_cand = std::max<uint64_t>(need_cand, q.h_counters->bin_entries);
-                    else need = std::max<uint64_t>(need, q.h_counters->instances);
-                }
-                // (a frame that ran with another level or bin size than the renderer's current ones says nothing about those)
-                const uint32_t qtx = (q.u.width + gs::kTile - 1) / gs::kTile, qty = (q.u.height + gs::kTile - 1) / gs::kTile;
-                const bool current = q.level == frame_level() && q.bin_shift == bin_geometry(qtx, qty).bin_shift;
-                if (q.level < kGlobalLevel && (q.h_counters->overflow & 2u) && current) bin_too_big = true;
-                if (current) fullest = std::max(fullest, q.h_counters->max_bin);
-            }
-            const int failed_level = sl.level;
-            if (debug_levels) {  // GS_DEBUG_LEVELS: what made the renderer change its depth-order level
-                std::fprintf(stderr, "[gs3d] frame %llu overflowed at level %d (refined %d, hold %u):", (unsigned long long)(frames_enqueued - pending),
-                             failed_level, (int)refined, slab_hold);
-                for (int k = 0; k < pending; ++k) {
-                    const FrameSlot& q = slots[(frames_enqueued - pending + k) % kSlots];
-                    std::fprintf(stderr, " [lvl %d bin 2^%d ovf %u max_bin %u E1 %u D %u slabs %u]", q.level, q.bin_shift, q.h_counters->overflow,
-                                 q.h_counters->max_bin, q.h_counters->bin_entries, q.h_counters->instances, q.h_counters->slabs);
-                }
-                std::fprintf(stderr, " capacity %u candidates %u\n", capacity, cand_capacity);
-            }
-            // the queued frames are dropped from the ring first: whatever is thrown below, the renderer stays usable
-            frames_enqueued -= pending;
-            pending = 0;
-            prev_retired = false;
-            if (bin_too_big) {  // a bin outgrew the in-LDS order of this level: one level up from here on
-                const bool slabs_unsuitable = failed_level == gs::kBinSlabLevel && fullest <= level_limit(gs::kBinSlabLevel);
-                if (slabs_unsuitable) {  // not the bin's size: equal or crowded depths (see slab_hold)
-                    slab_hold = std::min<uint32_t>(slab_hold * 2, 8192);
-                    slab_clean_frames = 0;
-                }
-                int wanted = failed_level + 1;
-                while (wanted < kGlobalLevel && fullest > level_limit(wanted)) ++wanted;
-                if (wanted >= gs::kBinSlabLevel && can_refine(sl.u)) {  // smaller bins before slabs or the global path
-                    refined = true;
-                    wanted = gs::kBinSlabLevel - 1;  // (what the smaller bins hold is not known yet: the largest in-LDS order)
-                    settle_level = true;
-                } else {
-                    if (sort_mode == 2 && wanted >= kGlobalLevel)
-                        throw Error(GS_ERR_OVERFLOW, slabs_unsuitable
-                                        ? "a bin's depths are too crowded for the bin-local order (one depth bucket beyond a slab, or more than 64 equal depths in one): needs the global depth-order path"
-                                        : "a bin holds more candidates than the bin-local sort can order");
-                    level = std::max(level, wanted);
-                }
-                if (refined) level = std::max(level, wanted);
-                frames_since_fallback = 0;
-            }
-            // runaway guard: one frame may need a path fall-back and a few grow steps (each grow is sized from the counts
-            // the overflowing frame reported, so it converges at once unless the chunk table and the lists take turns)
-            if (++redo_chain > 8) throw Error(GS_ERR_OVERFLOW, "instance buffers overflowed repeatedly");
-            if (grow && need_cand > cand_capacity) {
-                need_cand = need_cand + need_cand / 2 + 4096;  // 1.5x head-room: a moving camera should not re-grow every few frames
-                if (need_cand > kMaxInstances) throw Error(GS_ERR_OVERFLOW, "more than 2^30 level-1 candidates");
-                set_cand_capacity(static_cast<uint32_t>(need_cand));
-            }
-            if (grow && need > capacity) {
-                need = need + need / 2 + 4096;
-                if (need > kMaxInstances) throw Error(GS_ERR_OVERFLOW, "more than 2^30 tile instances");
-                set_capacity(static_cast<uint32_t>(need));
-            }
-            ++retries;
-            for (const Redo& f : redo) enqueue(f.u, f.rgba, f.bgra);
+            rerun_queued();
             return;
         }
         redo_chain = 0;
-        if (sl.level == gs::kBinSlabLevel && ++slab_clean_frames >= 64) slab_hold = 32;  // the slabs work on this scene (again)
-        if (settle_level && sort_mode != 1 && sl.level == level && level < kGlobalLevel) {
-            // the first clean frame after the bins were refined: its fullest bin says which order the smaller bins need -- straight
-            // there instead of 32 frames at the largest one per step down (config C: level 3 -> 2, k_bin_fast<16> -> <12>)
-            while (level > 0 && sl.h_counters->max_bin <= level_limit(level - 1) * 7 / 8) --level;
-            frames_since_fallback = 0;
-            settle_level = false;
-        }
-        if (sort_mode != 1 && level > 0) {  // one level down once the bins have fitted it for a while
-            if (sl.h_counters->max_bin <= level_limit(level - 1) * 7 / 8) {
-                // (from the global path back to the slabs: only after slab_hold frames, see there)
-                if (++frames_since_fallback >= (level == kGlobalLevel ? slab_hold : 32u)) {
-                    --level;
-                    frames_since_fallback = 0;
-                }
-            } else {
-                frames_since_fallback = 0;
+        policy.frame_retired(sl.level, sl.h_counters->max_bin);
+        last = frame_stats(sl);
+        have_frame = true;
+        const float v[7] = {last.ms_preprocess, last.ms_prefix_sum, last.ms_preprocess_sort, last.ms_sort,
+                            last.ms_tile_boundary, last.ms_render, last.ms_total};
+        for (int k = 0; k < 7; ++k) total_ms[k] += v[k];
+        ++total_frames;
+        ++lifetime_frames;
+        note_completion(sl, last.ms_total);
+        --pending;
+    }
+
+    // The oldest queued frame overflowed: every queued frame is dropped from the ring, the policy picks the level and the bins,
+    // the buffers grow to what the frames counted, and the frames are enqueued again.
+    void rerun_queued() {
+        for (auto& fb : sets)
+            if (fb.ready) fb.sync();
+        struct Redo {
+            gs_uniforms u;
+            float* rgba;
+            uint8_t* bgra;
+        };
+        std::vector<Redo> redo;
+        std::vector<DepthPolicy::QueuedFrame> ran;
+        uint64_t need = 0, need_cand = 0;  // (0: that buffer did not run over)
+        for (int k = 0; k < pending; ++k) {
+            const FrameSlot& q = queued(k);
+            const gs::Counters& c = *q.h_counters;
+            redo.push_back({q.u, q.rgba, q.bgra});
+            ran.push_back({q.level, q.bin_shift, q.u.width, q.u.height, c.overflow, c.max_bin});
+            if (c.overflow & 1u) {
+                // which of the two ran over: the level-1 candidates (E1: the frame's instance count then means nothing -- its
+                // bins were skipped) or the per-tile lists (D)
+                if (c.bin_entries > cand_capacity) need_cand = std::max<uint64_t>(need_cand, c.bin_entries);
+                else need = std::max<uint64_t>(need, c.instances);
             }
-        } else if (sort_mode != 1 && refined) {  // at the smallest order with the small bins: try the default bins again
-            if (sl.h_counters->max_bin <= level_limit(0) / 2) {  // four times the tiles per bin should still fit level 3 (<= 16384)
-                if (++frames_since_fallback >= 32) {
-                    refined = false;
-                    level = gs::kBinSlabLevel - 1;
-                    frames_since_fallback = 0;
-                }
-            } else {
-                frames_since_fallback = 0;
-            }
         }
+        if (debug_levels) report_overflow();
+        // the queued frames are dropped from the ring first: whatever is thrown below, the renderer stays usable
+        frames_enqueued -= pending;
+        pending = 0;
+        prev_retired = false;
+        switch (policy.frames_overflowed(ran.data(), static_cast<int>(ran.size()))) {
+            case DepthPolicy::kDepthsTooCrowded:
+                throw Error(GS_ERR_OVERFLOW, "a bin's depths are too crowded for the bin-local order (one depth bucket beyond a slab, or more than 64 equal depths in one): needs the global depth-order path");
+            case DepthPolicy::kBinTooFull:
+                throw Error(GS_ERR_OVERFLOW, "a bin holds more candidates than the bin-local sort can order");
+            case DepthPolicy::kRerun:
+                break;
+        }
+        // runaway guard: one frame may need a path fall-back and a few grow steps (each grow is sized from the counts
+        // the overflowing frame reported, so it converges at once unless the chunk table and the lists take turns)
+        if (++redo_chain > 8) throw Error(GS_ERR_OVERFLOW, "instance buffers overflowed repeatedly");
+        if (need_cand > cand_capacity) {
+            need_cand = need_cand + need_cand / 2 + 4096;  // 1.5x head-room: a moving camera should not re-grow every few frames
+            if (need_cand > kMaxInstances) throw Error(GS_ERR_OVERFLOW, "more than 2^30 level-1 candidates");
+            set_cand_capacity(static_cast<uint32_t>(need_cand));
+        }
+        if (need > capacity) {
+            need = need + need / 2 + 4096;
+            if (need > kMaxInstances) throw Error(GS_ERR_OVERFLOW, "more than 2^30 tile instances");
+            set_capacity(static_cast<uint32_t>(need));
+        }
+        ++retries;
+        for (const Redo& f : redo) enqueue(f.u, f.rgba, f.bgra);
+    }
+
+    void report_overflow() {  // GS_DEBUG_LEVELS: what made the renderer change its depth-order level
+        std::fprintf(stderr, "[gs3d] frame %llu overflowed at level %d (refined %d, hold %u):", (unsigned long long)(frames_enqueued - pending),
+                     oldest().level, (int)policy.refined, policy.slab_hold);
+        for (int k = 0; k < pending; ++k) {
+            const FrameSlot& q = queued(k);
+            std::fprintf(stderr, " [lvl %d bin 2^%d ovf %u max_bin %u E1 %u D %u slabs %u]", q.level, q.bin_shift, q.h_counters->overflow,
+                         q.h_counters->max_bin, q.h_counters->bin_entries, q.h_counters->instances, q.h_counters->slabs);
+        }
+        std::fprintf(stderr, " capacity %u candidates %u\n", capacity, cand_capacity);
+    }
+
+    gs_frame_stats frame_stats(const FrameSlot& sl) const {
         gs_frame_stats st{};
         st.num_gaussians = scene->n;
         st.num_visible = sl.h_counters->visible;
@@ -773,32 +705,35 @@ struct gs_renderer {
             st.ms_render = span(gs::ST_BLEND, gs::ST_END);
         }
         st.retries = retries;
-        last = st;
-        have_frame = true;
-        const float v[7] = {st.ms_preprocess, st.ms_prefix_sum, st.ms_preprocess_sort, st.ms_sort,
-                            st.ms_tile_boundary, st.ms_render, st.ms_total};
-        for (int k = 0; k < 7; ++k) total_ms[k] += v[k];
-        ++total_frames;
-        ++lifetime_frames;
-        {   // frames on different streams may finish out of order: measure against the latest completion so far
-            const uint64_t idx = frames_enqueued - pending;  // this frame
-            if (prev_retired) {
-                // (the frames' END stamps: one clock for every stream)
-                const int64_t dticks = static_cast<int64_t>(ts[gs::ST_END] - slots[latest_done % kSlots].h_stamps[gs::ST_END]);
-                const float dt = dticks > 0 ? static_cast<float>(static_cast<double>(dticks) * tick_ms) : 0.0f;
-                {
-                    if (intervals.size() >= kIntervalRing) intervals.erase(intervals.begin(), intervals.begin() + kIntervalRing / 2);
-                    intervals.push_back(dt > 0.0f ? dt : 0.0f);  // 0: it had already finished when its predecessor did
-                    // the blend tuner compares completion rates (or, for a host-paced consumer, the frames' own spans: BlendTuner::cost)
-                    tuners.sample(sl.tune_shape, sl.u.width, sl.u.height, dt > 0.0f ? dt : 0.0f, st.ms_total, sl.lockstep, sl.tune_round);
-                    if (dt > 0.0f) latest_done = idx;
-                }
-            } else {
-                latest_done = idx;
-            }
-            prev_retired = true;
+        return st;
+    }
+
+    // The completion-to-completion interval the oldest queued frame closes, for gs_get_frame_intervals and the blend tuner.
+    // Frames on different streams may finish out of order: measured against the latest completion so far.
+    void note_completion(const FrameSlot& sl, float ms_total) {
+        const uint64_t idx = frames_enqueued - pending;  // this frame
+        if (prev_retired) {
+            // (the frames' END stamps: one clock for every stream)
+            const int64_t dticks = static_cast<int64_t>(sl.h_stamps[gs::ST_END] - slots[latest_done % kSlots].h_stamps[gs::ST_END]);
+            const float dt = dticks > 0 ? static_cast<float>(static_cast<double>(dticks) * tick_ms) : 0.0f;  // 0: it had already finished when its predecessor did
+            if (intervals.size() >= kIntervalRing) intervals.erase(intervals.begin(), intervals.begin() + kIntervalRing / 2);
+            intervals.push_back(dt);
+            // the blend tuner compares completion rates (or, for a host-paced consumer, the frames' own spans: BlendTuner::cost)
+            tuners.sample(sl.tune_shape, sl.u.width, sl.u.height, dt, ms_total, sl.lockstep, sl.tune_round);
+            if (dt > 0.0f) latest_done = idx;
+        } else {
+            latest_done = idx;
         }
-        --pending;
+        prev_retired = true;
+    }
+
+    // what gs_get_stats and gs_poll_stats report: the most recently retired frame, the renderer's current figures over it
+    void latest_stats(gs_frame_stats* out) const {
+        *out = last;
+        out->num_gaussians = scene->n;
+        out->instance_capacity = capacity;
+        out->retries = retries;
+        out->blend_redo = out->blend_resolved = 0;  // (the blend's own counters: gs_get_stats reads them from the device)
     }
 
     void make_room() {
@@ -825,11 +760,11 @@ int gs_renderer_create(gs_scene* scene, gs_renderer** out) {
         if (const char* e = std::getenv("GS_EXP_MODE")) r->exp_mode = std::min(3, std::max(0, std::atoi(e)));  // initial gs_set_exp_mode
         if (const char* e = std::getenv("GS_BLEND_CONTRACTION")) r->contract = std::atoi(e) != 0;  // initial gs_set_blend_contraction
         if (const char* e = std::getenv("GS_ANTIALIASED")) r->antialiased = std::atoi(e) != 0;  // initial gs_set_antialiased
-        if (const char* e = std::getenv("GS_BIN_SHIFT")) r->min_bin_shift = std::min(5, std::max(2, std::atoi(e)));  // default bin edge
+        if (const char* e = std::getenv("GS_BIN_SHIFT")) r->policy.min_bin_shift = std::min(5, std::max(2, std::atoi(e)));  // default bin edge
         if (const char* e = std::getenv("GS_SORT_PATH")) {  // initial gs_set_sort_path, for hosts that cannot call it (the viewer)
             const int mode = std::atoi(e);
             if (mode < 0 || mode > 2) throw Error(GS_ERR_INVALID, "GS_SORT_PATH must be 0 (auto), 1 (global) or 2 (bin-local)");
-            r->sort_mode = mode;
+            r->policy.sort_mode = mode;
         }
         *out = r.release();
     });
@@ -838,10 +773,7 @@ int gs_renderer_create(gs_scene* scene, gs_renderer** out) {
 void gs_renderer_destroy(gs_renderer* r) {
     if (r)
         for (auto& fb : r->sets)
-            if (fb.ready) {
-                (void)hipStreamSynchronize(fb.stream);
-                if (fb.blend_stream) (void)hipStreamSynchronize(fb.blend_stream);
-            }
+            if (fb.ready) fb.sync_nothrow();
     delete r;
 }
 
@@ -906,12 +838,8 @@ int gs_get_stats(gs_renderer* r, gs_frame_stats* out) {
     return guarded([&] {
         if (!r || !out) throw Error(GS_ERR_INVALID, "null argument");
         r->drain();
-        *out = r->last;
-        out->num_gaussians = r->scene->n;
-        out->instance_capacity = r->capacity;
-        out->retries = r->retries;
+        r->latest_stats(out);
         // written by the blend itself, after it published the other counters: read from the device (everything has retired)
-        out->blend_redo = out->blend_resolved = 0;
         if (r->have_frame && r->last_set && r->last_set->counters.p) {
             gs::Counters c{};
             HIP_CHECK(hipMemcpy(&c, r->last_set->counters.p, sizeof c, hipMemcpyDeviceToHost));
@@ -931,11 +859,7 @@ int gs_poll_stats(gs_renderer* r, gs_frame_stats* out, uint64_t* frames_retired)
             HIP_CHECK(e);
             r->retire_oldest();
         }
-        *out = r->last;
-        out->num_gaussians = r->scene->n;
-        out->instance_capacity = r->capacity;
-        out->retries = r->retries;
-        out->blend_redo = out->blend_resolved = 0;
+        r->latest_stats(out);
         if (frames_retired) *frames_retired = r->lifetime_frames;
     });
 }
@@ -979,10 +903,7 @@ int gs_set_sort_path(gs_renderer* r, int mode) {
         if (!r) throw Error(GS_ERR_INVALID, "renderer is null");
         if (mode < 0 || mode > 2) throw Error(GS_ERR_INVALID, "sort path must be 0 (auto), 1 (global) or 2 (bin-local)");
         r->drain();
-        r->sort_mode = mode;
-        r->level = 0;
-        r->refined = false;
-        r->frames_since_fallback = 0;
+        r->policy.set_sort_mode(mode);
     });
 }
 
