@@ -966,7 +966,7 @@ __device__ __forceinline__ void bin_fast_body(const BuildArgs& a) {
         wbase = (uint32_t)w * (uint32_t)rounds * WAVE;
     }
     // attempt 0: the records as level 1 left them (any order inside a block's run).  attempt 1 (only after a run of more
-    // than 64 equal depths, i.e. a degenerate scene): the records rewritten in id order, so that the stable passes alone
+    // than 65 equal depths, i.e. a degenerate scene): the records rewritten in id order, so that the stable passes alone
     // leave equal depths in id order
     for (int attempt = 0; c != 0 && attempt < 2; ++attempt) {
         // ---- the bin's records, streamed: eight loads per thread in flight together (sixteen would not leave the registers
@@ -1036,7 +1036,7 @@ __device__ __forceinline__ void bin_fast_body(const BuildArgs& a) {
         }
         __syncthreads();
         if (attempt == 0) BUILD_T(9);
-        if (multi && redo) {  // a run of > 64 equal depths inside a slab: not handled here -- the global path takes the frame
+        if (multi && redo) {  // a run of > 65 equal depths inside a slab: not handled here -- the global path takes the frame
             if (tid == 0) atomicOr(&a.counters->overflow, 2u);
             __syncthreads();
             if (tid == 0) s_flag = 0;

@@ -1,7 +1,8 @@
 // gs_depth_policy.h -- how a frame's per-tile lists get their depth order, and the bin grid that goes
 // with it: which level the next frame runs at, what a frame that overflowed its level asks for, when to step back down.
 // Integer arithmetic on two of a frame's counters (`overflow`, `max_bin`).  Plain C++ without a device in sight:
-// tests/test_depth_policy.py drives it on the CPU.
+// tests/test_depth_policy.py drives it on the CPU.  tests/limit_scenes.py restates frames_overflowed and the bin geometry in
+// Python (predict, base_shift, can_refine) to predict a fresh renderer's stats: a change of the rules here changes them there.
 #pragma once
 
 #include <algorithm>
@@ -32,7 +33,8 @@ struct DepthPolicy {
     int level = 0;
     uint32_t frames_since_fallback = 0;
     // Depth slabs (level 4) can fail for reasons that have nothing to do with the bin's size -- one depth bucket beyond a slab, a
-    // run of more than 64 exactly equal depths inside one, more slabs than descriptors: the frame then goes to the global path,
+    // run of more than 65 exactly equal depths inside one (the run's first element counts at most 64 more), more slabs than
+    // descriptors: the frame then goes to the global path,
     // and since `max_bin` still fits level 4 the step-down below would send it straight back into the same failure every 32
     // frames, for ever.  Each such failure doubles the frames the renderer stays on the global path before it tries the slabs
     // again (32 .. 8192); 64 clean frames at level 4 reset it.

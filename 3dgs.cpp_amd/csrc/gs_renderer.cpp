@@ -638,7 +638,7 @@ struct gs_renderer {
         prev_retired = false;
         switch (policy.frames_overflowed(ran.data(), static_cast<int>(ran.size()))) {
             case DepthPolicy::kDepthsTooCrowded:
-                throw Error(GS_ERR_OVERFLOW, "a bin's depths are too crowded for the bin-local order (one depth bucket beyond a slab, or more than 64 equal depths in one): needs the global depth-order path");
+                throw Error(GS_ERR_OVERFLOW, "a bin's depths are too crowded for the bin-local order (one depth bucket beyond a slab, or more than 65 equal depths in one): needs the global depth-order path");
             case DepthPolicy::kBinTooFull:
                 throw Error(GS_ERR_OVERFLOW, "a bin holds more candidates than the bin-local sort can order");
             case DepthPolicy::kRerun:

@@ -1,0 +1,513 @@
+"""Scenes that stand exactly on a capacity of the binning and blend kernels: the candidates a depth-order level holds, the run
+of equal depths the tie step orders in place, the keys a depth bucket holds before the stable passes take over, the slab cut,
+the items of a level-1 block, the bin box the whole wave emits, the blend's chunks of 64.
+
+Nothing here is random.  Every candidate is ONE tiny isotropic Gaussian (radius 3 px) whose centre lies within 2.5 px of a
+tile's centre, so its tile box is that tile and nothing else; the camera is the identity, so view depth is -z bit for bit
+and a scene's depths are written as binary32 bit patterns.  A builder returns a LimitScene: the records, the frame, the
+environment the renderer needs, and `expect` -- the quantities it pins, exact by construction.  The second half of the module
+re-measures those quantities from the oracle's stages (tests/test_limit_scenes.py asserts they are equal, with no GPU) and
+restates the level policy of gs_depth_policy.h for a fresh renderer, which is where the GPU test's predicted stats come from.
+
+A plain module: numpy and tests/ only."""
+from dataclasses import dataclass, field
+
+import numpy as np
+
+from float64_cases import RECORD_FLOATS, _ndc, _place
+
+FOV = 45.0
+LEVEL_LIMITS = (4096, 8192, 12288, 16384, 65535)   # gs_levels.h: kBinSortLimit
+SLAB_LEVEL, GLOBAL_LEVEL = 4, 5
+SLAB_MAX = 12288                                    # candidates of one depth slab (gs_bin_l2.hip: MAXC of k_bin_slabs)
+MAX_SLABS = 16                                      # kMaxSlabs
+MSD_BUCKETS, MSD_BUCKET_MAX = 4096, 64              # kMsdBuckets, kMsdBucketMax
+TIE_RUN_MAX = 65                                    # the longest run of equal depths the tie step orders in place
+THREADS = 1024                                      # of a level-2 workgroup: element e of the ordered list is round e / 1024
+L1_ITEMS, L1_XCD_RUN, L1_BIG_BOX = 1024, 32, 12     # gs_bin.h
+BLEND_CHUNK = 64
+DEPTH_2 = 0x40000000                                # the bit pattern of 2.0f: [2, 4) holds 2^23 patterns
+PRIME = 1000003
+
+
+@dataclass
+class LimitScene:
+    name: str
+    records: np.ndarray
+    width: int
+    height: int
+    env: dict                      # environment of the renderer (GS_BIN_SHIFT, GS_L1_DENSE_MIN, ...)
+    pins: str                      # the limit this scene stands on
+    expect: dict                   # the pinned quantities, exact by construction (see measure())
+    slabs_fail: bool = False       # the depth slabs cannot order the fullest bin (a long run, too many slabs)
+    guard: dict = None             # guard scenes: the sites, the tuned layers, the quadrant, what the counters must say
+    min_shift: int = field(init=False)
+
+    def __post_init__(self):
+        self.min_shift = int(self.env.get("GS_BIN_SHIFT", 3))
+
+
+# ------------------------------------------------------------------------------------------------ placing
+def _splats(depth_bits, tile_x, tile_y, w, h, logit=None, pixel=None):
+    """One tiny Gaussian per entry, in id order: view depth = the binary32 pattern, tile box = exactly (tile_x, tile_y).
+    pixel = (px, py): centred on those pixels instead (tile_x, tile_y unused)."""
+    depth_bits = np.asarray(depth_bits, np.uint32)
+    n = len(depth_bits)
+    i = np.arange(n, dtype=np.int64)
+    tz = depth_bits.view(np.float32)
+    ux = 16.0 * np.asarray(tile_x, np.float64) + 7.5 + ((i * 7) % 5 - 2)
+    uy = 16.0 * np.asarray(tile_y, np.float64) + 7.5 + ((i * 3) % 5 - 2)
+    if pixel is not None:
+        ux, uy = np.asarray(pixel[0], np.float64), np.asarray(pixel[1], np.float64)
+    rec = np.zeros((n, RECORD_FLOATS), np.float32)
+    _place(rec, _ndc(ux, w), _ndc(uy, h), tz.astype(np.float64), FOV, w, h)
+    rec[:, 2] = -tz
+    rec[:, 6] = np.sin(0.37 * i) * 1.2
+    rec[:, 7] = np.cos(0.91 * i) * 1.2
+    rec[:, 8] = np.sin(1.73 * i + 1.0) * 1.2
+    rec[:, 54] = (-1.0 + 2.0 * ((i * 0.6180339887) % 1.0)) if logit is None else logit
+    rec[:, 55:58] = np.log(tz.astype(np.float64) * 1e-5)[:, None]   # 0.01 px: the 0.3 px dilation is all of the footprint
+    rec[:, 58] = 1.0
+    return rec
+
+
+def _bin_tiles(count, shift, bin_x, bin_y, first=0):
+    """Tiles of bin (bin_x, bin_y) for `count` candidates, dealt round robin over the bin's S x S tiles."""
+    s = 1 << shift
+    k = (np.arange(count, dtype=np.int64) + first) % (s * s)
+    return bin_x * s + k % s, bin_y * s + k // s
+
+
+def _spread_bits(count, lo=DEPTH_2, span=1 << 23):
+    """`count` distinct depth patterns in [lo, lo + span), scrambled against the id order."""
+    stride = span // count
+    assert stride >= 1
+    return (lo + ((np.arange(count, dtype=np.int64) * PRIME) % count) * stride).astype(np.uint32)
+
+
+def _background(shift, bins, skip, per_bin, w, h):
+    """A few hundred splats in every other bin of the frame, so that the fullest bin is not the only one."""
+    recs = []
+    for by in range(bins[1]):
+        for bx in range(bins[0]):
+            if (bx, by) == skip:
+                continue
+            tx, ty = _bin_tiles(per_bin, shift, bx, by)
+            recs.append(_splats(_spread_bits(per_bin, DEPTH_2 + 12345 * (1 + bx + 2 * by)), tx, ty, w, h))
+    return np.concatenate(recs) if recs else np.zeros((0, RECORD_FLOATS), np.float32)
+
+
+def _one_bin_scene(name, bits, shift, pins, expect, env=None, slabs_fail=False, frame_bins=2, first_tile=0):
+    """`bits` (id order) all in bin (1, 1) of a frame of frame_bins x frame_bins bins of 2^shift tiles; 200 in every other bin."""
+    w = h = 16 * (1 << shift) * frame_bins
+    bg = _background(shift, (frame_bins, frame_bins), (1, 1), 200, w, h)
+    tx, ty = _bin_tiles(len(bits), shift, 1, 1, first_tile)
+    rec = np.concatenate([bg, _splats(bits, tx, ty, w, h)])
+    e = dict(n=len(rec), visible=len(rec), fullest_bin={shift: len(bits)}, bin_entries={shift: len(rec)})
+    e.update(expect)
+    full_env = {"GS_BIN_SHIFT": str(shift)}
+    full_env.update(env or {})
+    return LimitScene(name, rec, w, h, full_env, pins, e, slabs_fail)
+
+
+# ------------------------------------------------------------------------------------------------ level-2 sizes
+def level2_size(count, shift=2):
+    """The fullest bin holds exactly `count` candidates of distinct depths.  shift 2: bins of 4 x 4 tiles, which the policy
+    cannot refine; shift 3 (the default): a frame whose bins can be halved, with the candidates dealt evenly over the bin's 64
+    tiles, so that each of the four smaller bins holds a quarter of them."""
+    sc = _one_bin_scene(f"level2_size/{count}@{shift}", _spread_bits(count), shift,
+                        f"candidates in the fullest bin = {count}", {})
+    if shift == 3:
+        tx, ty = _bin_tiles(count, 3, 1, 1)
+        quarter = np.bincount(((ty >> 2) & 1) * 2 + ((tx >> 2) & 1), minlength=4)
+        sc.expect["fullest_bin"][2] = int(quarter.max())
+        sc.expect["bin_entries"][2] = sc.expect["n"]
+        del sc.env["GS_BIN_SHIFT"]
+        sc.min_shift = 3
+    return sc
+
+
+# ------------------------------------------------------------------------------------------------ equal-depth runs
+RUN_PLACES = ("start", "end", "straddle", "scattered")
+
+
+def equal_run(length, place, slab):
+    """A bin of M distinct depths, one of which is shared by `length` Gaussians.  place: the run is the nearest of the bin
+    ("start": ordered position 0), the farthest ("end"), begins 30 elements short of the ordered list's element 1024
+    ("straddle": it crosses from one round of the workgroup to the next), or sits mid-bin with its ids scattered over the
+    whole id range.  slab: 20 000 candidates (depth slabs, level 4) instead of 3 000 (k_bin_fast<4>)."""
+    m = 20000 if slab else 3000
+    rank = {"start": 0, "end": m - 1, "straddle": THREADS - 30, "scattered": m // 2 + 7}[place]
+    ranks = (np.arange(m, dtype=np.int64) * PRIME) % m          # a permutation: rank of id j
+    at = int(np.nonzero(ranks == rank)[0][0])
+    extra = length - 1
+    if place == "scattered":
+        where = np.sort(((np.arange(extra, dtype=np.int64) * 7919 + 13) * (m // max(extra, 1))) % m)
+    else:
+        where = np.full(extra, at + 1)
+    ranks = np.insert(ranks, where, rank)
+    bits = (DEPTH_2 + ranks * ((1 << 23) // m)).astype(np.uint32)
+    fails = slab and length > TIE_RUN_MAX
+    return _one_bin_scene(f"equal_run/{length}/{place}/{'slab' if slab else 'fast'}", bits, 2,
+                          f"run of {length} equal depths at ordered position {rank}",
+                          dict(longest_run=length, run_start=rank), slabs_fail=fails)
+
+
+# ------------------------------------------------------------------------------------------------ crowded bucket
+def crowded_bucket(k):
+    """Clusters of k consecutive binary32 patterns in a bin whose depth span two sentinels fix at 2^24 patterns (2.0 and 8.0):
+    the bin's 4096 depth buckets are 8192 patterns wide (25 significant bits, shift 13).  Four clusters lie inside one bucket
+    each -- at its start, its end, and twice mid-bucket -- and one is cut in half by a bucket border; 1500 single candidates in
+    buckets of their own.  The fullest bucket holds exactly k."""
+    width = 8192
+    clusters = [(300, 0), (700, 100), (1100, 4000), (1500, width - k), (1800, width - k // 2)]
+    bits = [DEPTH_2, DEPTH_2 + (1 << 24)]
+    for bucket, off in clusters:
+        bits += [DEPTH_2 + bucket * width + off + j for j in range(k)]
+    bits += [DEPTH_2 + (2 + b) * width + 4321 for b in range(1500) if all(abs(2 + b - c) > 1 for c, _ in clusters)]
+    bits = np.asarray(bits, np.int64)
+    bits = bits[(np.arange(len(bits), dtype=np.int64) * PRIME) % len(bits)].astype(np.uint32)
+    return _one_bin_scene(f"crowded_bucket/{k}", bits, 2, f"{k} keys in one depth bucket",
+                          dict(fullest_bucket=k, bucket_shift=13, longest_run=1))
+
+
+# ------------------------------------------------------------------------------------------------ slab planning
+def _bucket_fill(counts, bucket_width):
+    """Depth patterns: counts[b] distinct ones in bucket b (from its first pattern on); the first and the last pattern of the
+    whole range are among them (they fix the bin's depth span: counts[0] and counts[-1] must not be 0)."""
+    assert counts[0] > 0 and counts[-1] > 0 and max(counts) <= bucket_width
+    bits = [DEPTH_2 + b * bucket_width + np.arange(c, dtype=np.int64) for b, c in enumerate(counts)]
+    bits = np.concatenate(bits)
+    bits[-1] = DEPTH_2 + len(counts) * bucket_width - 1
+    return bits[(np.arange(len(bits), dtype=np.int64) * PRIME) % len(bits)].astype(np.uint32)
+
+
+def slab_plan(kind):
+    """A level-4 bin whose bucket counts decide the slab cut.  The planner (k_bin_slabs) cuts the bin's depth span into 4096
+    buckets and closes a slab in front of the first bucket that would take it beyond 12288.
+      exact:  buckets of 6; the first 2048 hold 12288 -- the first slab is full to the last place;
+      over:   the same, but bucket 2047 holds 5 and bucket 2048 holds 2: with it the slab would hold 12289, so it closes at 12287;
+      most:   buckets of 1 and of 12288 in turn, and a last one of 1: every slab holds one bucket.  The planner cuts only where a slab
+              and the first bucket behind it hold more than 12288 between them, so slabs 1+2, 3+4, ... each hold more than 12288
+              and n slabs need more than floor(n / 2) x 12288 candidates: 11 fit below 65535 (5 x 12288 + 6), 12 would need more
+              than 73728.  kMaxSlabs = 16 can therefore not be reached through a frame, and neither can the planner's
+              `remaining > MAXC` exit behind the sixteenth slab.  This is the nearest reachable case: 11 slabs, five of them full."""
+    if kind in ("exact", "over"):
+        counts = [6] * 3334                       # 24-bit span: 4096 buckets of 4096 patterns (the last 762 stay empty ...
+        counts += [0] * (4096 - len(counts) - 1) + [1]   # ... but for the sentinel that fixes the span)
+        if kind == "over":
+            counts[2047], counts[2048] = 5, 2
+        width = 4096
+        first = 12288 if kind == "exact" else 12287
+        sizes = [first, sum(counts) - first]
+    else:
+        counts = [1, 12288] * 5
+        counts += [0] * (4096 - len(counts) - 1) + [1]
+        width = 16384                             # 26-bit span: depths 2.0 .. 512.0
+        sizes = [1, 12288] * 5 + [1]
+    bits = _bucket_fill(counts, width)
+    return _one_bin_scene(f"slab_plan/{kind}", bits, 2, f"slabs of {sizes[:3]} ... ({len(sizes)} in all)",
+                          dict(slab_sizes=sizes, bucket_shift=12 if width == 4096 else 14, longest_run=1))
+
+
+# ------------------------------------------------------------------------------------------------ level 1
+def level1_count(n, culled=0, w=256, h=256):
+    """n visible Gaussians (n = the items of the global path's level 1, and of the planes' when nothing is culled), with `culled`
+    more behind the camera, dealt between them in id order; dealt round robin over every tile of the frame."""
+    tx, ty = w // 16, h // 16
+    i = np.arange(n, dtype=np.int64)
+    t = (i * 37) % (tx * ty)
+    rec = _splats(_spread_bits(n), t % tx, t // tx, w, h)
+    fullest = int(np.bincount(((t // tx) >> 3) * 64 + ((t % tx) >> 3)).max())
+    if culled:
+        total = n + culled
+        out = np.zeros((total, RECORD_FLOATS), np.float32)
+        behind = np.zeros(total, bool)
+        behind[(np.arange(culled, dtype=np.int64) * total) // culled] = True
+        out[~behind] = rec
+        dead = _splats(_spread_bits(culled), np.zeros(culled), np.zeros(culled), w, h)
+        dead[:, 2] = -dead[:, 2]                  # behind the camera
+        out[behind] = dead
+        rec = out
+    blocks = (len(rec) + L1_ITEMS - 1) // L1_ITEMS
+    return LimitScene(f"level1_count/{n}+{culled}", rec, w, h, {}, f"N = {len(rec)}, V = {n}",
+                      dict(n=len(rec), visible=n, l1_blocks=blocks, bin_entries={3: n}, fullest_bin={3: fullest}))
+
+
+def level1_blocks(blocks):
+    """N = 1024 x blocks - 1 Gaussians, all visible: exactly `blocks` level-1 blocks over the planes, the last one item short.
+    A frame of 9 x 8 bins, so that 257 blocks' worth still leaves every bin below 4096 candidates (level 0, no re-run)."""
+    sc = level1_count(L1_ITEMS * blocks - 1, w=1152, h=1024)
+    assert sc.expect["fullest_bin"][3] <= LEVEL_LIMITS[0]
+    sc.name = f"level1_blocks/{blocks}"
+    sc.pins = f"{blocks} level-1 blocks"
+    return sc
+
+
+BIG_BOXES = ((1, 12), (2, 6), (3, 4), (1, 13), (2, 7))
+
+
+def big_box(rows, cols):
+    """Probe Gaussians whose bin box is exactly rows x cols bins (bins of 4 x 4 tiles), among small ones in the same wave.
+    A tile box is a square around the centre, so the frame is `rows` bins high and clips it: centre in the middle of the frame's
+    height, radius 8 (b - a) - 8 around the middle of tile columns [a, b), which is 7 px clear of changing either end."""
+    shift, s = 2, 4
+    w, h = 16 * s * 16, 16 * s * rows
+    n = 640
+    i = np.arange(n, dtype=np.int64)
+    t = (i * 29) % (64 * 4 * rows)
+    rec = _splats(_spread_bits(n), t % 64, t // 64, w, h)
+    probes = [5, 64 + 63, 200, 201, 3 * 64]       # lanes 5 and 63 of two waves, two neighbours, lane 0
+    a, b = s * 1, s * (1 + cols)
+    radius = 8.0 * (b - a) - 8.0
+    focal = w / (2.0 * np.tan(np.radians(FOV) / 2.0))
+    for j, p in enumerate(probes):
+        tz = 2.5 + 0.25 * j
+        one = rec[p:p + 1]
+        _place(one, _ndc(np.array([8.0 * (a + b)]), w), _ndc(np.array([h / 2.0 - 0.5]), h), np.array([tz]), FOV, w, h)
+        one[:, 2] = -np.float32(tz)
+        lam = (radius - 0.5) ** 2 / 9.0           # radius = ceil(3 sqrt(lambda)), lambda = sigma^2 + 0.3 + sqrt(0.1)
+        sigma = np.sqrt(lam - 0.3 - np.sqrt(0.1))
+        one[:, 55:58] = np.log(sigma * tz / focal)
+        one[:, 54] = -4.0                         # faint: they cover the whole frame
+    entries = n + len(probes) * (rows * cols - 1)
+    per_bin = np.bincount(np.delete(((t // 64) >> 2) * 16 + ((t % 64) >> 2), probes), minlength=16 * rows).reshape(rows, 16)
+    per_bin[:, 1:1 + cols] += len(probes)
+    fullest = int(per_bin.max())
+    return LimitScene(f"big_box/{rows}x{cols}", rec, w, h, {"GS_BIN_SHIFT": "2"}, f"bin box of {rows} x {cols} bins",
+                      dict(n=n, visible=n, probes={p: (cols, rows) for p in probes}, bin_entries={shift: entries},
+                           fullest_bin={shift: fullest}))
+
+
+# ------------------------------------------------------------------------------------------------ blend chunks
+BLEND_LENGTHS = (1, 63, 64, 65, 127, 128, 129, 191, 192, 193)
+
+
+def blend_chunk(k):
+    """Tile (2, 1) of a 96 x 64 frame holds exactly k entries and its right neighbour the next length of BLEND_LENGTHS; every
+    other tile is empty.  Opacity 0.02: alpha passes the 1/255 cut at a splat's centre and 193 of them leave T = 0.02, so no
+    pixel stops early and every entry of the list is walked."""
+    w, h = 96, 64
+    other = BLEND_LENGTHS[(BLEND_LENGTHS.index(k) + 1) % len(BLEND_LENGTHS)]
+    n = k + other
+    ids = (np.arange(n, dtype=np.int64) * 13) % n                 # the two tiles' ids interleave
+    in_other = ids >= k
+    rec = _splats(_spread_bits(n), np.where(in_other, 3, 2), np.ones(n), w, h, logit=np.log(0.02 / 0.98))
+    return LimitScene(f"blend_chunk/{k}", rec, w, h, {}, f"a tile list of {k} entries",
+                      dict(n=n, visible=n, tile_lists={(2, 1): k, (3, 1): other}, instances=n))
+
+
+# ------------------------------------------------------------------------------------------------ guard triggers
+GUARD_LIST, GUARD_RESOLVES, GUARD_PAIRS = 384, 8, 4096      # gs_blend.hip: kGuardList, kGuardMaxResolves, kGuardMaxPairs
+GUARD_FRAME = 48                                            # 3 x 3 tiles; everything happens in tile (1, 1), pixels 24 .. 31 of it
+GUARD_QUADRANT = (slice(24, 32), slice(24, 32))             # rows, columns of the image
+_LOGIT_LO, _LOGIT_HI = np.float32(0.125), np.float32(6.0)   # final-layer logits that surely do not / surely do break
+
+
+def _stacks(sites, layers, final_bits):
+    """`layers` splats on the centre of each site's pixel (power = 0 there: alpha is the opacity), the sites' layers taking turns
+    in depth; ids run against the depth order.  Layers 0 .. layers - 2 are weak -- together they leave T = 5e-4 -- and carry no
+    red; the last layer of a site is red and has the logit whose binary32 pattern is final_bits[site].  Sites are two pixels apart:
+    at that distance a 0.3 px^2 footprint stays below alpha 1/255 whatever its opacity, so a site's pixel sees its own stack only."""
+    n_sites = len(sites)
+    n = n_sites * layers
+    e = n - 1 - np.arange(n, dtype=np.int64)                  # depth rank of id i
+    layer, site = e // n_sites, e % n_sites
+    px = np.asarray([p[0] for p in sites], np.float64)[site]
+    py = np.asarray([p[1] for p in sites], np.float64)[site]
+    rec = _splats((DEPTH_2 + e * 1000).astype(np.uint32), None, None, GUARD_FRAME, GUARD_FRAME, pixel=(px, py))
+    weak = 1.0 - (5e-4) ** (1.0 / (layers - 1))
+    last = layer == layers - 1
+    rec[:, 54] = np.log(weak / (1.0 - weak))
+    rec[last, 54] = np.asarray(final_bits, np.uint32).view(np.float32)[site[last]]
+    rec[:, 6] = np.where(last, 3.0, -2.0)
+    return rec, np.nonzero(last)[0][np.argsort(site[last])]     # (records, id of each site's last layer)
+
+
+def breaks_at(oracle_image, sites):
+    """Per site: did render.comp:83 take the break at the last layer (its red never reached the pixel)?"""
+    return np.asarray([oracle_image[y, x, 0] == 0.0 for x, y in sites])
+
+
+def _tuned_stacks(sites, layers, image_of):
+    """Bisect every site's last logit over the binary32 patterns, against the oracle's own frame: the result is the SMALLEST
+    opacity with which the reference breaks there, so its T (1 - alpha) lies within one rounding step below 1e-4."""
+    lo = np.full(len(sites), _LOGIT_LO.view(np.uint32), np.int64)
+    hi = np.full(len(sites), _LOGIT_HI.view(np.uint32), np.int64)
+    assert not breaks_at(image_of(_stacks(sites, layers, lo)[0]), sites).any()
+    assert breaks_at(image_of(_stacks(sites, layers, hi)[0]), sites).all()
+    while (hi - lo > 1).any():
+        mid = (lo + hi) // 2
+        b = breaks_at(image_of(_stacks(sites, layers, mid)[0]), sites)
+        hi, lo = np.where(b, mid, hi), np.where(b, lo, mid)
+    return hi
+
+
+def _guard_scene(name, pins, sites, layers, image_of, want):
+    bits = _tuned_stacks(sites, layers, image_of)
+    rec, last_ids = _stacks(sites, layers, bits)
+    n = len(rec)
+    return LimitScene(name, rec, GUARD_FRAME, GUARD_FRAME, {}, pins,
+                      dict(n=n, visible=n, instances=n, tile_lists={(1, 1): n}),
+                      guard=dict(sites=sites, layers=layers, final_bits=bits, last_ids=last_ids, want=want))
+
+
+def guard_list(kept, image_of):
+    """One pixel, `kept` layers: the break decision falls on the quadrant's kept entry number `kept` (position kept - 1 of the
+    wave's list, which holds 384).  image_of(records) -> the oracle's frame at GUARD_FRAME x GUARD_FRAME."""
+    return _guard_scene(f"guard_list/{kept}", f"a break decision at kept entry {kept}", [(27, 27)], kept, image_of,
+                        "resolved" if kept <= GUARD_LIST else "redo")
+
+
+def guard_resolves(count, image_of):
+    """`count` pixels of one quadrant (of the nine at 25 / 27 / 29 in x and y), 40 layers each, every one of them with its break
+    decision inside the window at its last layer: `count` replays in one quadrant, all within the first 384 kept entries."""
+    sites = [(25 + 2 * (k % 3), 25 + 2 * (k // 3)) for k in range(count)]
+    assert count * 40 <= GUARD_LIST
+    return _guard_scene(f"guard_resolves/{count}", f"{count} replays in one quadrant", sites, 40, image_of,
+                        "resolved" if count <= GUARD_RESOLVES else "redo")
+
+
+def guard_pairs(kept):
+    """`kept` splats on one pixel, opacity 0.8: that pixel stops at the sixth entry and its eight neighbours within 320, but the
+    rest of the quadrant never blends anything and walks on, so the quadrant evaluates exactly `kept` kept entries.  No break
+    decision is tuned here: beyond 4096 the quadrant is given up whatever its pixels do."""
+    rec = _splats(_spread_bits(kept), None, None, GUARD_FRAME, GUARD_FRAME, logit=np.log(0.8 / 0.2),
+                  pixel=(np.full(kept, 27.0), np.full(kept, 27.0)))
+    return LimitScene(f"guard_pairs/{kept}", rec, GUARD_FRAME, GUARD_FRAME, {}, f"{kept} kept entries in one quadrant",
+                      dict(n=kept, visible=kept, instances=kept, tile_lists={(1, 1): kept}),
+                      guard=dict(sites=[(27, 27)], want="clean" if kept <= GUARD_PAIRS else "redo"))
+
+
+# ================================================================================================ measuring
+def tiles_across(pixels):
+    return (pixels + 15) // 16
+
+
+def grid_fits(tx, ty, s):
+    return ((tx - 1) >> s) + 1 <= 32 and ((ty - 1) >> s) + 1 <= 32
+
+
+def base_shift(tx, ty, min_shift):
+    s = max(2, min_shift)
+    while not grid_fits(tx, ty, s):
+        s += 1
+    return s
+
+
+def can_refine(w, h, min_shift):
+    tx, ty = tiles_across(w), tiles_across(h)
+    s = base_shift(tx, ty, min_shift)
+    return 2 < s <= 5 and grid_fits(tx, ty, s - 1)
+
+
+def bin_boxes(ref, shift):
+    """Per visible Gaussian: (ids, x0, y0, x1, y1) of its box in bins, upper bounds exclusive (gs_bin.h: l1_item)."""
+    ids = np.nonzero(ref["tiles"])[0]
+    box = ref["attr"]["aabb"][ids].astype(np.int64)
+    return ids, box[:, 0] >> shift, box[:, 1] >> shift, ((box[:, 2] - 1) >> shift) + 1, ((box[:, 3] - 1) >> shift) + 1
+
+
+def bin_members(ref, shift):
+    """{(bx, by): ids of the bin's candidates, ascending}."""
+    ids, x0, y0, x1, y1 = bin_boxes(ref, shift)
+    out = {}
+    for g, a, b, c, d in zip(ids.tolist(), x0.tolist(), y0.tolist(), x1.tolist(), y1.tolist()):
+        for y in range(b, d):
+            for x in range(a, c):
+                out.setdefault((x, y), []).append(g)
+    return {k: np.asarray(v, np.int64) for k, v in out.items()}
+
+
+def measure(scene, ref):
+    """The quantities of scene.expect, recomputed from the oracle's stages alone."""
+    m = {"n": len(ref["tiles"]), "visible": int((ref["tiles"] != 0).sum())}
+    e = scene.expect
+    if "instances" in e:
+        m["instances"] = len(ref["keys"])
+    if "l1_blocks" in e:
+        m["l1_blocks"] = (m["n"] + L1_ITEMS - 1) // L1_ITEMS
+    if "bin_entries" in e:
+        m["bin_entries"] = {}
+        for s in e["bin_entries"]:
+            _, x0, y0, x1, y1 = bin_boxes(ref, s)
+            m["bin_entries"][s] = int(((x1 - x0) * (y1 - y0)).sum())
+    if "probes" in e:
+        ids, x0, y0, x1, y1 = bin_boxes(ref, scene.min_shift)
+        at = {int(g): k for k, g in enumerate(ids)}
+        m["probes"] = {p: (int(x1[at[p]] - x0[at[p]]), int(y1[at[p]] - y0[at[p]])) for p in e["probes"]}
+        m["largest_other_box"] = int(np.delete((x1 - x0) * (y1 - y0), [at[p] for p in e["probes"]]).max())
+    if "tile_lists" in e:
+        b = ref["boundaries"].astype(np.int64)
+        tx = tiles_across(scene.width)
+        lens = b[1::2] - b[0::2]
+        m["tile_lists"] = {(int(t % tx), int(t // tx)): int(lens[t]) for t in np.nonzero(lens)[0]}
+    if "fullest_bin" in e:
+        m["fullest_bin"] = {}
+        for s in e["fullest_bin"]:
+            members = bin_members(ref, s)
+            key = max(members, key=lambda k: len(members[k]))
+            m["fullest_bin"][s] = len(members[key])
+            if s != scene.min_shift:
+                continue
+            ids = members[key]
+            bits = ref["attr"]["depth"][ids].view(np.uint32).astype(np.int64)
+            order = np.lexsort((ids, bits))
+            sb = bits[order]
+            if "longest_run" in e:
+                starts = np.nonzero(np.r_[True, sb[1:] != sb[:-1]])[0]
+                lens = np.diff(np.r_[starts, len(sb)])
+                m["longest_run"] = int(lens.max())
+                if "run_start" in e:
+                    m["run_start"] = int(starts[lens.argmax()])
+            if "bucket_shift" in e:
+                span = int(sb[-1] - sb[0])
+                nbits = span.bit_length()
+                sh = nbits - 12 if nbits > 12 else 0
+                m["bucket_shift"] = sh
+                bucket = (sb - sb[0]) >> sh
+                counts = np.bincount(bucket, minlength=MSD_BUCKETS)
+                if "fullest_bucket" in e:
+                    m["fullest_bucket"] = int(counts.max())
+                if "slab_sizes" in e:
+                    m["slab_sizes"] = plan_slabs(counts)
+    return m
+
+
+def plan_slabs(counts):
+    """The slab cut of k_bin_slabs over a bin's bucket histogram: a slab takes buckets while it stays <= 12288.  Returns the
+    slabs' sizes, or None where the planner gives up (a bucket beyond a slab, more than 16 slabs)."""
+    if counts.max() > SLAB_MAX:
+        return None
+    sizes, cur = [], 0
+    for c in counts.tolist():
+        if cur + c > SLAB_MAX:
+            sizes.append(cur)
+            cur = 0
+        cur += c
+    sizes.append(cur)
+    return sizes if len(sizes) <= MAX_SLABS else None
+
+
+def predict(scene, forced=False):
+    """What a FRESH renderer's stats say after one frame of the scene (gs_depth_policy.h, restated): the level it ends at, the
+    re-runs on the way, the bin edge, the fullest bin.  forced: gs_set_sort_path(2); "error" where that mode gives up."""
+    tx, ty = tiles_across(scene.width), tiles_across(scene.height)
+    shift = base_shift(tx, ty, scene.min_shift)
+    level, retries, refined = 0, 0, False
+    while True:
+        fullest = scene.expect["fullest_bin"][shift]
+        fits = level == GLOBAL_LEVEL or (fullest <= LEVEL_LIMITS[level] and not (level == SLAB_LEVEL and scene.slabs_fail))
+        if fits:
+            return dict(sort_level=level, sort_path=1 if level == GLOBAL_LEVEL else 2, retries=retries, bin_tiles=1 << shift,
+                        max_bin_entries=fullest, num_bin_entries=scene.expect["bin_entries"][shift])
+        wanted = level + 1
+        while wanted < GLOBAL_LEVEL and fullest > LEVEL_LIMITS[wanted]:
+            wanted += 1
+        if wanted >= SLAB_LEVEL and not refined and can_refine(scene.width, scene.height, scene.min_shift):
+            refined, shift, level = True, shift - 1, max(level, SLAB_LEVEL - 1)
+        else:
+            if forced and wanted >= GLOBAL_LEVEL:
+                return "error"
+            level = max(level, wanted)
+        retries += 1

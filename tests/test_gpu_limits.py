@@ -1,0 +1,275 @@
+"""The binning and blend kernels at the exact edge of their capacities (scenes: tests/limit_scenes.py; that they stand on the
+edge: tests/test_limit_scenes.py, on the CPU).  Every case: the stage taps bit for bit against the oracle, the image bit for
+bit in exp mode 2, the default blend (mode 3) within the guarded tolerance, and the frame's stats -- level, path, re-runs, bin
+edge, fullest bin, candidates -- equal to what the restated policy predicts for a fresh renderer.  A case that is no longer
+on its edge FAILS: the pinned quantity is re-measured from the oracle's stages here too.
+
+Not covered, and why:
+  * kMaxSlabs = 16 and the planner's `remaining > MAXC` exit: a bin of <= 65535 candidates cannot be cut into more than 11
+    slabs of <= 12288 (tests/test_limit_scenes.py::test_no_bin_of_a_frame_needs_more_than_eleven_slabs).  The nearest
+    reachable case, 11 slabs of which five are full, is test_slab_planning[most].
+  * kMsdBucketMax has no counter: 64 and 65 keys in a bucket must give the same lists, so those cases pin that BOTH orders are
+    right at the hand-over, not which one ran.
+"""
+import numpy as np
+import pytest
+
+import limit_scenes as ls
+from helpers import assert_guarded_close, assert_images_identical, compare_stages, oracle_frame
+
+pytestmark = pytest.mark.gpu
+
+STAT_KEYS = ("sort_path", "sort_level", "retries", "bin_tiles", "max_bin_entries", "num_bin_entries")
+
+
+def _frame(pkg, oracle, monkeypatch, scene, extra_env=None):
+    """The oracle's frame, the check that the scene is on its edge, and a fresh renderer under the scene's environment."""
+    monkeypatch.delenv("GS_SORT_PATH", raising=False)
+    for k, v in {**scene.env, **(extra_env or {})}.items():
+        monkeypatch.setenv(k, v)
+    verts, u_ref, ref = oracle_frame(oracle, scene.records, scene.width, scene.height)
+    got = ls.measure(scene, ref)
+    for key, want in scene.expect.items():
+        assert got[key] == want, f"{scene.name} missed its edge ({scene.pins}): {key} is {got[key]}, not {want}"
+    gs = pkg.Scene.from_records(scene.records, device=0)
+    u = pkg.camera_uniforms(pkg.make_camera(), scene.width, scene.height)
+    assert u.tobytes() == u_ref.tobytes()
+    return gs, pkg.Renderer(gs), u, ref
+
+
+def _assert_frame(pkg, rend, u, ref, scene, want, label):
+    """One frame: stats as predicted, every stage and the mode-2 image exact, the default blend within the guarded tolerance."""
+    img, _ = rend.render_host(u)
+    st = rend.stats()
+    have = {k: getattr(st, k) for k in STAT_KEYS}
+    print(f"{label}: {have}")
+    if want is not None:
+        assert have == {k: want[k] for k in STAT_KEYS}, f"{label}: stats {have}, predicted {want}"
+    assert st.num_visible == scene.expect["visible"] and st.num_gaussians == scene.expect["n"]
+    compare_stages(pkg, rend, u, ref)
+    assert_images_identical(img, ref["image"], label=label)
+    worst, redo, resolved = assert_guarded_close(rend, u, ref["image"], label=f"{label}, default blend")
+    print(f"{label}: default blend max |d| {worst:.3g}, quadrants re-rendered {redo}, breaks resolved {resolved}")
+    return st
+
+
+def _run(pkg, oracle, monkeypatch, scene, forced=False, extra_env=None):
+    gs, rend, u, ref = _frame(pkg, oracle, monkeypatch, scene, extra_env)
+    try:
+        want = ls.predict(scene, forced) if "fullest_bin" in scene.expect else None
+        rend.set_sort_path(2 if forced else 0)
+        label = f"{scene.name}{' forced' if forced else ''}{' ' + str(extra_env) if extra_env else ''}"
+        if want == "error":
+            with pytest.raises(pkg.GsError) as e:
+                rend.render_host(u)
+            assert e.value.code == -5
+            print(f"{label}: raised {e.value}")
+            return None
+        return _assert_frame(pkg, rend, u, ref, scene, want, label)
+    finally:
+        rend.close()
+        gs.close()
+
+
+# ------------------------------------------------------------------------------------------------ level-2 sizes
+@pytest.mark.parametrize("delta", [-1, 0, 1])
+@pytest.mark.parametrize("level", [0, 1, 2, 3])
+def test_level2_size_in_lds(pkg, oracle, gpu, monkeypatch, level, delta):
+    """kBinSortLimit[0..3] = 4096 / 8192 / 12288 / 16384: L - 1 and L candidates run k_bin_fast<4 / 8 / 12 / 16>, L + 1 is re-run
+    once at the next level (16385: depth slabs, since bins of 4 x 4 tiles cannot be refined)."""
+    count = ls.LEVEL_LIMITS[level] + delta
+    st = _run(pkg, oracle, monkeypatch, ls.level2_size(count))
+    assert st.sort_level == level + (delta > 0) and st.max_bin_entries == count and st.retries == (st.sort_level > 0)
+    _run(pkg, oracle, monkeypatch, ls.level2_size(count), forced=True)
+
+
+def test_level2_16385_refines_the_bins_first(pkg, oracle, gpu, monkeypatch):
+    """The other successor of 16384 + 1: where the bins can be halved they are, and the frame stays at the largest in-LDS order."""
+    st = _run(pkg, oracle, monkeypatch, ls.level2_size(16385, shift=3))
+    assert (st.bin_tiles, st.sort_level, st.retries, st.max_bin_entries) == (4, 3, 1, 4097)
+
+
+@pytest.mark.parametrize("queue", ["1", "0"])
+@pytest.mark.parametrize("count", [16385, 65534, 65535])
+def test_level2_size_in_slabs(pkg, oracle, gpu, monkeypatch, count, queue):
+    """Level 4 from its first candidate to its last, with the one-launch queue (GS_L2_QUEUE=1) and with k_bin_slabs + k_slab_work."""
+    for forced in (False, True):
+        st = _run(pkg, oracle, monkeypatch, ls.level2_size(count), forced=forced, extra_env={"GS_L2_QUEUE": queue})
+        assert (st.sort_path, st.sort_level, st.retries, st.max_bin_entries) == (2, 4, 1, count)
+
+
+@pytest.mark.parametrize("queue", ["1", "0"])
+def test_level2_65536_leaves_the_bin_local_path(pkg, oracle, gpu, monkeypatch, queue):
+    """One candidate beyond the slabs' 16-bit slot: the documented overflow error when the bin-local path is forced, the global
+    path with the same lists in automatic mode."""
+    sc = ls.level2_size(65536)
+    assert _run(pkg, oracle, monkeypatch, sc, forced=True, extra_env={"GS_L2_QUEUE": queue}) is None
+    st = _run(pkg, oracle, monkeypatch, sc, extra_env={"GS_L2_QUEUE": queue})
+    assert (st.sort_path, st.sort_level, st.retries, st.max_bin_entries) == (1, 5, 1, 65536)
+
+
+# ------------------------------------------------------------------------------------------------ equal-depth runs
+@pytest.mark.parametrize("place", ls.RUN_PLACES)
+@pytest.mark.parametrize("length", [64, 65, 66, 67])
+def test_equal_depth_run_in_a_fast_bin(pkg, oracle, gpu, monkeypatch, length, place):
+    """The tie step's run limit in k_bin_fast<4>: a run's first element counts at most 64 more, so 65 are ordered in place and 66
+    take the second attempt (records rewritten in id order).  Either way the bin stays bin-local and the lists are exact."""
+    for forced in (False, True):
+        st = _run(pkg, oracle, monkeypatch, ls.equal_run(length, place, slab=False), forced=forced)
+        assert (st.sort_path, st.sort_level, st.retries) == (2, 0, 0)
+
+
+@pytest.mark.parametrize("queue", ["1", "0"])
+@pytest.mark.parametrize("place", ls.RUN_PLACES)
+@pytest.mark.parametrize("length", [64, 65, 66, 67])
+def test_equal_depth_run_in_a_slab(pkg, oracle, gpu, monkeypatch, length, place, queue):
+    """The same limit inside a depth slab, which has no second attempt: 64 and 65 stay at level 4; 66 and 67 send the frame to
+    the global path (automatic) or raise (forced bin-local)."""
+    sc = ls.equal_run(length, place, slab=True)
+    env = {"GS_L2_QUEUE": queue}
+    st = _run(pkg, oracle, monkeypatch, sc, extra_env=env)
+    forced = _run(pkg, oracle, monkeypatch, sc, forced=True, extra_env=env)
+    if length <= 65:
+        assert (st.sort_path, st.sort_level, st.retries) == (2, 4, 1) and forced.sort_level == 4
+    else:
+        assert (st.sort_path, st.sort_level, st.retries) == (1, 5, 2) and forced is None
+
+
+# ------------------------------------------------------------------------------------------------ crowded bucket
+@pytest.mark.parametrize("k", [63, 64, 65, 66])
+def test_crowded_depth_bucket(pkg, oracle, gpu, monkeypatch, k):
+    """kMsdBucketMax = 64 keys in one of the 4096 depth buckets: 64 are ranked inside the bucket, 65 hand the bin to the stable
+    passes.  The kernel has no counter for which order ran: parity of the lists and the image at each k is the assertion."""
+    st = _run(pkg, oracle, monkeypatch, ls.crowded_bucket(k))
+    assert (st.sort_path, st.sort_level, st.retries) == (2, 0, 0)
+
+
+# ------------------------------------------------------------------------------------------------ slab planning
+@pytest.mark.parametrize("queue", ["1", "0"])
+@pytest.mark.parametrize("kind", ["exact", "over", "most"])
+def test_slab_planning(pkg, oracle, gpu, monkeypatch, kind, queue):
+    """A slab full to its last place (12288), a slab that closes at 12287 because the next bucket would make it 12289, and the
+    most slabs a bin of <= 65535 can be cut into (11; see the module docstring for kMaxSlabs)."""
+    for forced in (False, True):
+        st = _run(pkg, oracle, monkeypatch, ls.slab_plan(kind), forced=forced, extra_env={"GS_L2_QUEUE": queue})
+        assert (st.sort_path, st.sort_level, st.retries) == (2, 4, 1)
+
+
+# ------------------------------------------------------------------------------------------------ level 1
+def _level1(pkg, oracle, monkeypatch, scene, dense_min, sort_path):
+    gs, rend, u, ref = _frame(pkg, oracle, monkeypatch, scene, {"GS_L1_DENSE_MIN": dense_min})
+    try:
+        rend.set_sort_path(sort_path)
+        want = ls.predict(scene)
+        assert want["retries"] == 0 and want["sort_level"] == 0   # these scenes are about level 1: no bin beyond 4096
+        if sort_path == 1:
+            want.update(sort_path=1, sort_level=ls.GLOBAL_LEVEL)
+        _assert_frame(pkg, rend, u, ref, scene, want, f"{scene.name} dense_min {dense_min} path {sort_path}")
+    finally:
+        rend.close()
+        gs.close()
+
+
+@pytest.mark.parametrize("dense_min", ["0", "1000000000"])
+@pytest.mark.parametrize("n,culled", [(1023, 0), (1024, 0), (1025, 0), (1023, 300), (1024, 300), (1025, 300)])
+def test_level1_items_around_one_block(pkg, oracle, gpu, monkeypatch, n, culled, dense_min):
+    """kL1Items = 1024: N (the planes' items) and V (the dense lists' and the global path's items) one short of a block, a whole
+    block, one beyond."""
+    for sort_path in (0, 1):
+        _level1(pkg, oracle, monkeypatch, ls.level1_count(n, culled), dense_min, sort_path)
+
+
+@pytest.mark.parametrize("dense_min", ["0", "1000000000"])
+@pytest.mark.parametrize("blocks", [31, 32, 33, 255, 256, 257])
+def test_level1_block_counts_around_the_xcd_runs(pkg, oracle, gpu, monkeypatch, blocks, dense_min):
+    """kL1XcdRun = 32 blocks per XCD run and 8 runs per round (l1_grid, l1_block): one run short by a block, exact, one over; the
+    same for a whole round of 256."""
+    _level1(pkg, oracle, monkeypatch, ls.level1_blocks(blocks), dense_min, 0)
+
+
+@pytest.mark.parametrize("dense_min", ["0", "1000000000"])
+@pytest.mark.parametrize("rows,cols", ls.BIG_BOXES)
+def test_level1_bin_box_at_the_wave_emission_limit(pkg, oracle, gpu, monkeypatch, rows, cols, dense_min):
+    """kL1BigBox = 12: bin boxes of exactly 12 bins are emitted by their own lane, boxes of 13 and 14 by the whole wave -- in
+    k_l1_hist and in the scatter alike, or the counts and the lists disagree."""
+    for sort_path in (0, 1):
+        _level1(pkg, oracle, monkeypatch, ls.big_box(rows, cols), dense_min, sort_path)
+
+
+# ------------------------------------------------------------------------------------------------ blend chunks
+@pytest.mark.parametrize("lockstep", [0, 1])
+@pytest.mark.parametrize("k", ls.BLEND_LENGTHS)
+def test_blend_list_lengths_around_the_chunks(pkg, oracle, gpu, monkeypatch, k, lockstep):
+    """The blend walks a list in chunks of 64, ids fetched two chunks ahead and records one: lists that end one short of a
+    chunk, on it and one beyond, for one, two and three chunks, with every entry walked (no pixel stops early)."""
+    scene = ls.blend_chunk(k)
+    gs, rend, u, ref = _frame(pkg, oracle, monkeypatch, scene)
+    try:
+        rend.set_blend_lockstep(lockstep)
+        st = _assert_frame(pkg, rend, u, ref, scene, None, f"{scene.name} lockstep {lockstep}")
+        assert st.num_instances == scene.expect["instances"]
+        ranges = rend.stage("ranges", u).astype(np.int64)
+        tx = ls.tiles_across(scene.width)
+        assert ranges[2 * (1 * tx + 2) + 1] - ranges[2 * (1 * tx + 2)] == k
+    finally:
+        rend.close()
+        gs.close()
+
+
+# ------------------------------------------------------------------------------------------------ guard triggers
+def _guard_case(pkg, oracle, monkeypatch, scene):
+    """Mode 2 exact and mode 3 within the guarded tolerance like every case; then the default blend's counters, and the quadrant
+    under test bit for bit against the reference where it was re-rendered with the reference's arithmetic."""
+    gs, rend, u, ref = _frame(pkg, oracle, monkeypatch, scene)
+    try:
+        _assert_frame(pkg, rend, u, ref, scene, None, scene.name)
+        rend.set_exp_mode(3)
+        rend.set_blend_contraction(False)
+        img, _ = rend.render_host(u)
+        st = rend.stats()
+        rend.set_exp_mode(2)
+        redo, resolved = int(st.blend_redo), int(st.blend_resolved)
+        print(f"{scene.name}: quadrants re-rendered {redo}, breaks resolved {resolved}")
+        q = ls.GUARD_QUADRANT
+        same = np.array_equal(img[q][..., :3].view(np.uint32), np.ascontiguousarray(ref["image"][q][..., :3]).view(np.uint32))
+        return redo, resolved, same
+    finally:
+        rend.close()
+        gs.close()
+
+
+def _oracle_image(oracle):
+    return lambda rec: oracle_frame(oracle, rec, ls.GUARD_FRAME, ls.GUARD_FRAME)[2]["image"]
+
+
+@pytest.mark.parametrize("kept", [384, 385])
+def test_guard_list_of_kept_entries(pkg, oracle, gpu, monkeypatch, kept):
+    """kGuardList = 384: a break decision inside the window at the quadrant's 384th kept entry is replayed from the wave's list;
+    at the 385th the list does not hold it and the quadrant is re-rendered with the reference's arithmetic."""
+    redo, resolved, same = _guard_case(pkg, oracle, monkeypatch, ls.guard_list(kept, _oracle_image(oracle)))
+    if kept == 384:
+        assert (redo, resolved) == (0, 1)
+    else:
+        assert redo == 1 and same
+
+
+@pytest.mark.parametrize("count", [8, 9])
+def test_guard_replays_per_quadrant(pkg, oracle, gpu, monkeypatch, count):
+    """kGuardMaxResolves = 8: eight pixels of a quadrant with their break decision inside the window are eight replays; the ninth
+    gives the quadrant up."""
+    redo, resolved, same = _guard_case(pkg, oracle, monkeypatch, ls.guard_resolves(count, _oracle_image(oracle)))
+    if count == 8:
+        assert (redo, resolved) == (0, 8)
+    else:
+        assert redo == 1 and same
+
+
+@pytest.mark.parametrize("kept", [4095, 4096, 4097])
+def test_guard_pairs_per_quadrant(pkg, oracle, gpu, monkeypatch, kept):
+    """kGuardMaxPairs = 4096 kept entries per quadrant, the n of the coarse window: 4096 are blended by the guarded loop, 4097 are
+    not."""
+    redo, resolved, same = _guard_case(pkg, oracle, monkeypatch, ls.guard_pairs(kept))
+    if kept <= 4096:
+        assert redo == 0
+    else:
+        assert redo == 1 and same
