@@ -4,10 +4,6 @@
 
 namespace gs {
 
-#ifndef GS_DPP_TRANSPOSE
-#define GS_DPP_TRANSPOSE 1
-#endif
-
 // ---------------------------------------------------------------------------------------
 // Two-level binning: per-tile depth-ordered lists without sorting the D instances.
 //
@@ -58,7 +54,6 @@ __device__ __forceinline__ void cover_masks(int shift, int x0, int y0, int x1, i
 // that pipe was what bounded every kernel built on the transpose, hence the DPP forms for the four short strides.
 template <int J>
 __device__ __forceinline__ uint32_t lane_xor(uint32_t x) {
-#if GS_DPP_TRANSPOSE
     if (J == 1) return (uint32_t)__builtin_amdgcn_mov_dpp((int)x, 0xB1, 0xF, 0xF, true);   // quad_perm [1,0,3,2]
     if (J == 2) return (uint32_t)__builtin_amdgcn_mov_dpp((int)x, 0x4E, 0xF, 0xF, true);   // quad_perm [2,3,0,1]
     if (J == 4) {
@@ -69,7 +64,6 @@ __device__ __forceinline__ uint32_t lane_xor(uint32_t x) {
         const int t = __builtin_amdgcn_mov_dpp((int)x, 0x140, 0xF, 0xF, true);             // row_mirror: i -> 15 - i
         return (uint32_t)__builtin_amdgcn_mov_dpp(t, 0x141, 0xF, 0xF, true);                // row_half_mirror
     }
-#endif
     return (uint32_t)__builtin_amdgcn_ds_swizzle((int)x, (J << 10) | 0x1F);  // lane ^ J
 }
 template <int J>
@@ -222,15 +216,11 @@ __device__ __forceinline__ uint64_t cover_word(int shift, uint32_t box, int r) {
 // every L2 evicts its own partial copy of it: WRITE_SIZE was 4 x the bytes stored at 6 M Gaussians.  So runs of
 // kL1XcdRun consecutive blocks go to the SAME XCD (the lines are completed in one L2), and the XCDs still advance through
 // the scene side by side.  The grid is rounded up to whole rounds of 8 runs; the blocks past the end return at once.
-#ifndef GS_L1_XCD_RUN
-#define GS_L1_XCD_RUN 32
-#endif
-constexpr uint32_t kL1XcdRun = GS_L1_XCD_RUN;  // 0: workgroup b takes block b
+constexpr uint32_t kL1XcdRun = 32;
 __host__ __device__ constexpr uint32_t l1_grid(uint32_t nblk) {
-    return kL1XcdRun == 0 ? nblk : (nblk + 8u * kL1XcdRun - 1u) / (8u * kL1XcdRun) * (8u * kL1XcdRun);
+    return (nblk + 8u * kL1XcdRun - 1u) / (8u * kL1XcdRun) * (8u * kL1XcdRun);
 }
 __device__ __forceinline__ uint32_t l1_block() {
-    if (kL1XcdRun == 0) return blockIdx.x;
     const uint32_t xcd = blockIdx.x & 7u, j = blockIdx.x >> 3;
     return ((j / kL1XcdRun) * 8u + xcd) * kL1XcdRun + j % kL1XcdRun;
 }

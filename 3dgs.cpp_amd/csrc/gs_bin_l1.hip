@@ -8,10 +8,6 @@
 
 namespace gs {
 
-#ifndef GS_L1_WORDLOOP
-#define GS_L1_WORDLOOP 1
-#endif
-
 // Wave w of the block takes chunks 4w .. 4w + 3 (consecutive items): all loads of its four chunks are issued before
 // the first is used, and 8 such blocks are resident per CU -- the kernels are a handful of dependent memory round
 // trips each, so what matters is how many of them are in flight.
@@ -228,7 +224,6 @@ __global__ __launch_bounds__(BLOCK) void k_l1_scatter(L1Args a) {
 #pragma unroll 1
     for (int j = 0; j < kL1PerWave; ++j) {
         const int ch = w * kL1PerWave + j;
-#if GS_L1_WORDLOOP
         const uint32_t box = s_box[ch][lane];
 #pragma unroll 1
         for (int r = 0; r < R1; ++r) {
@@ -236,15 +231,6 @@ __global__ __launch_bounds__(BLOCK) void k_l1_scatter(L1Args a) {
             if (__builtin_amdgcn_ballot_w64(mr != 0) == 0) continue;
             walk_column(wave_transpose64(mr, lane), s_start[r * 64 + lane] + s_cnt[ch][r * 64 + lane], out, s_ids[ch]);
         }
-#else
-        uint64_t m[R1];
-        packed_cover_masks<R1>(a.g.grid_shift, s_box[ch][lane], m);
-#pragma unroll
-        for (int r = 0; r < R1; ++r) {
-            if (__builtin_amdgcn_ballot_w64(m[r] != 0) == 0) continue;
-            walk_column(wave_transpose64(m[r], lane), s_start[r * 64 + lane] + s_cnt[ch][r * 64 + lane], out, s_ids[ch]);
-        }
-#endif
     }
 }
 

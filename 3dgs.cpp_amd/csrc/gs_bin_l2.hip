@@ -1358,13 +1358,11 @@ template <> __global__ __launch_bounds__(1024, 4) void k_bin_fast<8>(BuildArgs a
 template <> __global__ __launch_bounds__(1024, 4) void k_bin_fast<12>(BuildArgs a) { bin_fast_body<12>(a); }
 template <> __global__ __launch_bounds__(1024, 4) void k_bin_fast<16>(BuildArgs a) { bin_fast_body<16>(a); }
 // bins of up to 65535 candidates, taken in depth slabs of <= 12288 (depth-order level 4): plan, then one workgroup per slab
-#ifndef GS_SLAB_ROUNDS
-#define GS_SLAB_ROUNDS 12  // candidates per thread of the slab kernels: slabs (and the bins k_bin_slabs takes itself) of <= 1024 x this
-#endif
-__global__ __launch_bounds__(1024, 4) void k_bin_slabs(BuildArgs a) { bin_fast_body<GS_SLAB_ROUNDS, 1>(a); }
-__global__ __launch_bounds__(1024, 4) void k_slab_work(BuildArgs a) { bin_fast_body<GS_SLAB_ROUNDS, 2>(a); }
+constexpr int kSlabRounds = 12;  // candidates per thread of the slab kernels: slabs (and the bins k_bin_slabs takes itself) of <= 1024 x this
+__global__ __launch_bounds__(1024, 4) void k_bin_slabs(BuildArgs a) { bin_fast_body<kSlabRounds, 1>(a); }
+__global__ __launch_bounds__(1024, 4) void k_slab_work(BuildArgs a) { bin_fast_body<kSlabRounds, 2>(a); }
 // the two of them as one launch of persistent workgroups over a queue of bins, then slabs
-__global__ __launch_bounds__(1024, 4) void k_bin_queue(BuildArgs a) { bin_fast_body<GS_SLAB_ROUNDS, 3>(a); }
+__global__ __launch_bounds__(1024, 4) void k_bin_queue(BuildArgs a) { bin_fast_body<kSlabRounds, 3>(a); }
 
 template <int R2, int THREADS, bool SORT>
 static hipError_t build_prepare() {  // > 64 KiB of dynamic LDS needs the attribute
@@ -1401,13 +1399,13 @@ hipError_t bin_prepare_device() {  // once per device (gs_renderer::init)
     if (e == hipSuccess) e = fast_prepare<16>();
     if (e == hipSuccess)
         e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bin_slabs), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)(FastLayout<GS_SLAB_ROUNDS>::WORDS * sizeof(uint32_t)));
+                                (int)(FastLayout<kSlabRounds>::WORDS * sizeof(uint32_t)));
     if (e == hipSuccess)
         e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_slab_work), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)(FastLayout<GS_SLAB_ROUNDS>::WORDS * sizeof(uint32_t)));
+                                (int)(FastLayout<kSlabRounds>::WORDS * sizeof(uint32_t)));
     if (e == hipSuccess)
         e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bin_queue), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)(FastLayout<GS_SLAB_ROUNDS>::WORDS * sizeof(uint32_t)));
+                                (int)(FastLayout<kSlabRounds>::WORDS * sizeof(uint32_t)));
     return e;
 }
 
@@ -1444,10 +1442,10 @@ void launch_bin_level2(const BinLaunch& b, int level, hipStream_t s) {
         else if (level == 3) hipLaunchKernelGGL(k_bin_fast<16>, dim3(bins), dim3(1024), FastLayout<16>::WORDS * sizeof(uint32_t), s, a);
         else if (b.slab_epoch != 0) {
             // one launch: persistent workgroups (one per CU's worth of LDS; more than fit simply find the queue drained) over bins, then slabs
-            hipLaunchKernelGGL(k_bin_queue, dim3(bins < kQueueWorkGroups ? bins : kQueueWorkGroups), dim3(1024), FastLayout<GS_SLAB_ROUNDS>::WORDS * sizeof(uint32_t), s, a);
+            hipLaunchKernelGGL(k_bin_queue, dim3(bins < kQueueWorkGroups ? bins : kQueueWorkGroups), dim3(1024), FastLayout<kSlabRounds>::WORDS * sizeof(uint32_t), s, a);
         } else {
-            hipLaunchKernelGGL(k_bin_slabs, dim3(bins), dim3(1024), FastLayout<GS_SLAB_ROUNDS>::WORDS * sizeof(uint32_t), s, a);
-            hipLaunchKernelGGL(k_slab_work, dim3(kSlabWorkGroups), dim3(1024), FastLayout<GS_SLAB_ROUNDS>::WORDS * sizeof(uint32_t), s, a);
+            hipLaunchKernelGGL(k_bin_slabs, dim3(bins), dim3(1024), FastLayout<kSlabRounds>::WORDS * sizeof(uint32_t), s, a);
+            hipLaunchKernelGGL(k_slab_work, dim3(kSlabWorkGroups), dim3(1024), FastLayout<kSlabRounds>::WORDS * sizeof(uint32_t), s, a);
         }
     } else if (b.bin_shift <= 3) {
         launch_build<1>(a, sort, bins, s);

@@ -8,17 +8,6 @@
 
 namespace gs {
 
-#ifndef GS_BLEND_ASM_ACCUMULATE
-#define GS_BLEND_ASM_ACCUMULATE 1  // the guarded mode's accumulate as one hand-written exec-masked block (A/B: 0 = the compiler's form;
-                                   // the same block for the nine-instruction accumulate of the other modes measured +-0: not kept)
-#endif
-#ifndef GS_BLEND_ASM_LOOP
-#define GS_BLEND_ASM_LOOP 1  // round 5: the guarded mode's pair loop as ONE hand-written loop that keeps `alive` in exec (A/B: 0 = the loop below)
-#endif
-#ifndef GS_BLEND_SALU_DIET
-#define GS_BLEND_SALU_DIET 2  // 2: the pair loop's tail hand-written as well (round 4: blend -3..4 %: the scalar unit is a co-bottleneck)
-#endif
-
 // ---------------------------------------------------------------------------------------
 // blend.  One wave per 8x8 pixel quadrant of a 16x16 tile (4 waves = one workgroup per tile), and the
 // four waves share nothing: their LDS slabs, tables and lists are wave-private, so a quadrant whose pixels have
@@ -85,7 +74,7 @@ __device__ __forceinline__ float min_q_rect(float c00, float c01, float c11, flo
 
 #if defined(GS_BLEND_STATS) || defined(GS_BLEND_CLOCK)
 // debug instrumentation (separate builds, never the shipped library).  GS_BLEND_STATS: the work counters (they live in the compiler's
-// form of the pair loop); GS_BLEND_CLOCK: only the shader clock the kernel ran at, measured around the SHIPPED loops
+// form of the pair loop, which the unguarded modes run: tools/blend_stats.py counts in exp mode 2); GS_BLEND_CLOCK: only the shader clock the kernel ran at, measured around the SHIPPED loops
 __device__ unsigned long long g_blend_stats[12];
 // per wave of the last launch: shader cycles (s_memtime) and constant-rate ticks (s_memrealtime) between its first and its last instruction
 // -- plain stores into the wave's own slot (two atomics per wave on two addresses serialise at 12 ns each: 0.8 ms for config B's 32 640 waves)
@@ -137,10 +126,7 @@ __device__ __forceinline__ void blend_fetch(BlendEntry& e, uint32_t g, const Att
 // blended with EXP = 2 altogether: launch_blend's `unit_opacity`.)  The constants carry 5 % head-room for the
 // second-order terms and the rounding of the thresholds themselves.
 constexpr float kGuardE0 = 2.0e-7f, kGuardE1 = 8.0e-8f;  // measured on the device: E0e = 6.9e-8 (+ 2^-23 = 1.88e-7) with this E1
-#ifndef GS_GUARD_SCALE
-#define GS_GUARD_SCALE 1.0f  // experiments only (tools/r04_guard.py): the window scaled; below 1 the guarantee is gone
-#endif
-constexpr float kGuardUnit = GS_GUARD_SCALE * 1.05f * kGuardE0, kGuardBase = 297.0f * kGuardUnit, kGuardStep = GS_GUARD_SCALE * 1.05f * (kGuardE1 + 2.3841858e-7f);
+constexpr float kGuardUnit = 1.05f * kGuardE0, kGuardBase = 297.0f * kGuardUnit, kGuardStep = 1.05f * (kGuardE1 + 2.3841858e-7f);
 constexpr float kGuardSMax = 297.0f;
 constexpr uint32_t kGuardMaxResolves = 8, kGuardMaxPairs = 4096;
 constexpr uint32_t kGuardList = 384;  // entries of a wave's list of kept entries (LDS, 1.5 KiB per wave: 19 KiB per workgroup, eight per CU)
@@ -165,9 +151,6 @@ static_assert(kGuardHi < 1.0043e-4f && kGuardLo > 9.966e-5f, "the coarse window 
 // chunk's prefetch outstanding: a possibly-pending load on its back-edge would make the compiler wait at every pair).
 __device__ __forceinline__ bool resolve_break(const uint32_t* __restrict__ klist, const uint32_t pos, const AttrRecord* __restrict__ rec,
                                               const uint2* __restrict__ exptab, const int lane, const float fxa, const float fya) {
-#ifdef GS_GUARD_STUB  // experiment: the replay compiled out (wrong decisions; timing only)
-    return false;
-#endif
     float T = 1.0f;
     bool brk = false;
     for (uint32_t p0 = 0; p0 <= pos; p0 += WAVE) {
@@ -212,9 +195,9 @@ __device__ __forceinline__ bool resolve_break(const uint32_t* __restrict__ klist
 //     read again -- after the weight alpha T was formed from the old T; the accumulate runs under exec = m2 & ~mk (one s_andn2);
 //   * the wave's kept entries are staged COMPACTED (rank order), so the loop walks an address and a count: no s_ff1 / s_bitset0.
 // Round 5: 25 vector + 7 scalar instructions per pair on the common path, two branches (the event test and the back edge); round 6: 23.25 + 7 and
-// 1.25 taken branches (below).  Same arithmetic, operation for operation, as the loop it
-// replaces (every product and sum of render.comp:66 rounded on its own, v_exp_f32, fl(o e), min, 1 - alpha, T (1 - alpha), the
-// fused accumulate of the guarded mode): the images of the two loops are bit-identical (tools/ab_image_check.py).
+// 1.25 taken branches (below).  Same arithmetic, operation for operation, as the compiler's form it
+// replaced (every product and sum of render.comp:66 rounded on its own, v_exp_f32, fl(o e), min, 1 - alpha, T (1 - alpha), the
+// fused accumulate of the guarded mode): the images of the two loops were bit-identical (profiles/r05_blend_pair_loop.txt).
 // The loop returns to C++ (event = 1) only where the guard needs it: a lane of m2 inside the guard's COARSE window around 1e-4 (the
 // slice test, one instruction on every pair, sends ~3 % of the pairs to the two compares of the coarse window, still inside the loop;
 // a third of those leave it); the pending pair is then finished by the caller (own window, resolve_break, accumulate) and the loop
@@ -339,9 +322,6 @@ __device__ __forceinline__ uint32_t blend_pair_loop(uint32_t& slab_addr, uint32_
 // way: the parity tests run in this mode); what goes is its mask traffic -- 17 scalar instructions and three taken branches per pair down to
 // 7 and one.  Registers: v[52:63] clobbered -- the record in v[54:63]; binary64 temporaries in the even-aligned pairs v[52:53] (the table
 // entry, then y), v[54:55] (kd, then the cubic), v[58:59] (x, r, r s) as the record's fields retire.
-#ifndef GS_BLEND_ASM_LOOP_EXACT
-#define GS_BLEND_ASM_LOOP_EXACT 1  // 0 (A/B builds): the compiler's form of the exact mode's pair loop
-#endif
 // Round 6: the single unsigned compare on pn = -power and the unroll by four of the guarded loop (see there); gs_expf_libm takes
 // power = -pn through the conversion's sign modifier.  The exp section is thirty issue slots here: pairs no pixel keeps branch over it.
 #define GS_PAIR_EXACT(J)                                                                                                      \
@@ -424,12 +404,14 @@ __device__ __forceinline__ bool blend_walk(const uint2 range, const uint32_t* __
                                            const float rx0, const float ry0, uint64_t alive, float& c0, float& c1, float& c2,
                                            uint32_t& resolved, bool& table_ready, const bool lockstep) {
     const uint2* __restrict__ exptab = exptab_rw;
+    // the guarded mode and the exact one walk the pairs in the hand-written loops above; the other five combinations in the compiler's
+    constexpr bool kAsmLoop = GUARD && EXP == 1 && !CONTRACT;
 #if defined(GS_BLEND_STATS)
-    constexpr bool kAsmLoop = false, kAsmLoopExact = false;  // (the work counters live in the compiler's form of the loop)
+    constexpr bool kAsmLoopExact = false;  // (the work counters live in the compiler's form of the loop)
 #else
-    constexpr bool kAsmLoop = GUARD && EXP == 1 && !CONTRACT && GS_BLEND_ASM_LOOP != 0;
-    constexpr bool kAsmLoopExact = !GUARD && EXP == 2 && !CONTRACT && GS_BLEND_ASM_LOOP_EXACT != 0;
+    constexpr bool kAsmLoopExact = !GUARD && EXP == 2 && !CONTRACT;
 #endif
+    static_assert(!GUARD || kAsmLoop, "the guard lives in blend_pair_loop alone");
     float T = 1.0f;
     c0 = c1 = c2 = 0.0f;
     uint32_t npairs = 0;                       // GUARD: (entry, wave) pairs evaluated so far (bounds every lane's step count)
@@ -492,7 +474,8 @@ __device__ __forceinline__ bool blend_walk(const uint2 range, const uint32_t* __
         if (bm == 0) continue;
         const uint64_t bm0 = bm;      // GUARD: the chunk's kept entries (bm is consumed below)
         const uint32_t kbase = npairs;  // GUARD: how many entries the list of kept entries held before this chunk
-        uint32_t rank = 0;              // GUARD: this lane's entry is the chunk's rank-th kept one
+        // the hand-written loops walk an address and a count: this lane's entry is the chunk's rank-th kept one
+        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(bm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bm, 0u));
         if (GUARD) {
             // abandon: set where a break decision had to be resolved (see there); more pairs than the coarse window allows for
             npairs += (uint32_t)__popcll(bm);
@@ -501,19 +484,20 @@ __device__ __forceinline__ bool blend_walk(const uint2 range, const uint32_t* __
                 break;
             }
             // the wave's list of kept entries, for resolve_break: the Gaussian id of the chunk's r-th kept entry at kbase + r
-            rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(bm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bm, 0u));
             const uint32_t at = kbase + rank;
             if (keep && at < kGuardList) klist[at] = g_cur;
             __builtin_amdgcn_wave_barrier();
         }
-        if constexpr (kAsmLoop) {
-            // the kept entries staged in rank order: the hand-written loop walks an address and a count
-            if (keep) {  // (the conic scaled by a power of two, signs as they are: the loop computes pn = -power; ncut = -cut)
+        if constexpr (kAsmLoop || kAsmLoopExact) {
+            // the kept entries staged in rank order
+            if (keep) {  // (the conic scaled by a power of two, signs as they are: the loops compute pn = -power; ncut = -cut)
                 slab[0][rank] = make_float4(0.5f * cur.co.x, cur.co.y, 0.5f * cur.co.z, cur.co.w);
                 slab[1][rank] = cur.uv;
                 slab[2][rank] = make_float4(cur.bc.x, -cut, 0.0f, 0.0f);
             }
             __builtin_amdgcn_wave_barrier();
+        }
+        if constexpr (kAsmLoop) {
             const uint32_t n_kept = (uint32_t)__popcll(bm0);
             uint32_t rem = n_kept - 1u;
             uint32_t slab_addr = (uint32_t)(uintptr_t)&slab[0][0];  // (the low half of a flat LDS pointer is the LDS offset)
@@ -575,13 +559,6 @@ __device__ __forceinline__ bool blend_walk(const uint2 range, const uint32_t* __
                 --rem;
             }
         } else if constexpr (kAsmLoopExact) {
-            const uint32_t r = __builtin_amdgcn_mbcnt_hi((uint32_t)(bm0 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bm0, 0u));
-            if (keep) {  // staged in rank order, the conic pre-scaled by a power of two (signs as they are: pn = -power), ncut = -cut
-                slab[0][r] = make_float4(0.5f * cur.co.x, cur.co.y, 0.5f * cur.co.z, cur.co.w);
-                slab[1][r] = cur.uv;
-                slab[2][r] = make_float4(cur.bc.x, -cut, 0.0f, 0.0f);
-            }
-            __builtin_amdgcn_wave_barrier();
             blend_pair_loop_exact((uint32_t)(uintptr_t)&slab[0][0], (uint32_t)__popcll(bm0) - 1u, alive, fx, fy, T, c0, c1, c2, exptab);
         } else {
         // conic pre-scaled once per entry: (-c00/2, -c01, -c11/2).  Scaling by a power of two commutes with every
@@ -593,11 +570,7 @@ __device__ __forceinline__ bool blend_walk(const uint2 range, const uint32_t* __
 
         while (bm) {
             const int k = __ffsll((unsigned long long)bm) - 1;
-#if GS_BLEND_SALU_DIET
             asm("s_bitset0_b64 %0, %1" : "+s"(bm) : "s"(k));  // bm &= bm - 1 costs three scalar instructions
-#else
-            bm &= bm - 1;
-#endif
             STAT_ADD(2, 1);                       // (entry, wave) pairs evaluated
             STAT_ADD(3, __popcll(alive));         // lanes alive
             float4 co = slab[0][k];
@@ -634,84 +607,13 @@ __device__ __forceinline__ bool blend_walk(const uint2 range, const uint32_t* __
                 const float alpha = fminf(0.99f, co.w * ex);
                 const float test_T = T * (1 - alpha);
                 // :82-85 break
-                uint64_t mk;
-                if (GUARD) {
-                    mk = m2 & __builtin_amdgcn_ballot_w64(test_T < 0.0001f);
-                    {
-                        uint64_t eq;  // upper half of the bit pattern == 0x38D1: inside the slice around 1e-4
-                        asm("v_cmp_eq_u32_sdwa %0, %1, %2 src0_sel:WORD_1 src1_sel:DWORD" : "=s"(eq) : "v"(test_T), "s"(kGuardSlice));  // (the constant in an SGPR: as a VGPR it was re-materialised at every pair)
-                        const uint64_t sl = m2 & eq;
-                        if (sl != 0) {  // (3 % of the pairs)
-                            uint64_t amb = sl & __builtin_amdgcn_ballot_w64(test_T >= kGuardLo && test_T < kGuardHi);  // the coarse window
-                            if (amb != 0) {  // ... and the lane's own?  (S: the finished chunks; T_cs / test_T - 1: this chunk, this step included)
-                                const float S_now = fminf(kGuardSMax, S + __builtin_fmaf(T_cs * 1.00001f, __builtin_amdgcn_rcpf(test_T), -1.0f));
-                                const float W = __builtin_fmaf((float)npairs, kGuardStep, S_now * kGuardUnit);
-                                const bool inside_own = test_T >= __builtin_fmaf(-0.0001f, W, 0.0001f) && test_T < __builtin_fmaf(0.0001f, W, 0.0001f);
-                                amb &= __builtin_amdgcn_ballot_w64(inside_own);
-                            }
-                            if (amb != 0) {  // ask the reference
-                                if (!table_ready) {  // the wave's copy of libm's table, on first use
-                                    if (lane < 32) {
-                                        const uint64_t v = kExpfTab[lane];
-                                        exptab_rw[lane] = make_uint2((uint32_t)v, (uint32_t)(v >> 32));
-                                    }
-                                    __builtin_amdgcn_wave_barrier();
-                                    table_ready = true;
-                                }
-                                mk &= ~amb;
-                                do {
-                                    const int a = __ffsll((unsigned long long)amb) - 1;
-                                    amb &= amb - 1;
-                                    const float fxa = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(fx), a));
-                                    const float fya = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(fy), a));
-                                    const uint32_t pos = kbase + (uint32_t)__popcll(bm0 & ((1ull << k) - 1ull));  // the tested entry in the list
-                                    // past the list's end, or one pixel too many: the quadrant is abandoned at the next chunk and
-                                    // re-rendered exactly (necessary / cheaper)
-                                    if (pos >= kGuardList || resolved >= kGuardMaxResolves) abandon = true;
-                                    else if (resolve_break(klist, pos, rec, exptab, lane, fxa, fya)) mk |= 1ull << a;
-                                    ++resolved;
-                                } while (amb != 0);
-                            }
-                        }
-                    }
-                } else {
-                    mk = m2 & __builtin_amdgcn_ballot_w64(test_T < 0.0001f);
-                }
+                const uint64_t mk = m2 & __builtin_amdgcn_ballot_w64(test_T < 0.0001f);
                 STAT_ADD(8, __popcll(m2 & ~mk));   // (pixel, entry) pairs that contribute (alpha >= 1/255, before the break)
                 // the reference's loop walks a pixel's list up to and including the entry it breaks at (render.comp:60-85)
                 STAT_ADD(7, (unsigned long long)__popcll(mk) * ((base - range.x) + (uint32_t)k + 1u));
-#if GS_BLEND_ASM_ACCUMULATE
-                if (GUARD) {
-                    // :87 c += color * alpha * T; T = T (1 - alpha) for the lanes that are kept and do not break -- under the exec
-                    // mask, as ONE block of seven instructions: written by the compiler the same region costs two more branches (a
-                    // skip for "no lane updates", which never pays here, and the jump back from the out-of-line block it places
-                    // the region in).  The guarded mode owes the reference its DECISIONS bit for bit (they hang on `power` and on
-                    // the T chain, both evaluated as written) and its pixels to rounding noise: the weight alpha * T is formed once
-                    // and each channel takes one fused multiply-add (every contribution within an ULP of the reference's, no
-                    // cancellation anywhere in this sum)
-                    const uint64_t updm = m2 & ~mk;
-                    uint64_t saved;
-                    float wgt;
-                    asm volatile("s_and_saveexec_b64 %[sv], %[um]\n\t"
-                                 "v_mul_f32 %[w], %[a], %[T]\n\t"
-                                 "v_fmac_f32 %[c0], %[r], %[w]\n\t"
-                                 "v_fmac_f32 %[c1], %[g], %[w]\n\t"
-                                 "v_fmac_f32 %[c2], %[b], %[w]\n\t"
-                                 "v_mov_b32 %[T], %[tt]\n\t"
-                                 "s_or_b64 exec, exec, %[sv]"
-                                 : [c0] "+v"(c0), [c1] "+v"(c1), [c2] "+v"(c2), [T] "+v"(T), [w] "=&v"(wgt), [sv] "=&s"(saved)
-                                 : [um] "s"(updm), [a] "v"(alpha), [r] "v"(uv.z), [g] "v"(uv.w), [b] "v"(bp.x), [tt] "v"(test_T)
-                                 : "scc");
-                } else {
-#endif
                 const bool upd = __builtin_amdgcn_inverse_ballot_w64(m2 & ~mk);
                 if (upd) {  // the accumulate runs under the exec mask: no selects
-                    if (GUARD) {  // (the compiler's form of the block above)
-                        const float wgt = alpha * T;
-                        c0 = __builtin_fmaf(uv.z, wgt, c0);
-                        c1 = __builtin_fmaf(uv.w, wgt, c1);
-                        c2 = __builtin_fmaf(bp.x, wgt, c2);
-                    } else if (CONTRACT) {
+                    if (CONTRACT) {
                         c0 = __builtin_fmaf(uv.z * alpha, T, c0);  // :87  FMA
                         c1 = __builtin_fmaf(uv.w * alpha, T, c1);
                         c2 = __builtin_fmaf(bp.x * alpha, T, c2);
@@ -722,24 +624,11 @@ __device__ __forceinline__ bool blend_walk(const uint2 range, const uint32_t* __
                     }
                     T = test_T;
                 }
-#if GS_BLEND_ASM_ACCUMULATE
-                }
-#endif
-#if GS_BLEND_SALU_DIET == 2
                 // alive &= ~mk; if (alive == 0) bm = 0 -- the pair loop then ends at its own test of bm.  Three scalar
                 // instructions, written out: left to itself the compiler spends six on "did the last pixel just saturate" (it
                 // materialises the condition as a lane mask before branching on it), and the CU's one scalar unit is a
                 // co-bottleneck of this loop (0.64 scalar instructions per vector one)
                 asm volatile("s_andn2_b64 %0, %0, %2\n\ts_cmp_eq_u64 %0, 0\n\ts_cselect_b64 %1, 0, %1" : "+s"(alive), "+s"(bm) : "s"(mk) : "scc");
-#elif GS_BLEND_SALU_DIET
-                // alive &= ~mk, kept opaque: left to itself the compiler turns "did the last pixel just saturate" into
-                // seven scalar instructions of boolean materialisation
-                asm volatile("s_andn2_b64 %0, %0, %1" : "+s"(alive) : "s"(mk) : "scc");
-                if (alive == 0) break;  // every pixel of the quadrant has saturated (the outer loop ends below)
-#else
-                alive &= ~mk;
-                if (alive == 0) bm = 0;
-#endif
             }
         }
         }  // (the compiler's form of the pair loop)

@@ -8,14 +8,6 @@
 
 namespace gs {
 
-#ifndef GS_PRE_AA_BISECT
-#define GS_PRE_AA_BISECT 0  // 1: the antialiased variant takes its per-frame cut by alpha_cut's full bisection (the A/B of DESIGN.md)
-#endif
-
-#ifndef GS_PRE_SH_LDS
-#define GS_PRE_SH_LDS 1  // k_preprocess fetches the SH blocks of a wave's visible Gaussians with LDS-DMA, whole lines at a time
-#endif
-
 // ---------------------------------------------------------------------------------------
 // preprocess.  One thread per Gaussian; position / cov3D / opacity are SoA planes (coalesced 256 B per
 // wave and plane); the SH block is AoS (48 contiguous floats) and is read only by lanes that survive
@@ -37,24 +29,17 @@ struct PreUniforms {
 // 64 float4 with a plane stride of 68 (272 dwords = 16 mod 64: the cooperative reads of 16 consecutive lanes cover all
 // 64 banks once).
 constexpr int kPrePlane = 68, kPreStage = 3 * kPrePlane + 16;  // + 64 scene ids (spatial order: where the records go)
-#if GS_PRE_SH_LDS
 // ... and, ahead of that (the two uses alias: the SH blocks are consumed before the records are staged), the SH blocks of up
 // to 32 of the wave's visible Gaussians, fetched by LDS-DMA: 32 x 192 B = 384 float4 (+ 64 source-lane bytes)
-#ifndef GS_PRE_SH_HALF
-#define GS_PRE_SH_HALF 32
-#endif
-constexpr int kPreShHalf = GS_PRE_SH_HALF;
+constexpr int kPreShHalf = 32;
 constexpr int kPreWaveLds = kPreShHalf * 12 + 4;  // float4 units; >= kPreStage
 static_assert(kPreWaveLds >= kPreStage, "the record stage must fit the wave's LDS slab");
-#else
-constexpr int kPreWaveLds = kPreStage;
-#endif
 
 // preprocess.comp:73-108 compute_sh (degree 3 always; only .x clamped), the channel's terms accumulated in the shader's order.
 // SH(j, k) = coefficient j of channel k.  Written coefficient-major (all three channels take term j before any takes term
 // j + 1): per channel the sequence of operations is the shader's, and a source that lives in LDS can be consumed as it is read
-// (FENCE: a compiler barrier every few terms, so that the 48 reads are not all hoisted into registers at once).
-template <bool FENCE, class SH>
+// (GS_SH_FENCE: a compiler barrier every few terms, so that the 48 reads are not all hoisted into registers at once).
+template <class SH>
 __device__ __forceinline__ void sh_to_rgb(const SH& S, float x, float y, float z, float (&rgb)[3]) {
     const float C2_0 = 1.0925484305920792f, C2_1 = -1.0925484305920792f, C2_2 = 0.31539156525252005f,
                 C2_3 = -1.0925484305920792f, C2_4 = 0.5462742152960396f;
@@ -62,7 +47,7 @@ __device__ __forceinline__ void sh_to_rgb(const SH& S, float x, float y, float z
                 C3_3 = 0.3731763325901154f, C3_4 = -0.4570457994644658f, C3_5 = 1.445305721320277f,
                 C3_6 = -0.5900435899266435f;
     float c[3];
-#define GS_SH_FENCE() do { if (FENCE) asm volatile("" : "+v"(c[0]), "+v"(c[1]), "+v"(c[2]) :: "memory"); } while (0)
+#define GS_SH_FENCE() asm volatile("" : "+v"(c[0]), "+v"(c[1]), "+v"(c[2]) :: "memory")
 #pragma unroll
     for (int k = 0; k < 3; ++k) c[k] = SH_C0 * S(0, k);
 #pragma unroll
@@ -103,10 +88,6 @@ __device__ __forceinline__ void sh_to_rgb(const SH& S, float x, float y, float z
 #undef GS_SH_FENCE
     if (rgb[0] < 0.0f) rgb[0] = 0.0f;
 }
-struct ShFromRegs {
-    float v[48];
-    __device__ __forceinline__ float operator()(int j, int k) const { return v[j * 3 + k]; }
-};
 struct ShFromLds {
     const float* p;
     __device__ __forceinline__ float operator()(int j, int k) const { return p[j * 3 + k]; }
@@ -241,11 +222,7 @@ __device__ __forceinline__ void preprocess_one(const SceneView& sv, const gs_uni
             // never contributes.  The cut is then the scaled opacity's, taken here (the load-time plane holds the unscaled one's).
             const float det_raw = cov.c[0][0] * cov.c[1][1] - cov.c[1][0] * cov.c[0][1];
             opacity = opacity * fminf(1.0f, sqrtf(fmaxf(0.0f, det_raw / det)));
-#if GS_PRE_AA_BISECT
-            acut = alpha_cut(opacity, reinterpret_cast<const uint2*>(kExpfTab));
-#else
             acut = alpha_cut_seeded(opacity, reinterpret_cast<const uint2*>(kExpfTab));
-#endif
         } else {
             acut = sv.acut[i];  // render.comp:78 as a bound on `power` (computed at load from the opacity; the blend's cut)
         }
@@ -266,7 +243,6 @@ __device__ __forceinline__ void preprocess_one(const SceneView& sv, const gs_uni
     // ---- the SH block of the visible Gaussians: 48 contiguous floats each (192 B = three 64-byte lines); only lanes
     // that survived every cull need them, so SH traffic is 192 B per VISIBLE Gaussian.
     float rgb[3] = {0.0f, 0.0f, 0.0f};
-#if GS_PRE_SH_LDS
     // Fetched wave-cooperatively with LDS-DMA (global_load_lds_dwordx4: global -> LDS without passing through VGPRs): the
     // visible lanes publish their lane numbers by rank; then lane l = 12 s + q of each instruction reads 16-byte chunk q of
     // the (5 b + s)-th visible Gaussian -- twelve adjacent lanes cover one Gaussian's three whole lines, where a lane reading
@@ -309,9 +285,9 @@ __device__ __forceinline__ void preprocess_one(const SceneView& sv, const gs_uni
             const float x = dx / len, y = dy / len, z = dz / len;
             const float4* blk = stage + (size_t)(my_rank - first) * chunks;
             if (sv.sh16) {  // binary16 storage, widened exactly
-                sh_to_rgb<true>(ShFromLds16{reinterpret_cast<const uint16_t*>(blk)}, x, y, z, rgb);
+                sh_to_rgb(ShFromLds16{reinterpret_cast<const uint16_t*>(blk)}, x, y, z, rgb);
             } else {
-                sh_to_rgb<true>(ShFromLds{reinterpret_cast<const float*>(blk)}, x, y, z, rgb);
+                sh_to_rgb(ShFromLds{reinterpret_cast<const float*>(blk)}, x, y, z, rgb);
             }
             if (!av.vis) {  // (with the dense lists the entry below carries depth and box: the N-wide planes are not written at all)
                 av.depth[oid] = depth;
@@ -322,48 +298,6 @@ __device__ __forceinline__ void preprocess_one(const SceneView& sv, const gs_uni
         // the record stage, may overwrite the slab
         __builtin_amdgcn_wave_barrier();
     }
-#else
-    // ---- the SH block of the visible Gaussians: 48 contiguous floats each (192 B = three 64-byte lines); only lanes
-    // that survived every cull need them, so SH traffic is 192 B per VISIBLE Gaussian
-    // (A wave-cooperative fetch -- twelve lanes reading the twelve 16-byte chunks of one Gaussian, three full-line requests
-    // instead of twelve quarter-line ones, the chunks handed to their owner through LDS -- measured 5 us SLOWER: 106 VGPRs
-    // instead of 73 while chunks and coefficients are live together, four waves per SIMD instead of six.)
-    if (vis) {
-        ShFromRegs sh;
-        if (sv.sh16) {  // opt-in binary16 storage (gs_scene_quantize_sh): 96 B per visible Gaussian, widened exactly
-            const uint4* __restrict__ shv = reinterpret_cast<const uint4*>(sv.sh16) + (size_t)i * 6;
-#pragma unroll
-            for (int q = 0; q < 6; ++q) {
-                const uint4 t = shv[q];
-                const uint32_t wds[4] = {t.x, t.y, t.z, t.w};
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    sh.v[8 * q + 2 * k + 0] = __half2float(__ushort_as_half((unsigned short)(wds[k] & 0xFFFFu)));
-                    sh.v[8 * q + 2 * k + 1] = __half2float(__ushort_as_half((unsigned short)(wds[k] >> 16)));
-                }
-            }
-        } else {
-            const float4* __restrict__ shv = reinterpret_cast<const float4*>(blob + (size_t)P_SH * N) + (size_t)i * 12;
-#pragma unroll
-            for (int q = 0; q < 12; ++q) {
-                const float4 t = shv[q];
-                sh.v[4 * q + 0] = t.x;
-                sh.v[4 * q + 1] = t.y;
-                sh.v[4 * q + 2] = t.z;
-                sh.v[4 * q + 3] = t.w;
-            }
-        }
-        float dx = px - u.camera_position[0];
-        float dy = py - u.camera_position[1];
-        float dz = pz - u.camera_position[2];
-        const float len = sqrtf(dx * dx + dy * dy + dz * dz);
-        sh_to_rgb<false>(sh, dx / len, dy / len, dz / len, rgb);
-        if (!av.vis) {
-            av.depth[oid] = depth;
-            av.aabb[oid] = make_ushort4((unsigned short)bx0, (unsigned short)by0, (unsigned short)bx1, (unsigned short)by1);
-        }
-    }
-#endif
     // :128 / :176.  With the dense lists of visible Gaussians (av.vis) nothing downstream reads the N-wide planes tiles / depth /
     // aabb -- level 1 streams the lists, level 2 the candidate records -- so they are not written: a culled Gaussian writes
     // nothing at all (the stage taps rebuild the planes from the lists: launch_vis_to_planes)

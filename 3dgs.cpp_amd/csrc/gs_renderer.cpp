@@ -14,7 +14,6 @@
 #include <cstring>
 #include <limits>
 #include <memory>
-#include <string>
 #include <vector>
 
 #include "gs_blend_tuner.h"
@@ -26,18 +25,11 @@ using namespace gs_host;
 // ------------------------------------------------------------------------------------------
 // gs_renderer
 // ------------------------------------------------------------------------------------------
-#ifndef GS_L1_DENSE
-#define GS_L1_DENSE 1  // 0 (A/B builds): level 1 walks the N-wide planes as in round 2
-#endif
 // One complete set of per-frame device buffers + the stream its passes run on.  Frames alternate between
 // sets, so with >= 2 sets the small launch-bound passes of frame i+1 (scans, binning) overlap the
 // VALU-bound blend of frame i on the same GPU.
 struct FrameBuffers {
     hipStream_t stream = nullptr;
-    // CU-partition experiment (GS_CU_MASK_PREP / GS_CU_MASK_BLEND): the blend runs on its own CU-masked stream
-    hipStream_t blend_stream = nullptr;
-    hipEvent_t prep_done = nullptr, blend_done = nullptr;
-    bool blend_recorded = false;
     // per-Gaussian attributes
     DevBuf<uint32_t> tiles;
     DevBuf<float> depth;
@@ -89,16 +81,9 @@ struct FrameBuffers {
     size_t n = 0;
     bool ready = false;
 
-    void init(size_t n_, uint32_t capacity, uint32_t cand_capacity, const std::vector<uint32_t>& mask_prep, const std::vector<uint32_t>& mask_blend, bool dense_lists) {
+    void init(size_t n_, uint32_t capacity, uint32_t cand_capacity, bool dense_lists) {
         n = n_;
-        if (!mask_prep.empty() && !mask_blend.empty()) {
-            HIP_CHECK(hipExtStreamCreateWithCUMask(&stream, static_cast<uint32_t>(mask_prep.size()), mask_prep.data()));
-            HIP_CHECK(hipExtStreamCreateWithCUMask(&blend_stream, static_cast<uint32_t>(mask_blend.size()), mask_blend.data()));
-            HIP_CHECK(hipEventCreateWithFlags(&prep_done, hipEventDisableTiming));
-            HIP_CHECK(hipEventCreateWithFlags(&blend_done, hipEventDisableTiming));
-        } else {
-            HIP_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-        }
+        HIP_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
         tiles.alloc(n);
         depth.alloc(n);
         aabb.alloc(n);
@@ -142,20 +127,11 @@ struct FrameBuffers {
         cand.alloc(3 * static_cast<size_t>(ccap));
         HIP_CHECK(hipMemset(cand.p, 0, 3 * static_cast<size_t>(ccap) * sizeof(uint32_t)));
     }
-    void sync() const {
-        HIP_CHECK(hipStreamSynchronize(stream));
-        if (blend_stream) HIP_CHECK(hipStreamSynchronize(blend_stream));
-    }
-    void sync_nothrow() const {  // (the destructor's path)
-        (void)hipStreamSynchronize(stream);
-        if (blend_stream) (void)hipStreamSynchronize(blend_stream);
-    }
+    void sync() const { HIP_CHECK(hipStreamSynchronize(stream)); }
+    void sync_nothrow() const { (void)hipStreamSynchronize(stream); }  // (the destructor's path)
     ~FrameBuffers() {
         drop_graph();
         if (stream) (void)hipStreamDestroy(stream);
-        if (blend_stream) (void)hipStreamDestroy(blend_stream);
-        if (prep_done) (void)hipEventDestroy(prep_done);
-        if (blend_done) (void)hipEventDestroy(blend_done);
     }
 };
 
@@ -308,30 +284,12 @@ struct gs_renderer {
         if (const char* e = std::getenv("GS_INITIAL_CAND_CAPACITY")) want_cand = std::max<uint64_t>(256, std::strtoull(e, nullptr, 10));
         else if (std::getenv("GS_INITIAL_CAPACITY")) want_cand = std::min<uint64_t>(want_cand, want);  // (the tests' small start applies to both)
         cand_capacity = static_cast<uint32_t>(std::min<uint64_t>(want_cand, capacity));
-        parse_cu_masks();
-        sets[0].init(scene->n, capacity, cand_capacity, mask_prep, mask_blend, scene->n >= dense_min);
-    }
-
-    // Experiment: GS_CU_MASK_PREP / GS_CU_MASK_BLEND = hex strings, most significant CU first,
-    // 256 bits each.  With both set, a frame's passes before the blend run on a stream restricted to the first mask and
-    // the blend on a stream restricted to the second, chained by events.
-    std::vector<uint32_t> mask_prep, mask_blend;
-    static std::vector<uint32_t> parse_mask(const char* hex) {
-        std::vector<uint32_t> words;
-        if (!hex) return words;
-        std::string h(hex);
-        while (h.size() % 8) h.insert(h.begin(), '0');
-        for (size_t i = h.size(); i >= 8; i -= 8) words.push_back(static_cast<uint32_t>(std::stoul(h.substr(i - 8, 8), nullptr, 16)));
-        return words;
-    }
-    void parse_cu_masks() {
-        mask_prep = parse_mask(std::getenv("GS_CU_MASK_PREP"));
-        mask_blend = parse_mask(std::getenv("GS_CU_MASK_BLEND"));
+        sets[0].init(scene->n, capacity, cand_capacity, scene->n >= dense_min);
     }
 
     void set_num_sets(int k) {
         for (int i = 0; i < k; ++i)
-            if (!sets[i].ready) sets[i].init(scene->n, capacity, cand_capacity, mask_prep, mask_blend, scene->n >= dense_min);
+            if (!sets[i].ready) sets[i].init(scene->n, capacity, cand_capacity, scene->n >= dense_min);
         num_sets = k;
     }
 
@@ -426,7 +384,7 @@ struct gs_renderer {
         // list of visible Gaussians, which k_preprocess then writes beside the planes
         const bool l1_any_order = bin_local && geo.bin_shift <= 3;
         // (the lists exist only for scenes of >= dense_min Gaussians: FrameBuffers::init; the blend zeroes their counters)
-        const bool dense_list = GS_L1_DENSE && l1_any_order && n != 0 && n >= dense_min && fb.vis.p && u.width != 0 && u.height != 0;
+        const bool dense_list = l1_any_order && n != 0 && n >= dense_min && fb.vis.p && u.width != 0 && u.height != 0;
         gs::AttrView av{fb.tiles.p, fb.depth.p, fb.aabb.p, fb.rec.p, dense_list ? fb.vis.p : nullptr, dense_list ? fb.vis_count.p : nullptr,
                         fb.vis_region_slots};
         fb.planes_stale = dense_list;
@@ -438,10 +396,9 @@ struct gs_renderer {
             HIP_CHECK(hipMemsetAsync(cnt, 0, sizeof(gs::Counters), stream));
             HIP_CHECK(hipMemsetAsync(fb.ranges.p, 0, 2 * nt * sizeof(uint32_t), stream));  // no Gaussians: every tile (0, 0)
         }
-        if (fb.blend_stream && fb.blend_recorded) HIP_CHECK(hipStreamWaitEvent(stream, fb.blend_done, 0));  // the set's previous blend
         // the frame's launches; `fp` non-null = replayable form (per-frame values read from fb.params), no span events
         uint64_t* const stamps = fb.stamps.p;
-        auto passes = [&](const gs::FrameParams* fp, hipStream_t bstream) {
+        auto passes = [&](const gs::FrameParams* fp) {
             gs::launch_preprocess(sv, u, av, cnt, fp, stamps, antialiased, stream);
             lap(3);
             if (!bin_local && n != 0) {
@@ -517,19 +474,14 @@ struct gs_renderer {
             }
             lap(6);
             // ---- blend ----
-            if (bstream != stream) {
-                HIP_CHECK(hipEventRecord(fb.prep_done, stream));
-                HIP_CHECK(hipStreamWaitEvent(bstream, fb.prep_done, 0));
-            }
             gs::launch_blend(fb.ranges.p, fb.sorted.p, tile_order.p, av, u.width, u.height, d_rgba, d_bgra, cnt,
-                             fused_counters ? sl.h_counters : nullptr, blend_exp_mode(), contract, fp, lockstep, stamps, bstream);
-            gs::launch_frame_end(stamps, sl.h_stamps, fp, bstream);
+                             fused_counters ? sl.h_counters : nullptr, blend_exp_mode(), contract, fp, lockstep, stamps, stream);
+            gs::launch_frame_end(stamps, sl.h_stamps, fp, stream);
             lap(7);
         };
         depth_order = bin_local ? nullptr : fb.dvals[1].p;
         sorted_gid = fb.sorted.p;
-        hipStream_t bstream = fb.blend_stream ? fb.blend_stream : stream;
-        const bool replay = graph_mode && fused_counters && !fb.blend_stream;
+        const bool replay = graph_mode && fused_counters;
         if (replay) {
             *sl.h_params = gs::FrameParams{u, d_rgba, d_bgra, sl.h_counters, sl.h_stamps};
             HIP_CHECK(hipMemcpyAsync(fb.params.p, sl.h_params, sizeof(gs::FrameParams), hipMemcpyHostToDevice, stream));
@@ -543,7 +495,7 @@ struct gs_renderer {
                 hipGraph_t graph = nullptr;
                 HIP_CHECK(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
                 try {
-                    passes(fb.params.p, stream);
+                    passes(fb.params.p);
                 } catch (...) {
                     (void)hipStreamEndCapture(stream, &graph);
                     if (graph) (void)hipGraphDestroy(graph);
@@ -557,14 +509,10 @@ struct gs_renderer {
             }
             HIP_CHECK(hipGraphLaunch(fb.graph_execs[gi], stream));
         } else {
-            passes(nullptr, bstream);
+            passes(nullptr);
         }
-        if (!fused_counters) HIP_CHECK(hipMemcpyAsync(sl.h_counters, cnt, sizeof(gs::Counters), hipMemcpyDeviceToHost, bstream));
-        HIP_CHECK(hipEventRecord(sl.done, bstream));
-        if (fb.blend_stream) {
-            HIP_CHECK(hipEventRecord(fb.blend_done, bstream));
-            fb.blend_recorded = true;
-        }
+        if (!fused_counters) HIP_CHECK(hipMemcpyAsync(sl.h_counters, cnt, sizeof(gs::Counters), hipMemcpyDeviceToHost, stream));
+        HIP_CHECK(hipEventRecord(sl.done, stream));
         HIP_CHECK(hipGetLastError());
 
         sl.level = lv;

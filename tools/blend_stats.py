@@ -9,6 +9,11 @@ walked_pairs        (pixel, entry) pairs the REFERENCE's loop walks: every pixel
 contributing_pairs  of those, the ones with alpha >= 1/255 that are accumulated
 wave_pairs          (entry, 8x8-pixel wave) pairs this implementation evaluates after its exact quadrant culling
 lanes_in_exp        lanes that reach exp() in them
+
+The counters live in the compiler's form of the pair loop, which the guarded default (exp mode 3) does not run, so the frames are
+rendered in exp mode 2.  That counts the same work: every counter is a function of the keep and break decisions alone, and modes 2
+and 3 take the same decisions (the alpha cut is decided on `power`, the break is the reference's or resolved
+exactly).  A quadrant that mode 3 abandons and walks a second time is that mode's cost, not the workload's, and is not counted.
 """
 import argparse
 import ctypes
@@ -43,6 +48,7 @@ def main():
         scene = pkg.Scene.from_records(rec)
         del rec
         rend = pkg.Renderer(scene)
+        rend.set_exp_mode(2)  # (the counted loop: see above)
         u = pkg.camera_uniforms(pkg.make_camera(), w, h)
         out = (ctypes.c_ulonglong * 12)()
         for _ in range(3):  # the first frames may be re-run at a larger sort level: keep the last, clean one
