@@ -3,10 +3,16 @@
 // (Renderer::updateUniforms, src/Renderer.cpp:719-754).  fp32, one rounding per operation,
 // glm 1.0.0's operation order (the reference pins glm at CMakeLists.txt:31-35; glm itself is
 // not vendored, so its published formulas are restated here).  Column-major 4x4: m[c*4+r].
+// Also the order a large scene is read in (spatial_order, at the end; no counterpart in the reference).
+// Plain C++ without a device in sight.
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <limits>
+#include <utility>
+#include <vector>
 
 #include "../../include/gs3d_hip.h"
 
@@ -175,6 +181,53 @@ inline void activate_record(const float* r, float* v) {
         out[j * 3 + 1] = shs[(j - 1) + SH_N + 2];
         out[j * 3 + 2] = shs[(j - 1) + SH_N * 2 + 1];
     }
+}
+
+// ---- the order the per-frame kernels read a large scene in (gs_scene::make_spatial_copy): ascending Morton code of the
+// position, ties by id.
+//   * per axis the finite coordinates' bounding box [lo, hi] is cut into 2^21 cells: cell = min(2^21 - 1, floor(t 2^21)) with
+//     t = (v - lo) / (hi - lo) evaluated in binary64 from the binary32 values;
+//   * a degenerate axis (no finite coordinate, or all of them equal) takes hi = lo + 1 in binary32;
+//   * a non-finite coordinate (NaN, +-inf) maps to cell 0;
+//   * the code interleaves the three cells bit by bit, x lowest: bit 3 b + k of the code is bit b of axis k's cell.
+// tests/test_limit_scenes.py drives it on the CPU (tests/native/spatial_order_sim.cpp) against
+// tests/limit_scenes.py::morton_order, which restates it in numpy: a change of the rules here changes them there.
+inline uint64_t morton_spread21(uint64_t v) {  // 21 bits -> every third bit
+    v &= 0x1FFFFFull;
+    v = (v | v << 32) & 0x1F00000000FFFFull;
+    v = (v | v << 16) & 0x1F0000FF0000FFull;
+    v = (v | v << 8) & 0x100F00F00F00F00Full;
+    v = (v | v << 4) & 0x10C30C30C30C30C3ull;
+    v = (v | v << 2) & 0x1249249249249249ull;
+    return v;
+}
+
+// pos[k]: the n coordinates of axis k (x, y, z).  Returns the scene ids in the order they are read: order[j] = id of read slot j.
+inline std::vector<uint32_t> spatial_order(const float* const pos[3], uint64_t n) {
+    float lo[3], hi[3];
+    for (int k = 0; k < 3; ++k) {
+        lo[k] = std::numeric_limits<float>::infinity();
+        hi[k] = -lo[k];
+        for (uint64_t i = 0; i < n; ++i) {
+            const float v = pos[k][i];
+            if (std::isfinite(v)) lo[k] = std::min(lo[k], v), hi[k] = std::max(hi[k], v);
+        }
+        if (!(hi[k] > lo[k])) hi[k] = lo[k] + 1.0f;
+    }
+    std::vector<std::pair<uint64_t, uint32_t>> keyed(n);
+    for (uint64_t i = 0; i < n; ++i) {
+        uint64_t code = 0;
+        for (int k = 0; k < 3; ++k) {
+            const float v = pos[k][i];
+            const double t = std::isfinite(v) ? (static_cast<double>(v) - lo[k]) / (static_cast<double>(hi[k]) - lo[k]) : 0.0;
+            code |= morton_spread21(static_cast<uint64_t>(std::min(2097151.0, std::max(0.0, t * 2097152.0)))) << k;
+        }
+        keyed[i] = {code, static_cast<uint32_t>(i)};
+    }
+    std::sort(keyed.begin(), keyed.end());
+    std::vector<uint32_t> order(n);
+    for (uint64_t i = 0; i < n; ++i) order[i] = keyed[i].second;
+    return order;
 }
 
 }  // namespace host

@@ -46,7 +46,7 @@ void gs_scene::drop_spatial_copy() {
     spatial_blob.release();
     std::fprintf(stderr, "[gs3d] no memory for the scene's copy in spatial order: rendering from the blob as loaded\n");
 }
-// Spatial order: Morton code of the position (21 bits per axis over the scene's bounding box), ties by id.
+// Spatial order: Morton code of the position (21 bits per axis over the scene's bounding box), ties by id (gs_host_math.h: spatial_order).
 void gs_scene::make_spatial_copy() {
     uint64_t min_n = 4ull << 20;
     if (const char* e = std::getenv("GS_SPATIAL_MIN")) min_n = std::strtoull(e, nullptr, 10);
@@ -55,38 +55,8 @@ void gs_scene::make_spatial_copy() {
     std::vector<float> pos(3 * n);
     for (int k = 0; k < 3; ++k)
         HIP_CHECK(hipMemcpy(pos.data() + static_cast<size_t>(k) * n, blob + static_cast<size_t>(gs::P_POS + k) * st, n * sizeof(float), hipMemcpyDeviceToHost));
-    float lo[3], hi[3];
-    for (int k = 0; k < 3; ++k) {
-        lo[k] = std::numeric_limits<float>::infinity();
-        hi[k] = -lo[k];
-        for (uint64_t i = 0; i < n; ++i) {
-            const float v = pos[static_cast<size_t>(k) * n + i];
-            if (std::isfinite(v)) lo[k] = std::min(lo[k], v), hi[k] = std::max(hi[k], v);
-        }
-        if (!(hi[k] > lo[k])) hi[k] = lo[k] + 1.0f;
-    }
-    auto spread = [](uint64_t v) {  // 21 bits -> every third bit
-        v &= 0x1FFFFFull;
-        v = (v | v << 32) & 0x1F00000000FFFFull;
-        v = (v | v << 16) & 0x1F0000FF0000FFull;
-        v = (v | v << 8) & 0x100F00F00F00F00Full;
-        v = (v | v << 4) & 0x10C30C30C30C30C3ull;
-        v = (v | v << 2) & 0x1249249249249249ull;
-        return v;
-    };
-    std::vector<std::pair<uint64_t, uint32_t>> keyed(n);
-    for (uint64_t i = 0; i < n; ++i) {
-        uint64_t code = 0;
-        for (int k = 0; k < 3; ++k) {
-            const float v = pos[static_cast<size_t>(k) * n + i];
-            const double t = std::isfinite(v) ? (static_cast<double>(v) - lo[k]) / (static_cast<double>(hi[k]) - lo[k]) : 0.0;
-            code |= spread(static_cast<uint64_t>(std::min(2097151.0, std::max(0.0, t * 2097152.0)))) << k;
-        }
-        keyed[i] = {code, static_cast<uint32_t>(i)};
-    }
-    std::sort(keyed.begin(), keyed.end());
-    std::vector<uint32_t> order(n);
-    for (uint64_t i = 0; i < n; ++i) order[i] = keyed[i].second;
+    const float* const planes[3] = {pos.data(), pos.data() + n, pos.data() + 2 * n};
+    const std::vector<uint32_t> order = gs::host::spatial_order(planes, n);
     perm.alloc(n);
     HIP_CHECK(hipMemcpy(perm.p, order.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
     spatial_blob.alloc(gs::blob_floats(n));

@@ -1,13 +1,22 @@
-"""Scenes that stand exactly on a capacity of the binning and blend kernels: the candidates a depth-order level holds, the run
-of equal depths the tie step orders in place, the keys a depth bucket holds before the stable passes take over, the slab cut,
-the items of a level-1 block, the bin box the whole wave emits, the blend's chunks of 64.
+"""Scenes that stand exactly on a capacity or a cooperative step of the per-frame kernels.
+  * binning and blend: the candidates a depth-order level holds, the run of equal depths the tie step orders in place, the keys a
+    depth bucket holds before the stable passes take over, the slab cut, the items of a level-1 block, the bin box the whole
+    wave emits, the blend's chunks of 64, the guard's list, replays and pairs;
+  * k_preprocess (wave_patterns): every count of visible lanes of a wave at which the LDS-DMA fetch of the SH blocks, the wave's
+    run of slots in the dense lists or the four-lanes-per-record store changes shape, in the lowest lanes, the highest, and
+    spread; every exit of a culled lane; a ragged last wave; in index order and in a spatial order that is a known scramble of
+    the ids (morton_order restates gs_host_math.h's spatial_order); and the dense lists full to their last slot (dense_lists_full);
+  * the global depth order (radix_blocks): every shape of the radix passes' grid -- 1 to 4 entries per thread of the scan, a
+    block that owns two tiles, later passes over V << N keys with a tile one key short, full and one over -- with depth
+    patterns of extreme low bytes and equal depths across tiles and blocks.
 
-Nothing here is random.  Every candidate is ONE tiny isotropic Gaussian (radius 3 px) whose centre lies within 2.5 px of a
-tile's centre, so its tile box is that tile and nothing else; the camera is the identity, so view depth is -z bit for bit
-and a scene's depths are written as binary32 bit patterns.  A builder returns a LimitScene: the records, the frame, the
-environment the renderer needs, and `expect` -- the quantities it pins, exact by construction.  The second half of the module
-re-measures those quantities from the oracle's stages (tests/test_limit_scenes.py asserts they are equal, with no GPU) and
-restates the level policy of gs_depth_policy.h for a fresh renderer, which is where the GPU test's predicted stats come from.
+Nothing here is random but the SH coefficients of the wave patterns (a fixed seed).  Every candidate is ONE tiny isotropic
+Gaussian (radius 3 px) whose centre lies within 2.5 px of a tile's centre, so its tile box is that tile and nothing else; the
+camera is the identity, so view depth is -z bit for bit and a scene's depths are written as binary32 bit patterns.  A builder
+returns a LimitScene: the records, the frame, the environment the renderer needs, and `expect` -- the quantities it pins, exact by
+construction.  The second half of the module re-measures those quantities from the oracle's stages (tests/test_limit_scenes.py
+asserts they are equal, with no GPU) and restates the level policy of gs_depth_policy.h for a fresh renderer, which is where the
+GPU test's predicted stats come from.
 
 A plain module: numpy and tests/ only."""
 from dataclasses import dataclass, field
@@ -26,6 +35,9 @@ TIE_RUN_MAX = 65                                    # the longest run of equal d
 THREADS = 1024                                      # of a level-2 workgroup: element e of the ordered list is round e / 1024
 L1_ITEMS, L1_XCD_RUN, L1_BIG_BOX = 1024, 32, 12     # gs_bin.h
 BLEND_CHUNK = 64
+WAVE, PRE_BLOCK = 64, 256                           # gs_device.h: a wave, a workgroup of k_preprocess (four waves)
+VIS_REGIONS = 256                                   # gs_kernels.h: kVisRegions, the dense lists of visible Gaussians
+SORT_TILE, SORT_MAX_BLOCKS, SCAN_THREADS = 2048, 1024, 256   # gs_kernels.h: kSortTileKeys, kSortMaxBlocks; k_radix_scan's workgroup
 DEPTH_2 = 0x40000000                                # the bit pattern of 2.0f: [2, 4) holds 2^23 patterns
 PRIME = 1000003
 
@@ -379,6 +391,297 @@ def guard_pairs(kept):
                       guard=dict(sites=[(27, 27)], want="clean" if kept <= GUARD_PAIRS else "redo"))
 
 
+# ------------------------------------------------------------------------------------------------ the spatial read order
+def morton_order(pos):
+    """gs_host_math.h's spatial_order restated: the scene ids in the order the per-frame kernels read a scene of >= GS_SPATIAL_MIN Gaussians.
+    Per axis 2^21 cells over the finite coordinates' bounding box (hi = lo + 1 in binary32 on a degenerate axis), a non-finite
+    coordinate in cell 0, the three cells interleaved bit by bit with x lowest, ties by id.  The cell is computed with the
+    header's own binary64 operations on the binary32 values -- one subtraction each, one division, a product by 2^21 -- so it
+    is the same number, not an approximation of it."""
+    pos = np.asarray(pos, np.float32)
+    n = len(pos)
+    code = np.zeros(n, np.uint64)
+    for k in range(3):
+        v = pos[:, k]
+        fin = np.isfinite(v)
+        lo, hi = (v[fin].min(), v[fin].max()) if fin.any() else (np.float32(np.inf), np.float32(-np.inf))
+        if not hi > lo:
+            with np.errstate(invalid="ignore"):
+                hi = np.float32(lo + np.float32(1.0))
+        with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+            c = (v.astype(np.float64) - np.float64(lo)) / (np.float64(hi) - np.float64(lo)) * 2097152.0
+        c = np.where(fin & ~np.isnan(c), c, 0.0)              # (std::max(0.0, NaN) is 0.0)
+        cell = np.minimum(2097151.0, np.maximum(0.0, c)).astype(np.uint64)
+        for b in range(21):
+            code |= ((cell >> np.uint64(b)) & np.uint64(1)) << np.uint64(3 * b + k)
+    return np.lexsort((np.arange(n), code)).astype(np.uint32)
+
+
+# ------------------------------------------------------------------------------------------------ preprocess, wave by wave
+WAVE_COUNTS = (0, 1, 4, 5, 6, 9, 10, 11, 20, 21, 31, 32, 33, 37, 42, 43, 59, 60, 61, 63, 64)
+WAVE_PLACEMENTS = ("lowest", "highest", "spread")
+WAVE_TAILS = ("ends_group", "mid_group")
+WAVE_RAGGED = 37                                    # valid lanes of the ragged last wave
+CULL_KINDS = ("behind", "near", "off_grid")
+_WAVE_FRAME = (1152, 128)
+_ANCHOR = 1e7
+
+
+def placement_mask(count, placement):
+    """The visible lanes of a wave, as a 64-bit mask (bit l = lane l)."""
+    if placement == "lowest":
+        lanes = range(count)
+    elif placement == "highest":
+        lanes = range(WAVE - count, WAVE)
+    else:
+        lanes = [(k * WAVE + WAVE // 2) // count for k in range(count)]   # count 1: lane 32
+    return sum(1 << l for l in lanes)
+
+
+def _wave_design(order, tail):
+    """Per wave, in read order: (valid lanes, mask of visible lanes).  63 waves of (placement, count), then with tail
+    "mid_group" one wave of every other lane, then the ragged wave: lane 0, every third lane and its last lane -- but in
+    spatial order the first and the last read slot hold the anchors, which are culled."""
+    waves = [(WAVE, placement_mask(c, p)) for p in WAVE_PLACEMENTS for c in WAVE_COUNTS]
+    if tail == "mid_group":
+        waves.append((WAVE, sum(1 << l for l in range(1, WAVE, 2))))
+    ragged = sum(1 << l for l in range(0, WAVE_RAGGED, 3)) | 1 << (WAVE_RAGGED - 1)
+    if order == "spatial":
+        ragged &= ~(1 << (WAVE_RAGGED - 1))
+    waves.append((WAVE_RAGGED, ragged))
+    assert waves[0][1] & 1 == 0                     # read slot 0 is culled in either order
+    return waves
+
+
+def wave_patterns(order, tail="ends_group"):
+    """k_preprocess at every count of visible lanes.  One wave per (count, placement), counts WAVE_COUNTS -- the steps of the
+    LDS-DMA fetch of the SH blocks (5 | 6 and 10 | 11 Gaussians per instruction, 32 | 33 per round, 60 lanes that fetch) and of
+    the record store -- placed in the lowest lanes, the highest lanes, or spread over the wave; then a ragged wave of 37 lanes,
+    which ends the last workgroup (tail "ends_group": 64 waves) or is followed by three waves without any Gaussian ("mid_group":
+    one more wave first, so that the ragged one is the first of its workgroup).  The culled lanes of a wave take the kernel's
+    exits in turn: behind the camera, inside the near cut (z = -0.19), a tile box that is empty (centred three frame heights off
+    the grid).
+
+    The visible ones are _splats with a 0.5 px footprint (radius 3 still, one tile each; the antialiased mode's factor is then
+    0.45 instead of 3e-4, so its frames are not black) and 45 SH rest coefficients ~ N(0, 0.6) from a fixed seed: a swapped
+    block or 16-byte chunk changes the colour.
+
+    order "spatial" (GS_SPATIAL_MIN=0): the Gaussian in read slot j has scene id sigma(j) = (PRIME j + 12345) mod N, and the
+    positions are such that the order of gs_host_math.h's spatial_order IS sigma.  World x strictly increases with the read slot (the splat's
+    pixel is then computed from it and its own depth: depths span 4096 binary32 patterns, which moves a pixel by < 0.3 px);
+    two culled anchors at y = z = -9999995 and +10000005 (read slots 0 and N - 1) make the y and z cells 9.5 units wide with
+    0 near the middle of one, so the whole cluster shares its y and its z cell and the code orders by x alone."""
+    w, h = _WAVE_FRAME
+    waves = _wave_design(order, tail)
+    n = sum(v for v, _ in waves)
+    valid_before = np.cumsum([0] + [v for v, _ in waves])
+    vis = np.zeros(n, bool)
+    kind = np.full(n, -1)
+    for wv, (valid, mask) in enumerate(waves):
+        lanes = np.arange(valid)
+        on = np.array([(mask >> l) & 1 for l in range(valid)], bool)
+        vis[valid_before[wv] + lanes] = on
+        off = lanes[~on]
+        kind[valid_before[wv] + off] = np.arange(len(off)) % 3
+    j = np.arange(n, dtype=np.int64)
+    nvis = int(vis.sum())
+    bits = np.full(n, DEPTH_2, np.uint32)
+    bits[vis] = _spread_bits(nvis, span=4096)
+    tz = bits.view(np.float32).astype(np.float64)
+    tan_x = np.tan(np.radians(float(np.float32(FOV))) / 2.0)
+    cols = w // 16
+    u = j * cols / n                                             # strictly increasing: the column and the place inside it
+    nominal = 16.0 * np.floor(u) + 5.5 + 4.0 * (u - np.floor(u))
+    x_world = _ndc(nominal, w) * 2.0 * tan_x
+    px = ((x_world / (tz * tan_x) + 1.0) * w - 1.0) / 2.0
+    assert (np.abs(px - nominal) < 0.3).all()
+    py = 16.0 * ((j * 5) % (h // 16)) + 7.5 + ((j * 3) % 5 - 2)
+    rec = _splats(bits, None, None, w, h, pixel=(px, py))
+    focal = w / (2.0 * tan_x)
+    rec[:, 55:58] = np.log(0.5 * tz / focal)[:, None]            # 0.5 px: lambda = 0.25 + 0.3 + sqrt(0.1), radius ceil(2.79)
+    rec[:, 9:54] = (0.6 * np.random.default_rng(20240607).normal(size=(n, 45))).astype(np.float32)
+    rec[kind == 0, 2] = np.float32(2.0)
+    rec[kind == 1, 2] = np.float32(-0.19)
+    rec[kind == 2, 1] = np.float32(6.0 * tan_x * h / w)          # NDC y = -3 at depth 2
+    env = {"GS_SPATIAL_MIN": "1000000000"}
+    sigma = j
+    if order == "spatial":
+        env = {"GS_SPATIAL_MIN": "0"}
+        for slot, a in ((0, np.float32(-_ANCHOR + 5.0)), (n - 1, np.float32(_ANCHOR + 5.0))):
+            assert not vis[slot]
+            rec[slot, 1:3] = (a, a)                               # (x stays: the least and the greatest of the scene)
+        sigma = (j * PRIME + 12345) % n
+        out = np.empty_like(rec)
+        out[sigma] = rec
+        rec = out
+        assert np.array_equal(morton_order(rec[:, :3]), sigma)
+    masks = [m for _, m in waves]
+    e = dict(n=n, visible=nvis, wave_masks=masks, ragged_lanes=WAVE_RAGGED,
+             placements={p: list(WAVE_COUNTS) for p in WAVE_PLACEMENTS}, cull_kinds_in_every_wave=True, tiles_per_visible=1,
+             waves_after_the_ragged_one=(-len(waves)) % (PRE_BLOCK // WAVE))
+    return LimitScene(f"wave_patterns/{order}/{tail}", rec, w, h, env, f"{len(waves)} waves of k_preprocess, {nvis} of {n} visible", e)
+
+
+def read_order(scene):
+    """The scene ids in the order k_preprocess reads them."""
+    if scene.env.get("GS_SPATIAL_MIN") == "0":
+        return morton_order(scene.records[:, :3])
+    return np.arange(len(scene.records), dtype=np.uint32)
+
+
+def _measure_waves(scene, ref, m):
+    order = read_order(scene)
+    n = len(order)
+    tiles = ref["tiles"][order]
+    lanes = np.zeros(-(-n // WAVE) * WAVE, bool)
+    lanes[:n] = tiles != 0
+    m["wave_masks"] = [sum(1 << l for l in np.nonzero(row)[0].tolist()) for row in lanes.reshape(-1, WAVE)]
+    m["ragged_lanes"] = n % WAVE
+    m["waves_after_the_ragged_one"] = (-len(m["wave_masks"])) % (PRE_BLOCK // WAVE)
+    m["placements"] = {p: [c for c in WAVE_COUNTS if placement_mask(c, p) in m["wave_masks"][:-1]] for p in WAVE_PLACEMENTS}
+    m["tiles_per_visible"] = int(tiles.max())
+    # the exit a culled Gaussian takes, from its record: behind (z > 0), the near cut (0 > z >= -0.2), else its box
+    z = scene.records[order, 2]
+    kind = np.where(z > 0, 0, np.where(z >= -0.2, 1, 2))
+    ok = True
+    for wv in range(len(m["wave_masks"])):
+        k = kind[wv * WAVE:(wv + 1) * WAVE][tiles[wv * WAVE:(wv + 1) * WAVE] == 0]
+        ok &= len(k) < 3 or set(k.tolist()) == {0, 1, 2}
+    m["cull_kinds_in_every_wave"] = bool(ok)
+
+
+def dense_lists_full():
+    """262144 Gaussians, all visible, with the dense lists on: the smallest scene in which every one of the 256 lists is full to
+    its last slot -- vis_region_slots = 1024 = the four workgroups of 256 that append to a list (region = (i / 256) % 256)."""
+    sc = level1_count(VIS_REGIONS * L1_ITEMS, w=1152, h=1024)
+    assert sc.expect["fullest_bin"][3] <= LEVEL_LIMITS[0]
+    sc.name = "dense_lists_full"
+    sc.env = {"GS_L1_DENSE_MIN": "0"}
+    sc.pins = "256 dense lists of 1024 entries in 1024 slots"
+    sc.expect["list_fill"] = dict(lists=VIS_REGIONS, slots=L1_ITEMS, fewest=L1_ITEMS, most=L1_ITEMS)
+    return sc
+
+
+def vis_region_slots(n):
+    """gs_bin_l1.hip: vis_region_slots."""
+    groups = (n + PRE_BLOCK - 1) // PRE_BLOCK
+    slots = (groups + VIS_REGIONS - 1) // VIS_REGIONS * PRE_BLOCK
+    return L1_ITEMS if slots == 0 else (slots + L1_ITEMS - 1) // L1_ITEMS * L1_ITEMS
+
+
+# ------------------------------------------------------------------------------------------------ the global path's grid
+RADIX_SIZES = (524288, 524289, 1048577, 1572865, 2097152, 2097153)
+RADIX_SMALL_V = (2047, 2048, 2049, 4097)
+_RADIX_FRAME = (1152, 1024)
+
+
+def radix_grid(n):
+    """(blocks, entries per thread of k_radix_scan) of a scene of n Gaussians: gs_renderer.cpp, gs_radix.hip."""
+    blocks = max(1, min(SORT_MAX_BLOCKS, (n + SORT_TILE - 1) // SORT_TILE))
+    return blocks, (blocks + SCAN_THREADS - 1) // SCAN_THREADS
+
+
+def radix_tiles_of_block(count, blocks):
+    """[t0, t1) per block over `count` keys: t0 = b ntiles / blocks (k_radix_hist, k_radix_scatter)."""
+    ntiles = (count + SORT_TILE - 1) // SORT_TILE
+    b = np.arange(blocks + 1, dtype=np.int64)
+    t = b * ntiles // blocks
+    return t[:-1], t[1:]
+
+
+def _radix_whole_tiles(n):
+    """The tiles of the first pass (2048 ids each) that are visible as a whole.  With one tile per block EVERY tile border is a
+    change of the owning block, and whole tiles on both sides of each of them would be the whole scene: taken are the first two
+    tiles, the last two (the last one ragged), both sides of the block numbers 256, 512 and 768 -- where k_radix_scan's threads
+    take one more entry each -- and the tiles of a block that owns two, with the block before it."""
+    blocks, _ = radix_grid(n)
+    ntiles = (n + SORT_TILE - 1) // SORT_TILE
+    t0, t1 = radix_tiles_of_block(n, blocks)
+    tiles = {0, 1, ntiles - 2, ntiles - 1}
+    for b in (256, 512, 768):
+        if b < blocks:
+            tiles |= {int(t1[b - 1]) - 1, int(t0[b])}
+    for b in np.nonzero(t1 - t0 > 1)[0].tolist():
+        tiles |= set(range(int(t0[b]) - 1, int(t1[b])))
+    return sorted(tiles)
+
+
+def radix_blocks(n, v=None):
+    """n Gaussians behind the camera but for the visible ones, on the global path: the radix passes' grid is sized by n (blocks =
+    min(1024, ceil(n / 2048)): RADIX_SIZES give 256, 257, 513, 769, 1024 and 1024 blocks over 1025 tiles) while the passes after the
+    first run over the V visible keys only, so that most blocks own no tile.
+    v None: visible are every 97th id and the whole tiles of _radix_whole_tiles (tens of thousands).  v given: exactly v ids spread
+    evenly from the first id to the last (RADIX_SMALL_V: the later passes' single tile one key short, full, and one and two tiles
+    with one key more).
+    Depths: distinct patterns scrambled against the ids; the eight patterns whose three low bytes are each 0x00 or 0xFF, each in
+    three tiles (so equal depths in different tiles and blocks); five more groups of five equal depths, each group's ids a fifth
+    of the scene apart; and, where a block owns two tiles, the last id (alone in the block's second tile) at the depth of an id of
+    the block's first tile, so that the carry between a block's tiles moves a cursor that is then used, in every pass."""
+    w, h = _RADIX_FRAME
+    blocks, per = radix_grid(n)
+    ntiles = (n + SORT_TILE - 1) // SORT_TILE
+    if v is None:
+        mask = np.zeros(n, bool)
+        mask[::97] = True
+        for t in _radix_whole_tiles(n):
+            mask[t * SORT_TILE:(t + 1) * SORT_TILE] = True
+        ids = np.nonzero(mask)[0]
+    else:
+        ids = (np.arange(v, dtype=np.int64) * (n - 1)) // (v - 1)
+    nv = len(ids)
+    bits = _spread_bits(nv).astype(np.int64)
+    third = nv // 3
+    for c in range(8):                                           # 0x40 bb bb bb: depths 2.0 .. 2.99
+        pattern = DEPTH_2 | (0xFF0000 if c & 4 else 0) | (0xFF00 if c & 2 else 0) | (0xFF if c & 1 else 0)
+        for k in range(3):
+            bits[k * third + 100 + 37 * c] = pattern
+    for g in range(5):
+        bits[(g * 7 + 3 + np.arange(5) * (nv // 5)) % nv] = DEPTH_2 + 7777 * (g + 1) + 1
+    t0, t1 = radix_tiles_of_block(n, blocks)
+    two = np.nonzero(t1 - t0 > 1)[0]
+    if len(two) and v is None:
+        first_tile = int(t0[two[0]])
+        bits[-1] = bits[np.searchsorted(ids, first_tile * SORT_TILE + 5)]   # (the whole tile is visible: that id is)
+    i = np.arange(nv, dtype=np.int64)
+    t = (i * 37) % ((w // 16) * (h // 16))
+    rec = np.zeros((n, RECORD_FLOATS), np.float32)
+    rec[:, 2] = 3.0                                              # behind the camera
+    rec[:, 55:58] = np.float32(np.log(3e-5))
+    rec[:, 58] = 1.0
+    rec[ids] = _splats(bits.astype(np.uint32), t % (w // 16), t // (w // 16), w, h)
+    e = dict(n=n, visible=nv, radix=dict(blocks=blocks, per=per, blocks_owning_two_tiles=int(len(two)),
+                                         tiles_of_the_later_passes=(nv + SORT_TILE - 1) // SORT_TILE),
+             low_byte_patterns_in_several_tiles=8, equal_depths_across_blocks=True)
+    if len(two) and v is None:
+        e["radix"]["carry_shares_a_digit"] = [True] * 4
+    return LimitScene(f"radix_blocks/{n}/{'grid' if v is None else v}", rec, w, h, {}, f"N = {n}: {blocks} blocks, V = {nv}", e)
+
+
+def _measure_radix(scene, ref, m):
+    n = len(ref["tiles"])
+    blocks, per = radix_grid(n)
+    t0, t1 = radix_tiles_of_block(n, blocks)
+    two = np.nonzero(t1 - t0 > 1)[0]
+    ids = np.nonzero(ref["tiles"])[0]
+    bits = ref["attr"]["depth"][ids].view(np.uint32).astype(np.int64)
+    m["radix"] = dict(blocks=blocks, per=per, blocks_owning_two_tiles=int(len(two)),
+                      tiles_of_the_later_passes=(len(ids) + SORT_TILE - 1) // SORT_TILE)
+    if "carry_shares_a_digit" in scene.expect["radix"]:
+        tile = ids // SORT_TILE
+        first = t0[two[0]] if len(two) else -2                   # (no such block: nothing shares anything)
+        a, b = bits[tile == first], bits[tile == first + 1]
+        m["radix"]["carry_shares_a_digit"] = [bool(set(((a >> s) & 255).tolist()) & set(((b >> s) & 255).tolist())) for s in (0, 8, 16, 24)]
+    tile = ids // SORT_TILE
+    low = bits & 0xFFFFFF
+    combos = [(0xFF0000 if c & 4 else 0) | (0xFF00 if c & 2 else 0) | (0xFF if c & 1 else 0) for c in range(8)]
+    m["low_byte_patterns_in_several_tiles"] = sum(len(set(tile[low == p].tolist())) > 1 for p in combos)
+    order = np.lexsort((ids, bits))
+    sb, st = bits[order], tile[order]
+    block_of_tile = np.searchsorted(t1, np.arange(int(t1[-1])), side="right")
+    same = sb[1:] == sb[:-1]
+    m["equal_depths_across_blocks"] = bool((same & (st[1:] != st[:-1]) & (block_of_tile[st[1:]] != block_of_tile[st[:-1]])).any())
+
+
 # ================================================================================================ measuring
 def tiles_across(pixels):
     return (pixels + 15) // 16
@@ -423,6 +726,14 @@ def measure(scene, ref):
     """The quantities of scene.expect, recomputed from the oracle's stages alone."""
     m = {"n": len(ref["tiles"]), "visible": int((ref["tiles"] != 0).sum())}
     e = scene.expect
+    if "wave_masks" in e:
+        _measure_waves(scene, ref, m)
+    if "radix" in e:
+        _measure_radix(scene, ref, m)
+    if "list_fill" in e:
+        region = (np.nonzero(ref["tiles"])[0] // PRE_BLOCK) % VIS_REGIONS
+        fill = np.bincount(region, minlength=VIS_REGIONS)
+        m["list_fill"] = dict(lists=len(fill), slots=vis_region_slots(m["n"]), fewest=int(fill.min()), most=int(fill.max()))
     if "instances" in e:
         m["instances"] = len(ref["keys"])
     if "l1_blocks" in e:

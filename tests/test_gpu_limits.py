@@ -1,8 +1,12 @@
-"""The binning and blend kernels at the exact edge of their capacities (scenes: tests/limit_scenes.py; that they stand on the
-edge: tests/test_limit_scenes.py, on the CPU).  Every case: the stage taps bit for bit against the oracle, the image bit for
-bit in exp mode 2, the default blend (mode 3) within the guarded tolerance, and the frame's stats -- level, path, re-runs, bin
-edge, fullest bin, candidates -- equal to what the restated policy predicts for a fresh renderer.  A case that is no longer
-on its edge FAILS: the pinned quantity is re-measured from the oracle's stages here too.
+"""The per-frame kernels at the exact edge of their capacities and of their cooperative steps (scenes: tests/limit_scenes.py; that
+they stand on the edge: tests/test_limit_scenes.py, on the CPU).  Every case: the stage taps bit for bit against the oracle, the
+image bit for bit in exp mode 2, the default blend (mode 3) within the guarded tolerance, and the frame's stats -- level, path,
+re-runs, bin edge, fullest bin, candidates -- equal to what the restated policy predicts for a fresh renderer.  A case that is
+no longer on its edge FAILS: the pinned quantity is re-measured from the oracle's stages here too.
+
+Binning and blend: every capacity.  k_preprocess: every count of visible lanes of a wave at which its SH fetch, its run of slots
+in the dense lists or its record store changes shape, under every combination of SH storage, read order, dense lists and the
+antialiased mode, and the dense lists full to their last slot.  The global depth order: every shape of its grid.
 
 Not covered, and why:
   * kMaxSlabs = 16 and the planner's `remaining > MAXC` exit: a bin of <= 65535 candidates cannot be cut into more than 11
@@ -10,12 +14,20 @@ Not covered, and why:
     reachable case, 11 slabs of which five are full, is test_slab_planning[most].
   * kMsdBucketMax has no counter: 64 and 65 keys in a bucket must give the same lists, so those cases pin that BOTH orders are
     right at the hand-over, not which one ran.
+  * k_preprocess's `det <= 0` exit: the 0.3 dilation keeps the determinant positive for every finite covariance, so no culled
+    lane of the wave patterns takes it (they take the near cut, on either side of the camera, and the empty tile box).
+  * a block of the radix passes that owns MORE than two tiles, and a carry between a block's tiles in the passes after the
+    first: both need more than 2 097 152 keys (N > 3 145 728, V > 2 097 152); the full-size tests run them.
 """
 import numpy as np
 import pytest
 
+import aa_reference as aa
+import float64_check as chk
 import limit_scenes as ls
-from helpers import assert_guarded_close, assert_images_identical, compare_stages, oracle_frame
+import np_reference as npr
+from float64_cases import Frame
+from helpers import assert_guarded_close, assert_images_identical, compare_stages, expected_depth_order, oracle_frame
 
 pytestmark = pytest.mark.gpu
 
@@ -273,3 +285,154 @@ def test_guard_pairs_per_quadrant(pkg, oracle, gpu, monkeypatch, kept):
         assert redo == 0
     else:
         assert redo == 1 and same
+
+
+# ------------------------------------------------------------------------------------------------ preprocess, wave by wave
+AA_RECORD_TAPS = ("radius", "conic_opacity", "uv_rg", "b", "alpha_cut")
+_wave_refs = {}
+
+
+def _wave_reference(oracle, order, tail, sh16):
+    """The scene, the oracle's frame of it (on coefficients rounded to binary16 where the scene is read from that storage), its
+    re-measured pins and the float64 frame description: computed once per (order, tail, storage), shared by the cases, read only."""
+    key = (order, tail, sh16)
+    if key not in _wave_refs:
+        scene = ls.wave_patterns(order, tail)
+        verts, u_ref, ref = oracle_frame(oracle, scene.records, scene.width, scene.height)
+        got = ls.measure(scene, ref)
+        for name, want in scene.expect.items():
+            assert got[name] == want, f"{scene.name} missed its pattern: {name} is {got[name]}, not {want}"
+        if sh16:
+            verts["sh"] = verts["sh"].astype(np.float16).astype(np.float32)
+            ref = oracle.stages(verts, u_ref)
+        frame = Frame(scene.name, scene.records, fov=ls.FOV, width=scene.width, height=scene.height, sh16=sh16)
+        _wave_refs[key] = (scene, verts, u_ref, ref, frame)
+    return _wave_refs[key]
+
+
+def _all_taps(rend, u):
+    """Every stage tap of the last frame, the record's fields of the visible Gaussians only."""
+    tiles = rend.stage("tiles")
+    vis = tiles != 0
+    out = dict(tiles=tiles, depth=rend.stage("depth")[vis], aabb=rend.stage("aabb").reshape(-1, 4)[vis])
+    for name in AA_RECORD_TAPS:
+        t = rend.stage(name)
+        out[name] = (t.reshape(len(tiles), -1)[vis] if t.size != len(tiles) else t[vis]).view(np.uint32)
+    for name in ("sorted_tile", "sorted_gid"):
+        out[name] = rend.stage(name)
+    out["ranges"] = rend.stage("ranges", u)
+    return out
+
+
+@pytest.mark.parametrize("antialiased", [False, True], ids=["plain", "antialiased"])
+@pytest.mark.parametrize("dense_min", ["1000000000", "0"], ids=["planes", "dense_lists"])
+@pytest.mark.parametrize("order", ["index", "spatial"])
+@pytest.mark.parametrize("sh16", [False, True], ids=["fp32", "binary16"])
+@pytest.mark.parametrize("tail", ls.WAVE_TAILS)
+def test_preprocess_at_every_visible_lane_count(pkg, oracle, gpu, monkeypatch, tail, sh16, order, dense_min, antialiased):
+    """k_preprocess's wave-cooperative steps -- the LDS-DMA fetch of the SH blocks by rank, the wave's run of slots in the dense
+    lists, the four-lanes-per-record store through the scene ids -- at every count and placement of visible lanes
+    (limit_scenes.wave_patterns), for each combination of SH storage, read order, level-1 input and the antialiased mode.  The
+    plain frame: every tap and the mode-2 image bit for bit against the oracle, the default blend within the guarded tolerance,
+    V and N, and the taps against float64.  The antialiased frame: test_gpu_antialiased.py's contract."""
+    scene, verts, u_ref, ref, frame = _wave_reference(oracle, order, tail, sh16)
+    monkeypatch.delenv("GS_SORT_PATH", raising=False)
+    for k, v in {**scene.env, "GS_L1_DENSE_MIN": dense_min}.items():
+        monkeypatch.setenv(k, v)
+    label = f"{scene.name} {'binary16' if sh16 else 'fp32'} dense_min {dense_min}"
+    u = pkg.camera_uniforms(pkg.make_camera(), scene.width, scene.height)
+    assert u.tobytes() == u_ref.tobytes()
+    gs = pkg.Scene.from_records(scene.records, device=0)
+    made = [gs]
+    try:
+        if sh16:
+            gs.quantize_sh()
+        rend = pkg.Renderer(gs)
+        made.append(rend)
+        _assert_frame(pkg, rend, u, ref, scene, None, label)
+        out = chk.outputs_from_hip(rend, u)
+        rep = chk.assert_matches_float64(out, frame, label=f"{label} (HIP taps)")
+        assert (rep["radius_explained"], rep["box_explained"], rep["visibility_explained"]) == (0, 0, 0)
+        if not antialiased:
+            return
+        off = _all_taps(rend, u)
+        plain = rend.stage("conic_opacity").reshape(-1, 4)[:, 3].copy()
+        rend.set_antialiased(True)
+        img_on, _ = rend.render_host(u)
+        st = rend.stats()
+        assert st.num_visible == scene.expect["visible"] and st.num_gaussians == scene.expect["n"]
+        on = _all_taps(rend, u)
+        # taps other than the opacity and its alpha cut: the mode-off frame's
+        for name in off:
+            if name not in ("conic_opacity", "alpha_cut"):
+                np.testing.assert_array_equal(on[name], off[name], err_msg=f"{label}: tap {name} with the mode on")
+        np.testing.assert_array_equal(on["conic_opacity"][:, :3], off["conic_opacity"][:, :3])
+        vis = on["tiles"] != 0
+        scaled = rend.stage("conic_opacity").reshape(-1, 4)[:, 3]
+        assert (scaled[vis] < plain[vis]).all() and (on["alpha_cut"].view(np.float32) >= off["alpha_cut"].view(np.float32)).all()
+        # the frame: the plain frame of S', on the device and from the oracle
+        prime = verts.copy()
+        prime["scale_opacity"][vis, 3] = scaled[vis]
+        s2 = pkg.Scene.from_vertices(prime, device=0)
+        made.append(s2)
+        if sh16:
+            s2.quantize_sh()
+        r2 = pkg.Renderer(s2)
+        made.append(r2)
+        img2, _ = r2.render_host(u)
+        np.testing.assert_array_equal(img_on.view(np.uint32), img2.view(np.uint32))
+        two = _all_taps(r2, u)
+        for name in on:
+            np.testing.assert_array_equal(on[name], two[name], err_msg=f"{label}: tap {name}, mode on vs the plain frame of S'")
+        ref2 = oracle.stages(prime, u_ref)
+        assert_images_identical(img_on, ref2["image"], label=f"{label}: antialiased frame vs the oracle on S'")
+        assert (ref2["image"][..., :3] != 0).any()
+        compare_stages(pkg, rend, u, ref2)
+        np.testing.assert_array_equal(on["alpha_cut"], oracle.alpha_cut(prime["scale_opacity"][:, 3])[vis].view(np.uint32))
+        assert_guarded_close(rend, u, ref2["image"], label=f"{label}: antialiased, default blend vs the oracle on S'")
+        # the factor against float64, within aa_reference's bound
+        pre = npr.preprocess(npr.activate(scene.records), frame.camera64())
+        sub = {k: (v[vis] if isinstance(v, np.ndarray) and v.shape[:1] == (len(vis),) else v) for k, v in pre.items()}
+        comp_gpu = scaled[vis].astype(np.float64) / plain[vis]
+        want = aa.comp64(sub)
+        bad = aa.comp_violations(comp_gpu, sub, want)
+        worst = float((np.abs(comp_gpu ** 2 - want ** 2) / aa.comp_tolerance(sub)).max())
+        print(f"{label}: comp in [{comp_gpu.min():.3g}, {comp_gpu.max():.3g}], worst |d comp^2| / bound = {worst:.3g}")
+        assert not bad.any(), f"{label}: {bad.sum()} of {len(bad)} factors outside the bound; worst |d comp^2| / bound = {worst:.3g}"
+    finally:
+        for o in reversed(made):
+            o.close()
+
+
+def test_dense_lists_full_to_the_last_slot(pkg, oracle, gpu, monkeypatch):
+    """262144 Gaussians, all visible: each of the 256 dense lists receives exactly its 1024 slots' worth, from four workgroups."""
+    _level1(pkg, oracle, monkeypatch, ls.dense_lists_full(), "0", 0)
+
+
+# ------------------------------------------------------------------------------------------------ the global path's grid
+@pytest.mark.parametrize("n,v", [(n, None) for n in ls.RADIX_SIZES] + [(ls.RADIX_SIZES[1], v) for v in ls.RADIX_SMALL_V])
+def test_global_depth_order_grid(pkg, oracle, gpu, monkeypatch, n, v):
+    """The radix passes' grid, blocks = min(1024, ceil(N / 2048)): k_radix_scan's 1, 2, 3 and 4 entries per thread (256 | 257,
+    513, 769 blocks), 1024 blocks of one tile each and 1024 blocks of which the last owns two (the carry between a block's tiles),
+    with the later passes running over V << N keys -- one tile one key short, full, and one key into the next among them."""
+    scene = ls.radix_blocks(n, v)
+    gs, rend, u, ref = _frame(pkg, oracle, monkeypatch, scene)
+    try:
+        rend.set_sort_path(1)
+        img, _ = rend.render_host(u)
+        st = rend.stats()
+        print(f"{scene.name}: {scene.pins}; sort_path {st.sort_path}, retries {st.retries}, V {st.num_visible}")
+        assert (st.sort_path, st.retries, st.num_visible, st.num_gaussians) == (1, 0, scene.expect["visible"], n)
+        vis = np.nonzero(ref["tiles"])[0]
+        bits = ref["attr"]["depth"][vis].view(np.uint32)
+        want = vis[np.lexsort((vis, bits))].astype(np.uint32)
+        np.testing.assert_array_equal(want, expected_depth_order(ref["attr"], ref["tiles"]))
+        got = rend.stage("depth_order")
+        bad = np.nonzero(got != want)[0] if len(got) == len(want) else None
+        assert bad is not None and len(bad) == 0, (f"{scene.name}: the depth order has {len(got)} entries for {len(want)}" if bad is None else
+                                                  f"{scene.name}: the depth order differs at {len(bad)} places, first {bad[:4]}")
+        compare_stages(pkg, rend, u, ref)
+        assert_images_identical(img, ref["image"], label=scene.name)
+    finally:
+        rend.close()
+        gs.close()

@@ -1,11 +1,23 @@
 """The builders of tests/limit_scenes.py stand where they say: every pinned quantity, recomputed from the oracle's stages (tile
 boxes, depth bits, ranges) and the bin geometry of gs_depth_policy.h, equals what the builder promises -- exactly, with no GPU.
-This is what keeps tests/test_gpu_limits.py from passing while no longer on its edge."""
+This is what keeps tests/test_gpu_limits.py from passing while no longer on its edge.
+
+Also here, because the wave patterns in spatial order rest on it: the spatial read order of gs_host_math.h's spatial_order (driven through
+tests/native/spatial_order_sim.cpp) against its numpy restatement limit_scenes.morton_order, exactly."""
+import ctypes as C
+import os
+import subprocess
+
 import numpy as np
 import pytest
 
+import float64_check as chk
 import limit_scenes as ls
+from float64_cases import Frame
 from helpers import oracle_frame
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "3dgs.cpp_amd", "csrc")
 
 LEVEL2_COUNTS = [lim + d for lim in ls.LEVEL_LIMITS for d in (-1, 0, 1)]
 
@@ -170,3 +182,177 @@ def test_guard_pairs(oracle, kept):
     assert got["tile_lists"] == {(1, 1): kept} and sc.guard["want"] == ("clean" if kept <= 4096 else "redo")
     # a pixel two or more away from the splats never blends anything: it is what keeps the quadrant walking to the list's end
     assert not ref["image"][24, 24, :3].any() and ref["image"][27, 27, :3].any()
+
+
+# ------------------------------------------------------------------------------------------------ the spatial read order
+@pytest.fixture(scope="module")
+def spatial_sim(tmp_path_factory):
+    out = str(tmp_path_factory.mktemp("spatial") / "libspatial_order_sim.so")
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-Werror", "-shared", "-fPIC", "-I", CSRC,
+                           os.path.join(ROOT, "tests", "native", "spatial_order_sim.cpp"), "-o", out])
+    lib = C.CDLL(out)
+    fp = C.POINTER(C.c_float)
+    lib.so_order.argtypes = [fp, fp, fp, C.c_uint64, C.POINTER(C.c_uint32)]
+    lib.so_order.restype = None
+    lib.so_spread21.argtypes = [C.c_uint64]
+    lib.so_spread21.restype = C.c_uint64
+
+    def order(pos):
+        planes = [np.ascontiguousarray(pos[:, k], np.float32) for k in range(3)]
+        out = np.zeros(len(pos), np.uint32)
+        lib.so_order(*[p.ctypes.data_as(fp) for p in planes], len(pos), out.ctypes.data_as(C.POINTER(C.c_uint32)))
+        return out
+    order.spread21 = lib.so_spread21
+    return order
+
+
+def _spatial_cases():
+    rng = np.random.default_rng(7)
+    n = 5000
+    rnd = rng.normal(0.0, 3.0, (n, 3)).astype(np.float32)
+    dup = rnd.copy()
+    dup[n // 2:] = dup[:n - n // 2]                              # every position twice: the code ties, the id decides
+    dup[::7] = dup[0]                                            # ... and one of them hundreds of times
+    flat = rnd.copy()
+    flat[:, 1] = np.float32(-2.5)                                # hi = lo + 1 on y
+    far = rnd.copy()
+    far[:, 2] = np.float32(3e9)                                  # lo + 1 == lo in binary32: 0 / 0 on z, cell 0
+    odd = rnd.copy()
+    odd[5::11, 0] = np.nan
+    odd[3::13, 1] = np.inf
+    odd[2::17, 2] = -np.inf
+    odd[100] = (np.nan, np.inf, -np.inf)
+    none = np.full((40, 3), np.nan, np.float32)                  # no finite coordinate at all: every code 0, id order
+    coarse = (rng.integers(0, 4, (n, 3)) * 0.25).astype(np.float32)   # 64 distinct positions, on cell borders
+    return dict(random=rnd, duplicates=dup, constant_axis=flat, constant_axis_far=far, non_finite=odd, nothing_finite=none,
+                cell_borders=coarse, one=rnd[:1], two=rnd[:2], empty=rnd[:0])
+
+
+@pytest.mark.parametrize("name", list(_spatial_cases()))
+def test_spatial_order_header_against_numpy(spatial_sim, name):
+    pos = _spatial_cases()[name]
+    got, want = spatial_sim(pos), ls.morton_order(pos)
+    np.testing.assert_array_equal(got, want)
+    assert np.array_equal(np.sort(got), np.arange(len(pos)))
+    if name == "nothing_finite":
+        assert np.array_equal(got, np.arange(len(pos)))
+    if name == "duplicates":
+        rank = np.argsort(got)                                   # ties go by id: of two Gaussians in one place the lower id is read first
+        half = len(pos) // 2
+        same = (pos[:half] == pos[half:2 * half]).all(axis=1)
+        assert same.sum() > 1000 and (rank[:half][same] < rank[half:2 * half][same]).all()
+        crowd = np.arange(0, len(pos), 7)
+        assert (np.diff(rank[crowd]) > 0).all()                  # the hundreds in one place: in id order
+
+
+def test_spatial_order_bit_layout(spatial_sim):
+    """x is the lowest bit of each triple: bit b of a cell lands on bit 3 b of the spread value; 21 bits, no more."""
+    for b in range(21):
+        assert spatial_sim.spread21(1 << b) == 1 << (3 * b)
+    assert spatial_sim.spread21(1 << 21) == 0 and spatial_sim.spread21((1 << 21) - 1) == sum(1 << (3 * b) for b in range(21))
+    # two points that differ in x alone, in y alone, in z alone, from a common corner: x moves the order least
+    pos = np.array([[0, 0, 0], [0, 0, 1], [0, 1, 0], [1, 0, 0], [1, 1, 1]], np.float32)
+    np.testing.assert_array_equal(spatial_sim(pos), [0, 3, 2, 1, 4])
+    np.testing.assert_array_equal(ls.morton_order(pos), [0, 3, 2, 1, 4])
+
+
+# ------------------------------------------------------------------------------------------------ preprocess, wave by wave
+@pytest.mark.parametrize("tail", ls.WAVE_TAILS)
+@pytest.mark.parametrize("order", ["index", "spatial"])
+def test_wave_patterns(oracle, spatial_sim, order, tail):
+    sc = ls.wave_patterns(order, tail)
+    got, ref = _check(oracle, sc)
+    masks = got["wave_masks"]
+    counts = [bin(m).count("1") for m in masks]
+    print(f"{sc.name}: N {got['n']}, V {got['visible']}, visible lanes per wave in read order {counts}")
+    assert set(ls.WAVE_COUNTS) <= set(counts[:63]) and len(masks) == (64 if tail == "ends_group" else 65)
+    assert masks.count(1) == 1 and masks.count(1 << 63) == 1    # "only lane 0", "only lane 63"
+    assert got["ragged_lanes"] == ls.WAVE_RAGGED and got["waves_after_the_ragged_one"] == (0 if tail == "ends_group" else 3)
+    last = masks[-1]
+    assert last >> ls.WAVE_RAGGED == 0 and ((last & 1, last >> (ls.WAVE_RAGGED - 1)) == ((1, 1) if order == "index" else (1, 0)))
+    # the order the kernels read in is the header's, and in spatial order it is the scramble the builder set out to get
+    read = ls.read_order(sc)
+    if order == "spatial":
+        np.testing.assert_array_equal(spatial_sim(sc.records[:, :3]), read)
+        n = len(read)
+        np.testing.assert_array_equal(read, (np.arange(n, dtype=np.int64) * ls.PRIME + 12345) % n)
+    # the float64 reference sees the same Gaussians, and the oracle's taps are its frame within float64_check's bounds
+    fr = Frame(sc.name, sc.records, fov=ls.FOV, width=sc.width, height=sc.height)
+    np.testing.assert_array_equal(chk.reference(fr)["pre"]["tiles"] > 0, ref["tiles"] != 0)
+    out = dict(chk.outputs_from_oracle(oracle, ref), image=None)
+    rep = chk.assert_matches_float64(out, fr)
+    assert (rep["radius_explained"], rep["box_explained"], rep["visibility_explained"]) == (0, 0, 0)
+    # SH rest coefficients that matter: the colour differs from the DC term's alone
+    vis = ref["tiles"] != 0
+    assert np.abs(ref["attr"]["color_radii"][vis, :3] - (0.28209479177387814 * sc.records[vis, 6:9] + 0.5)).max() > 0.5
+
+
+def test_wave_patterns_notice_a_shifted_mask(oracle):
+    """The re-measurement is sensitive: the same Gaussians one read slot later (index order), or two ids exchanged between a
+    visible and a culled slot (spatial order), and the pinned masks no longer hold."""
+    sc = ls.wave_patterns("index")
+    sc.records = np.roll(sc.records, 1, axis=0)
+    with pytest.raises(AssertionError, match="wave_masks"):
+        _check(oracle, sc)
+    sc = ls.wave_patterns("spatial")
+    read = ls.read_order(sc)
+    vis_slot = 64 * 2 + 0                                        # wave 2 is (count 4, lowest): its lane 0 is visible, lane 5 is not
+    a, b = read[vis_slot], read[vis_slot + 5]
+    x = sc.records[[a, b], 0].copy()
+    sc.records[[a, b]] = sc.records[[b, a]]
+    sc.records[[a, b], 0] = x                                    # (x stays with the id, so the read order stays)
+    np.testing.assert_array_equal(ls.read_order(sc), read)
+    with pytest.raises(AssertionError, match="wave_masks"):
+        _check(oracle, sc)
+
+
+def test_dense_lists_full(oracle):
+    sc = ls.dense_lists_full()
+    got, _ = _check(oracle, sc)
+    assert got["list_fill"] == dict(lists=256, slots=1024, fewest=1024, most=1024) and got["n"] == got["visible"] == 262144
+    # one workgroup fewer and the last list is a quarter short; one more and the lists grow by a whole level-1 block
+    assert ls.vis_region_slots(262144 - 256) == 1024 and ls.vis_region_slots(262144 + 1) == 2048
+    p = ls.predict(sc)
+    assert (p["sort_level"], p["retries"]) == (0, 0)
+
+
+# ------------------------------------------------------------------------------------------------ the global path's grid
+RADIX_CASES = [(n, None) for n in ls.RADIX_SIZES] + [(ls.RADIX_SIZES[1], v) for v in ls.RADIX_SMALL_V]
+
+
+@pytest.mark.parametrize("n,v", RADIX_CASES)
+def test_radix_blocks(oracle, n, v):
+    sc = ls.radix_blocks(n, v)
+    got, ref = _check(oracle, sc)
+    r = got["radix"]
+    print(f"{sc.name}: N {got['n']}, V {got['visible']}, {r}")
+    assert (r["blocks"], r["per"]) == {524288: (256, 1), 524289: (257, 2), 1048577: (513, 3), 1572865: (769, 4),
+                                       2097152: (1024, 4), 2097153: (1024, 4)}[n]
+    assert r["blocks_owning_two_tiles"] == (1 if n == 2097153 else 0)
+    if v is None:
+        assert 10000 < got["visible"] < 50000 and (n != 2097153 or r["carry_shares_a_digit"] == [True] * 4)
+        ids = np.nonzero(ref["tiles"])[0]
+        whole = np.bincount(ids // ls.SORT_TILE, minlength=-(-n // ls.SORT_TILE))
+        full = [t for t in ls._radix_whole_tiles(n)]
+        assert all(whole[t] == min(ls.SORT_TILE, n - t * ls.SORT_TILE) for t in full) and whole.min() >= 1
+    else:
+        assert got["visible"] == v and r["tiles_of_the_later_passes"] == -(-v // 2048)
+    # in the passes after the first (V keys, the grid still sized by N) at most one tile per block, and most blocks none
+    t0, t1 = ls.radix_tiles_of_block(got["visible"], r["blocks"])
+    assert (t1 - t0).max() == 1 and (t1 - t0 == 0).sum() == r["blocks"] - r["tiles_of_the_later_passes"] > r["blocks"] // 2
+
+
+def test_radix_blocks_notice_a_perturbed_grid(oracle, monkeypatch):
+    """The re-measurement is sensitive: one Gaussian fewer and no block owns two tiles; a grid restated with 1023 blocks, or
+    tiles of 2047 keys, and the pinned numbers no longer hold."""
+    sc = ls.radix_blocks(2097153)
+    short = ls.LimitScene(sc.name, sc.records[:-1], sc.width, sc.height, sc.env, sc.pins, sc.expect)
+    with pytest.raises(AssertionError, match="the builder promises"):
+        _check(oracle, short)
+    sc = ls.radix_blocks(524289, 2048)
+    for name, value in (("SORT_MAX_BLOCKS", 256), ("SORT_TILE", 2047), ("SCAN_THREADS", 128)):
+        with monkeypatch.context() as mp:
+            mp.setattr(ls, name, value)
+            with pytest.raises(AssertionError, match="radix"):
+                _check(oracle, sc)
+    _check(oracle, sc)
