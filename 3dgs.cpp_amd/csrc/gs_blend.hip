@@ -48,7 +48,8 @@ namespace gs {
 // min over the pixel rectangle [xa,xb] x [ya,yb] of q(d) = 0.5 (c00 dx^2 + c11 dy^2) + c01 dx dy,
 // d = uv - pixel.  q is convex with its minimum 0 at d = 0: inside the rectangle the answer is 0,
 // otherwise the minimum lies on an edge facing the centre, where q is a 1-D parabola.
-__device__ __forceinline__ float min_q_rect(float c00, float c01, float c11, float u, float v, float xa,
+// h00 = c00 / 2, h11 = c11 / 2; r11 = -c01 rcp(c11), r00 = -c01 rcp(c00): the entry's own terms, carried in its record.
+__device__ __forceinline__ float min_q_rect(float h00, float c01, float h11, float r11, float r00, float u, float v, float xa,
                                             float xb, float ya, float yb) {
     const float dx_lo = u - xb, dx_hi = u - xa, dy_lo = v - yb, dy_hi = v - ya;
     const bool in_x = !(dx_lo > 0.0f) && !(dx_hi < 0.0f), in_y = !(dy_lo > 0.0f) && !(dy_hi < 0.0f);  // NaN -> inside
@@ -57,8 +58,6 @@ __device__ __forceinline__ float min_q_rect(float c00, float c01, float c11, flo
     // (a segment from the centre to a point of a far edge crosses a near edge, where the convex q is smaller): at most
     // one vertical and one horizontal edge; on an edge one coordinate is fixed and the other is the parabola's
     // minimiser r * fixed, clamped to the edge.
-    const float h00 = 0.5f * c00, h11 = 0.5f * c11;
-    const float r11 = -c01 * __builtin_amdgcn_rcpf(c11), r00 = -c01 * __builtin_amdgcn_rcpf(c00);
     const float a = dx_lo > 0.0f ? dx_lo : dx_hi;  // the vertical edge nearer to the centre: dx fixed, parabola in dy
     const float t = fminf(fmaxf(r11 * a, dy_lo), dy_hi);
     const float qv = __builtin_fmaf(t, __builtin_fmaf(h11, t, c01 * a), h00 * a * a);
@@ -66,7 +65,8 @@ __device__ __forceinline__ float min_q_rect(float c00, float c01, float c11, flo
     const float s = fminf(fmaxf(r00 * b, dx_lo), dx_hi);
     const float qh = __builtin_fmaf(s, __builtin_fmaf(h00, s, c01 * b), h11 * b * b);
     // The cull `mq > lim` needs mq to be a LOWER bound of q over the quadrant, and evaluating the parabola at an inexact
-    // minimiser (v_rcp_f32: 1 ULP) OVER-estimates its minimum -- by a second-order amount: q(t* + dt) - q(t*) = h dt^2 with
+    // minimiser (r11, r00 are v_rcp_f32's, 1 ULP, evaluated once per Gaussian in k_preprocess instead of once per wave and entry
+    // here) OVER-estimates its minimum -- by a second-order amount: q(t* + dt) - q(t*) = h dt^2 with
     // dt/t* ~ 2^-23, i.e. ~1e-14 relative, which the caller's slack (9.6e-7 x the quadratic's largest terms) absorbs
     // many times over.  A coarser reciprocal or a smaller slack must revisit this.
     return in_x ? (in_y ? 0.0f : qh) : (in_y ? qv : fminf(qv, qh));
@@ -90,15 +90,14 @@ __device__ uint2 g_blend_clock[kClockSlots];
 struct BlendEntry {
     float4 co;  // c00 c01 c11 opacity
     float4 uv;  // u v r g
-    float2 bc;  // b, alpha cut
+    float4 bc;  // b, alpha cut, r11, r00 (min_q_rect)
 };
 
 __device__ __forceinline__ void blend_fetch(BlendEntry& e, uint32_t g, const AttrRecord* __restrict__ rec) {
     const AttrRecord* r = rec + g;  // one 64-byte line
     e.co = r->conic_op;
     e.uv = r->uv_rg;
-    const float4 t = r->b_depth_r;
-    e.bc = make_float2(t.x, t.w);
+    e.bc = r->b_cut_r;
 }
 
 // ---- the guard of render.comp:82-85 for a fast exp (GUARD) ---------------------------------------------------------
@@ -162,7 +161,7 @@ __device__ __forceinline__ bool resolve_break(const uint32_t* __restrict__ klist
             const AttrRecord* r = rec + klist[p];
             co = r->conic_op;
             uv = make_float2(r->uv_rg.x, r->uv_rg.y);
-            cut = r->b_depth_r.w;
+            cut = r->b_cut_r.y;
         }
         const float dx = uv.x - fxa, dy = uv.y - fya;
         const float cx = -0.5f * co.x, cy = -co.y, cz = -0.5f * co.z;
@@ -392,8 +391,8 @@ __device__ __forceinline__ void blend_pair_loop_exact(uint32_t slab_addr, const 
         : "vcc", "scc", "memory", "v52", "v53", "v54", "v55", "v56", "v57", "v58", "v59", "v60", "v61", "v62", "v63");
 }
 
-// One pass of a wave over its tile's list: returns false if the quadrant has to be re-rendered exactly (GUARD only; c0..c2
-// are then meaningless).  slab: this wave's three planes of 64 float4 {c00' c01' c11' o} {u v r g} {b, cut, -, -} --
+// One pass of a wave over its tile's list (rx0 .. rx1, ry0 .. ry1: the quadrant's pixel rectangle): returns false if the quadrant
+// has to be re-rendered exactly (GUARD only; c0..c2 are then meaningless).  slab: this wave's three planes of 64 float4 {c00' c01' c11' o} {u v r g} {b, cut, -, -} --
 // plane-major keeps the staging ds_write_b128 conflict-free (lane stride 16 B); one scalar-derived address + constant offsets
 // serve the broadcast reads.  resolved: GUARD, how many break decisions resolve_break took.
 // EXP: 0 the pipeline-defined polynomial (gs_exp_blend), 1 the hardware's v_exp_f32, 2 libm's expf restated (gs_expf_libm).
@@ -401,7 +400,7 @@ template <int EXP, bool CONTRACT, bool GUARD>
 __device__ __forceinline__ bool blend_walk(const uint2 range, const uint32_t* __restrict__ sorted_gid,
                                            const AttrRecord* __restrict__ rec, float4 (*__restrict__ slab)[WAVE],
                                            uint2* __restrict__ exptab_rw, uint32_t* __restrict__ klist, const int lane, const float fx, const float fy,
-                                           const float rx0, const float ry0, uint64_t alive, float& c0, float& c1, float& c2,
+                                           const float rx0, const float rx1, const float ry0, const float ry1, uint64_t alive, float& c0, float& c1, float& c2,
                                            uint32_t& resolved, bool& table_ready, const bool lockstep) {
     const uint2* __restrict__ exptab = exptab_rw;
     // the guarded mode and the exact one walk the pairs in the hand-written loops above; the other five combinations in the compiler's
@@ -422,7 +421,7 @@ __device__ __forceinline__ bool blend_walk(const uint2 range, const uint32_t* __
     BlendEntry nxt;
     nxt.co = make_float4(0, 0, 0, 0);
     nxt.uv = make_float4(0, 0, 0, 0);
-    nxt.bc = make_float2(0, 0);
+    nxt.bc = make_float4(0, 0, 0, 0);
     uint32_t g_next = 0, g_nxt = 0;  // ids of chunk +2 (in flight); GUARD: the ids `nxt` was fetched through
     {
         const uint32_t i0 = range.x + lane;
@@ -454,20 +453,23 @@ __device__ __forceinline__ bool blend_walk(const uint2 range, const uint32_t* __
         // classify entry `lane` of this chunk against the wave's quadrant.  cut = +inf: no power <= 0 is kept (never
         // enters); -inf (NaN or infinite opacity: min(0.99, NaN) is 0.99 in the pipeline's definition): never culled
         const float cut = cur.bc.y;
-        bool keep = have && cut <= 0.0f;
-        if (keep) {
-            const float mq = min_q_rect(cur.co.x, cur.co.y, cur.co.z, cur.uv.x, cur.uv.y, rx0, rx0 + 7.0f, ry0, ry0 + 7.0f);
+        // (the conic scaled by a power of two: exact, and |c / 2| = |c| / 2 bit for bit -- the quadrant test, its slack and the
+        //  staged record share the two products)
+        const float h00 = 0.5f * cur.co.x, h11 = 0.5f * cur.co.z;
+        uint64_t bm = __builtin_amdgcn_ballot_w64(have) & __builtin_amdgcn_ballot_w64(cut <= 0.0f);
+        {   // (every lane: the wave pays for these instructions as soon as one lane needs them, and the AND of two scalar masks
+            //  needs no branch and no rebuilding from a VGPR; what a lane without an entry computes is never looked at)
+            const float mq = min_q_rect(h00, cur.co.y, h11, cur.bc.z, cur.bc.w, cur.uv.x, cur.uv.y, rx0, rx1, ry0, ry1);
             // The rounding error of the shader's `power` (and of mq) is relative to the TERMS c00 dx^2, c11 dy^2,
             // c01 dx dy, not to their sum: a thin diagonal splat far from its centre has terms ~1e5 cancelling to
             // q ~ 5.  The slack therefore grows with the terms at the quadrant's corner farthest from the centre
             // (16 roundings of 2^-24 each, generously).
-            const float ax = fmaxf(fabsf(cur.uv.x - rx0), fabsf(cur.uv.x - (rx0 + 7.0f)));
-            const float ay = fmaxf(fabsf(cur.uv.y - ry0), fabsf(cur.uv.y - (ry0 + 7.0f)));
-            const float mag = __builtin_fmaf(0.5f * fabsf(cur.co.x) * ax, ax,
-                                             __builtin_fmaf(0.5f * fabsf(cur.co.z) * ay, ay, fabsf(cur.co.y) * ax * ay));
-            keep = !(mq > __builtin_fmaf(mag, 9.6e-7f, -cut));  // NaN -> keep
+            const float ax = fmaxf(fabsf(cur.uv.x - rx0), fabsf(cur.uv.x - rx1));
+            const float ay = fmaxf(fabsf(cur.uv.y - ry0), fabsf(cur.uv.y - ry1));
+            const float mag = __builtin_fmaf(fabsf(h00) * ax, ax, __builtin_fmaf(fabsf(h11) * ay, ay, fabsf(cur.co.y) * ax * ay));
+            bm &= __builtin_amdgcn_ballot_w64(!(mq > __builtin_fmaf(mag, 9.6e-7f, -cut)));  // NaN -> keep
         }
-        uint64_t bm = __ballot(keep);
+        const bool keep = __builtin_amdgcn_inverse_ballot_w64(bm);  // (the scalar mask as the lanes' predicate, as it is)
         STAT_ADD(0, 1);
         STAT_ADD(6, __popcll(__ballot(have)));
         STAT_ADD(1, __popcll(bm));
@@ -491,11 +493,18 @@ __device__ __forceinline__ bool blend_walk(const uint2 range, const uint32_t* __
         if constexpr (kAsmLoop || kAsmLoopExact) {
             // the kept entries staged in rank order
             if (keep) {  // (the conic scaled by a power of two, signs as they are: the loops compute pn = -power; ncut = -cut)
-                slab[0][rank] = make_float4(0.5f * cur.co.x, cur.co.y, 0.5f * cur.co.z, cur.co.w);
+                slab[0][rank] = make_float4(h00, cur.co.y, h11, cur.co.w);
                 slab[1][rank] = cur.uv;
-                slab[2][rank] = make_float4(cur.bc.x, -cut, 0.0f, 0.0f);
+                *reinterpret_cast<float2*>(&slab[2][rank]) = make_float2(cur.bc.x, -cut);  // (the loops read these two alone)
             }
             __builtin_amdgcn_wave_barrier();
+        } else {
+            // conic pre-scaled once per entry: (-c00/2, -c01, -c11/2).  Scaling by a power of two commutes with every
+            // rounding below, so power is bit-identical to render.comp:66 evaluated as written while the per-pixel body
+            // loses the -0.5 multiply
+            slab[0][lane] = make_float4(-h00, -cur.co.y, -h11, cur.co.w);
+            slab[1][lane] = cur.uv;
+            slab[2][lane] = make_float4(cur.bc.x, cut, 0.0f, 0.0f);
         }
         if constexpr (kAsmLoop) {
             const uint32_t n_kept = (uint32_t)__popcll(bm0);
@@ -515,9 +524,11 @@ __device__ __forceinline__ bool blend_walk(const uint2 range, const uint32_t* __
                 }
                 if (amb != 0) {  // ask the reference
                     if (!table_ready) {  // the wave's copy of libm's table, on first use
-                        if (lane < 32) {
-                            const uint64_t v = kExpfTab[lane];
-                            exptab_rw[lane] = make_uint2((uint32_t)v, (uint32_t)(v >> 32));
+                        int l = lane;
+                        asm volatile("" : "+v"(l));  // (cold: keeps the table's per-lane address from being formed, and held, ahead of the chunk loop)
+                        if (l < 32) {
+                            const uint64_t v = kExpfTab[l];
+                            exptab_rw[l] = make_uint2((uint32_t)v, (uint32_t)(v >> 32));
                         }
                         __builtin_amdgcn_wave_barrier();
                         table_ready = true;
@@ -561,13 +572,6 @@ __device__ __forceinline__ bool blend_walk(const uint2 range, const uint32_t* __
         } else if constexpr (kAsmLoopExact) {
             blend_pair_loop_exact((uint32_t)(uintptr_t)&slab[0][0], (uint32_t)__popcll(bm0) - 1u, alive, fx, fy, T, c0, c1, c2, exptab);
         } else {
-        // conic pre-scaled once per entry: (-c00/2, -c01, -c11/2).  Scaling by a power of two commutes with every
-        // rounding below, so power is bit-identical to render.comp:66 evaluated as written while the per-pixel body
-        // loses the -0.5 multiply
-        slab[0][lane] = make_float4(-0.5f * cur.co.x, -cur.co.y, -0.5f * cur.co.z, cur.co.w);
-        slab[1][lane] = cur.uv;
-        slab[2][lane] = make_float4(cur.bc.x, cut, 0.0f, 0.0f);
-
         while (bm) {
             const int k = __ffsll((unsigned long long)bm) - 1;
             asm("s_bitset0_b64 %0, %1" : "+s"(bm) : "s"(k));  // bm &= bm - 1 costs three scalar instructions
@@ -660,11 +664,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
     const unsigned long long stat_w0 = wall_clock64();   // s_memrealtime: the constant-rate clock
 #endif
     static_assert(!GUARD || (EXP != 2 && !CONTRACT), "the guard belongs to a fast exp on the uncontracted arithmetic");
-    if (fp) {  // graph replay: this frame's targets come from the parameter block
-        rgba = reinterpret_cast<float4*>(fp->rgba);
-        bgra = reinterpret_cast<uchar4*>(fp->bgra);
-        host_counters = fp->host_counters;
-    }
+    if (fp) host_counters = fp->host_counters;  // graph replay: this frame's targets come from the parameter block (the images: at the stores)
     // wave-private slabs (no cross-wave sharing; the only workgroup barrier is the lockstep one at the top of blend_walk's chunk loop)
     __shared__ float4 s_rec[4][3][WAVE];
     __shared__ uint2 s_exptab[(EXP == 2 || GUARD) ? 4 : 1][32];  // wave-private copies of kExpfTab: filled and read by their own wave, wave_barrier only
@@ -694,7 +694,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
     const uint32_t px = qx0 + (lane & 7), py = qy0 + (lane >> 3);
     const bool inside = px < width && py < height;  // render.comp:36-39
     const float fx = (float)px, fy = (float)py;
-    const float rx0 = (float)qx0, ry0 = (float)qy0;
+    const float rx0 = (float)qx0, ry0 = (float)qy0, rx1 = (float)qx0 + 7.0f, ry1 = (float)qy0 + 7.0f;
 
     const uint2 range = ranges[tile];
     float c0 = 0.0f, c1 = 0.0f, c2 = 0.0f;
@@ -706,7 +706,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
         uint32_t resolved = 0, unused;
         bool table_ready = EXP == 2;  // GUARD: the wave copies libm's table into LDS when it first needs it
         const bool done = blend_walk<EXP, CONTRACT, GUARD>(range, sorted_gid, rec, s_rec[w], s_exptab[(EXP == 2 || GUARD) ? w : 0],
-                                                           s_klist[GUARD ? w : 0], lane, fx, fy, rx0, ry0, alive, c0, c1, c2, resolved,
+                                                           s_klist[GUARD ? w : 0], lane, fx, fy, rx0, rx1, ry0, ry1, alive, c0, c1, c2, resolved,
                                                            table_ready, lockstep != 0);
         if (GUARD && resolved != 0 && lane == 0) atomicAdd(&counters->blend_resolved, resolved);
         if (GUARD && !done) {  // wave-uniform: the whole quadrant again, with the reference's arithmetic
@@ -721,8 +721,12 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
             if (lane == 0) atomicAdd(&counters->blend_redo, 1u);
             // (alone: the other waves of the tile are in their own walks, or done.  lockstep = false HERE, always: this wave has left the
             // lockstepped loop, its siblings may still be in it -- a barrier in this walk would deadlock the tile)
-            (void)blend_walk<2, false, false>(range, sorted_gid, rec, s_rec[w], s_exptab[w], nullptr, lane, fx, fy, rx0, ry0, alive, c0, c1, c2,
-                                              unused, table_ready, false);
+            // (cold: the range laundered, so that nothing of this walk's prologue -- the same expressions as the fast walk's -- is computed
+            //  once ahead of the fast walk and kept in registers across it)
+            uint2 range_again = range;
+            asm volatile("" : "+s"(range_again.x), "+s"(range_again.y));
+            (void)blend_walk<2, false, false>(range_again, sorted_gid, rec, s_rec[w], s_exptab[w], nullptr, lane, fx, fy, rx0, rx1, ry0, ry1, alive, c0, c1,
+                                              c2, unused, table_ready, false);
         }
     }
 #if defined(GS_BLEND_STATS) || defined(GS_BLEND_CLOCK)
@@ -733,8 +737,17 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
     }
 #endif
     // (no __syncthreads / s_barrier from here to the end: see the header)
-    if (inside) {
-        const size_t p = (size_t)py * width + px;
+    // What the stores need is formed HERE, not carried across the walk (whose loop owns every register the kernel has): the targets, and
+    // the pixel from its coordinates as floats, which the walk keeps anyway (integers below 2^24: the conversion back is exact).
+    if (fp) {
+        rgba = reinterpret_cast<float4*>(fp->rgba);
+        bgra = reinterpret_cast<uchar4*>(fp->bgra);
+    }
+    float fx_end = fx, fy_end = fy;
+    asm volatile("" : "+v"(fx_end), "+v"(fy_end));
+    const uint32_t px_end = (uint32_t)fx_end, py_end = (uint32_t)fy_end;
+    if (px_end < width && py_end < height) {  // render.comp:36-39
+        const size_t p = (size_t)py_end * width + px_end;
         if (rgba) rgba[p] = make_float4(c0, c1, c2, 1.0f);  // :98
         if (bgra) {
             // imageStore to B8G8R8A8_UNORM: clamp to [0,1], round to nearest

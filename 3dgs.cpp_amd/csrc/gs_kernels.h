@@ -34,7 +34,7 @@ struct SceneView {
 };
 
 // Per-frame buffers indexed by Gaussian id.
-// What the blend gathers per list entry -- conic + opacity, uv + r g, b: 36 bytes -- lives in ONE 64-byte, 64-byte
+// What the blend gathers per list entry -- conic + opacity, uv + r g, b + alpha cut + r11 r00: 48 bytes -- lives in ONE 64-byte, 64-byte
 // aligned record per Gaussian, so that an entry costs the memory system one line instead of three (three separate
 // arrays measured 10 % slower in the blend and 9 % in the frame rate: the gathers are request-bound, not byte-bound).
 // The record is the reference's VertexAttribute (common.glsl:42-49) in spirit; what the binning kernels stream or
@@ -42,8 +42,11 @@ struct SceneView {
 struct AttrRecord {
     float4 conic_op;   // c00 c01 c11 opacity
     float4 uv_rg;      // u v r g
-    float4 b_depth_r;  // b, depth, radius, alpha cut (the most negative `power` at which render.comp:78 keeps the entry)
-    uint4 pad_;        // zeros (k_preprocess writes a record as one full 64-byte line); the blend never reads it
+    // b, alpha cut (the most negative `power` at which render.comp:78 keeps the entry), and the two entry-only terms of the
+    // blend's quadrant test: r11 = -c01 rcp(c11), r00 = -c01 rcp(c00) (gs_blend.hip, min_q_rect), evaluated once per Gaussian
+    // here instead of once per (wave, entry) there
+    float4 b_cut_r;
+    float4 depth_radius;  // depth, radius, 0, 0: read by the stage taps only (k_preprocess writes a record as one full 64-byte line)
 };
 static_assert(sizeof(AttrRecord) == 64, "one line per Gaussian");
 

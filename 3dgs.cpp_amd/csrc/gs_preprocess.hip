@@ -25,10 +25,10 @@ struct PreUniforms {
     uint64_t* stamps;        // nullable: the frame's timeline
 };
 
-// Wave-private LDS of k_preprocess: the attribute records of a wave's 64 Gaussians on their way to HBM, three planes of
+// Wave-private LDS of k_preprocess: the attribute records of a wave's 64 Gaussians on their way to HBM, four planes of
 // 64 float4 with a plane stride of 68 (272 dwords = 16 mod 64: the cooperative reads of 16 consecutive lanes cover all
 // 64 banks once).
-constexpr int kPrePlane = 68, kPreStage = 3 * kPrePlane + 16;  // + 64 scene ids (spatial order: where the records go)
+constexpr int kPrePlane = 68, kPreStage = 4 * kPrePlane + 16;  // + 64 scene ids (spatial order: where the records go)
 // ... and, ahead of that (the two uses alias: the SH blocks are consumed before the records are staged), the SH blocks of up
 // to 32 of the wave's visible Gaussians, fetched by LDS-DMA: 32 x 192 B = 384 float4 (+ 64 source-lane bytes)
 constexpr int kPreShHalf = 32;
@@ -304,7 +304,7 @@ __device__ __forceinline__ void preprocess_one(const SceneView& sv, const gs_uni
     if (valid && !av.vis) av.tiles[oid] = num_tiles;
 
     // ---- the 64-byte-strided record of every visible Gaussian.  Wave-cooperative: the records pass through LDS and four
-    // lanes write one record -- ONE 64-byte request per visible Gaussian (the last quarter as zeros) instead of three
+    // lanes write one record -- ONE 64-byte request per visible Gaussian (the last quarter: depth and radius, for the taps) instead of three
     // 16-byte ones from its own lane: k_preprocess 39 -> 37 us (without any record store it takes 30).
     const uint64_t vm = __ballot(vis);
     if (av.vis) {  // 16 bytes per visible Gaussian, the wave's entries back to back
@@ -316,9 +316,13 @@ __device__ __forceinline__ void preprocess_one(const SceneView& sv, const gs_uni
     if (vis) {
         stage[0 * kPrePlane + lane] = make_float4(c00, c01, c11, opacity);
         stage[1 * kPrePlane + lane] = make_float4(uvx, uvy, rgb[0], rgb[1]);
-        stage[2 * kPrePlane + lane] = make_float4(rgb[2], depth, radii, acut);
+        // the blend's entry-only terms (gs_blend.hip, min_q_rect: the minimiser of q along an edge is r * the fixed coordinate), with
+        // the very operations the blend used to spend on them per (wave, entry): v_rcp_f32, then the product with -c01
+        const float r11 = -c01 * __builtin_amdgcn_rcpf(c11), r00 = -c01 * __builtin_amdgcn_rcpf(c00);
+        stage[2 * kPrePlane + lane] = make_float4(rgb[2], acut, r11, r00);
+        stage[3 * kPrePlane + lane] = make_float4(depth, radii, 0.0f, 0.0f);
     }
-    uint32_t* const s_oid = reinterpret_cast<uint32_t*>(stage + 3 * kPrePlane);  // [64] (behind the three planes; spatial order only)
+    uint32_t* const s_oid = reinterpret_cast<uint32_t*>(stage + 4 * kPrePlane);  // [64] (behind the four planes; spatial order only)
     if (sv.perm) s_oid[lane] = oid;
     __builtin_amdgcn_wave_barrier();
     {
@@ -327,8 +331,8 @@ __device__ __forceinline__ void preprocess_one(const SceneView& sv, const gs_uni
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
             const uint32_t r = (uint32_t)t * 16u + (lane >> 2);
-            if ((vm >> r) & 1ull) {  // the whole line: leaving the unused quarter out (three lanes per record) measured 2 us slower
-                const float4 val = c < 3u ? stage[c * kPrePlane + r] : make_float4(0, 0, 0, 0);
+            if ((vm >> r) & 1ull) {  // the whole line: leaving the last quarter out (three lanes per record) measured 2 us slower
+                const float4 val = stage[c * kPrePlane + r];
                 float4* const dst = sv.perm ? reinterpret_cast<float4*>(av.rec + s_oid[r]) + c : rec0 + (size_t)r * 4 + c;
                 *dst = val;
             }

@@ -957,9 +957,9 @@ int gs_debug_download(gs_renderer* r, int stage, void* dst, uint64_t bytes) {
                     float* out = static_cast<float*>(dst);
                     for (uint64_t i = 0; i < n; ++i) {
                         const gs::AttrRecord& a = recs[i];
-                        if (stage == GS_STAGE_RADIUS) out[i] = a.b_depth_r.z;
-                        else if (stage == GS_STAGE_B) out[i] = a.b_depth_r.x;
-                        else if (stage == GS_STAGE_ALPHA_CUT) out[i] = a.b_depth_r.w;
+                        if (stage == GS_STAGE_RADIUS) out[i] = a.depth_radius.y;
+                        else if (stage == GS_STAGE_B) out[i] = a.b_cut_r.x;
+                        else if (stage == GS_STAGE_ALPHA_CUT) out[i] = a.b_cut_r.y;
                         else std::memcpy(out + 4 * i, stage == GS_STAGE_CONIC_OPACITY ? &a.conic_op : &a.uv_rg, 16);
                     }
                     return;
