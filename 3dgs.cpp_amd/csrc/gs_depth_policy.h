@@ -27,6 +27,7 @@ struct BinGeometry {
 // after 32 frames that would have fitted the level below, go back down.
 struct DepthPolicy {
     static constexpr int kGlobalLevel = gs::kBinSortLevels;
+    static constexpr int kOneSizeShift = 4;  // bins of 2^4 x 2^4 tiles or more: one in-LDS size (16384) at every bin-local level, no slabs
     static uint32_t level_limit(int lv) { return gs::kBinSortLimit[lv]; }
 
     int sort_mode = 0;  // 0 auto, 1 global depth order, 2 bin-local (forced: a bin beyond 16384 is an error)
@@ -108,13 +109,18 @@ struct DepthPolicy {
         if (!bin_too_big) return kRerun;
         // a bin outgrew the in-LDS order of this level: one level up from here on
         const int failed_level = frames[0].level;
-        const bool slabs_unsuitable = failed_level == gs::kBinSlabLevel && fullest <= level_limit(gs::kBinSlabLevel);
+        // bins of 16 x 16 tiles or more are ordered by one kernel at every bin-local level (k_bin_build: 16384 candidates in LDS,
+        // whatever the level) and have no slabs: a bin beyond that has nothing to climb to but smaller bins or the global path,
+        // and its failure says nothing about the slabs
+        const bool one_size = frames[0].bin_shift >= kOneSizeShift;
+        const bool slabs_unsuitable = !one_size && failed_level == gs::kBinSlabLevel && fullest <= level_limit(gs::kBinSlabLevel);
         if (slabs_unsuitable) {  // not the bin's size: equal or crowded depths (see slab_hold)
             slab_hold = std::min<uint32_t>(slab_hold * 2, 8192);
             slab_clean_frames = 0;
         }
         int wanted = failed_level + 1;
         while (wanted < kGlobalLevel && fullest > level_limit(wanted)) ++wanted;
+        if (one_size) wanted = kGlobalLevel;
         if (wanted >= gs::kBinSlabLevel && can_refine(frames[0].width, frames[0].height)) {  // smaller bins before slabs or the global path
             refined = true;
             wanted = gs::kBinSlabLevel - 1;  // (what the smaller bins hold is not known yet: the largest in-LDS order)
@@ -128,8 +134,9 @@ struct DepthPolicy {
         return kRerun;
     }
 
-    // a frame that ran at `ran_level` retired without overflow; `max_bin`: the candidates in its fullest bin
-    void frame_retired(int ran_level, uint32_t max_bin) {
+    // a frame that ran at `ran_level` with bins of 2^ran_bin_shift tiles retired without overflow; `max_bin`: the candidates in
+    // its fullest bin
+    void frame_retired(int ran_level, uint32_t max_bin, int ran_bin_shift = 3) {
         if (ran_level == gs::kBinSlabLevel && ++slab_clean_frames >= 64) slab_hold = 32;  // the slabs work on this scene (again)
         if (settle_level && sort_mode != 1 && ran_level == level && level < kGlobalLevel) {
             // the first clean frame after the bins were refined: its fullest bin says which order the smaller bins need -- straight
@@ -139,7 +146,10 @@ struct DepthPolicy {
             settle_level = false;
         }
         if (sort_mode != 1 && level > 0) {  // one level down once the bins have fitted it for a while
-            if (max_bin <= level_limit(level - 1) * 7 / 8) {
+            // (bins without slabs leave the global path only for what their one kernel holds: frames_overflowed would send a
+            // fuller bin straight back, every slab_hold frames, and no longer doubles the hold for it)
+            const bool no_slabs_below = level == kGlobalLevel && ran_bin_shift >= kOneSizeShift;
+            if (max_bin <= level_limit(no_slabs_below ? gs::kBinSlabLevel - 1 : level - 1) * 7 / 8) {
                 // (from the global path back to the slabs: only after slab_hold frames, see there)
                 if (++frames_since_fallback >= (level == kGlobalLevel ? slab_hold : 32u)) {
                     --level;

@@ -542,7 +542,7 @@ struct gs_renderer {
             return;
         }
         redo_chain = 0;
-        policy.frame_retired(sl.level, sl.h_counters->max_bin);
+        policy.frame_retired(sl.level, sl.h_counters->max_bin, sl.bin_shift);
         last = frame_stats(sl);
         have_frame = true;
         const float v[7] = {last.ms_preprocess, last.ms_prefix_sum, last.ms_preprocess_sort, last.ms_sort,

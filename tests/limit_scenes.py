@@ -2,6 +2,9 @@
   * binning and blend: the candidates a depth-order level holds, the run of equal depths the tie step orders in place, the keys a
     depth bucket holds before the stable passes take over, the slab cut, the items of a level-1 block, the bin box the whole
     wave emits, the blend's chunks of 64, the guard's list, replays and pairs;
+  * k_bin_build (bins of 16 x 16 and 32 x 32 tiles, and every bin size of the global path): its one capacity of 16384, the
+    sort rounds of 1024, a wave's run of the list, one tile that takes every candidate, boxes clipped to the bin, a bin cut
+    by the frame's edge (build_size, build_unrefinable, build_one_tile, build_boxes, equal_run with shift 4 and 5);
   * k_preprocess (wave_patterns): every count of visible lanes of a wave at which the LDS-DMA fetch of the SH blocks, the wave's
     run of slots in the dense lists or the four-lanes-per-record store changes shape, in the lowest lanes, the highest, and
     spread; every exit of a culled lane; a ragged last wave; in index order and in a spatial order that is a known scramble of
@@ -33,6 +36,8 @@ MAX_SLABS = 16                                      # kMaxSlabs
 MSD_BUCKETS, MSD_BUCKET_MAX = 4096, 64              # kMsdBuckets, kMsdBucketMax
 TIE_RUN_MAX = 65                                    # the longest run of equal depths the tie step orders in place
 THREADS = 1024                                      # of a level-2 workgroup: element e of the ordered list is round e / 1024
+BUILD_MAX = 16384                                   # gs_bin_l2.hip: MAXC of k_bin_build<R2, 1024, true>, at EVERY bin-local level
+ONE_SIZE_SHIFT = 4                                  # gs_depth_policy.h: kOneSizeShift, the bins k_bin_build orders (no slabs)
 L1_ITEMS, L1_XCD_RUN, L1_BIG_BOX = 1024, 32, 12     # gs_bin.h
 BLEND_CHUNK = 64
 WAVE, PRE_BLOCK = 64, 256                           # gs_device.h: a wave, a workgroup of k_preprocess (four waves)
@@ -102,18 +107,22 @@ def _background(shift, bins, skip, per_bin, w, h):
     recs = []
     for by in range(bins[1]):
         for bx in range(bins[0]):
-            if (bx, by) == skip:
+            if (bx, by) == skip or per_bin == 0:
                 continue
             tx, ty = _bin_tiles(per_bin, shift, bx, by)
             recs.append(_splats(_spread_bits(per_bin, DEPTH_2 + 12345 * (1 + bx + 2 * by)), tx, ty, w, h))
     return np.concatenate(recs) if recs else np.zeros((0, RECORD_FLOATS), np.float32)
 
 
-def _one_bin_scene(name, bits, shift, pins, expect, env=None, slabs_fail=False, frame_bins=2, first_tile=0):
-    """`bits` (id order) all in bin (1, 1) of a frame of frame_bins x frame_bins bins of 2^shift tiles; 200 in every other bin."""
+def _one_bin_scene(name, bits, shift, pins, expect, env=None, slabs_fail=False, frame_bins=2, first_tile=0, background=200,
+                   tile=None):
+    """`bits` (id order) all in bin (1, 1) of a frame of frame_bins x frame_bins bins of 2^shift tiles, dealt round robin over
+    its tiles (or all in `tile`); `background` (200) in every other bin."""
     w = h = 16 * (1 << shift) * frame_bins
-    bg = _background(shift, (frame_bins, frame_bins), (1, 1), 200, w, h)
+    bg = _background(shift, (frame_bins, frame_bins), (1, 1), background, w, h)
     tx, ty = _bin_tiles(len(bits), shift, 1, 1, first_tile)
+    if tile is not None:
+        tx, ty = np.full(len(bits), tile[0]), np.full(len(bits), tile[1])
     rec = np.concatenate([bg, _splats(bits, tx, ty, w, h)])
     e = dict(n=len(rec), visible=len(rec), fullest_bin={shift: len(bits)}, bin_entries={shift: len(rec)})
     e.update(expect)
@@ -143,13 +152,22 @@ def level2_size(count, shift=2):
 RUN_PLACES = ("start", "end", "straddle", "scattered")
 
 
-def equal_run(length, place, slab):
+def equal_run(length, place, slab, shift=2):
     """A bin of M distinct depths, one of which is shared by `length` Gaussians.  place: the run is the nearest of the bin
     ("start": ordered position 0), the farthest ("end"), begins 30 elements short of the ordered list's element 1024
     ("straddle": it crosses from one round of the workgroup to the next), or sits mid-bin with its ids scattered over the
-    whole id range.  slab: 20 000 candidates (depth slabs, level 4) instead of 3 000 (k_bin_fast<4>)."""
+    whole id range.  slab: 20 000 candidates (depth slabs, level 4) instead of 3 000 (k_bin_fast<4>).
+    shift 4 or 5 (k_bin_build, which has no tie step and no tie limit: its four passes are stable and its input is in id
+    order): the bin holds 3000 candidates IN ALL, the run among them, so that the workgroup takes ceil(3000 / 1024) = 3 rounds
+    and wave w owns elements 192 w .. 192 w + 191 of the list; "straddle" begins 30 elements short of element 192 -- or, a run
+    shorter than that, on element 191 -- and crosses from wave 0's elements into wave 1's."""
     m = 20000 if slab else 3000
-    rank = {"start": 0, "end": m - 1, "straddle": THREADS - 30, "scattered": m // 2 + 7}[place]
+    straddle = THREADS - 30
+    if shift >= ONE_SIZE_SHIFT:
+        assert not slab
+        m -= length - 1
+        straddle = 3 * WAVE - min(30, length - 1)
+    rank = {"start": 0, "end": m - 1, "straddle": straddle, "scattered": m // 2 + 7}[place]
     ranks = (np.arange(m, dtype=np.int64) * PRIME) % m          # a permutation: rank of id j
     at = int(np.nonzero(ranks == rank)[0][0])
     extra = length - 1
@@ -160,9 +178,123 @@ def equal_run(length, place, slab):
     ranks = np.insert(ranks, where, rank)
     bits = (DEPTH_2 + ranks * ((1 << 23) // m)).astype(np.uint32)
     fails = slab and length > TIE_RUN_MAX
-    return _one_bin_scene(f"equal_run/{length}/{place}/{'slab' if slab else 'fast'}", bits, 2,
+    return _one_bin_scene(f"equal_run/{length}/{place}/{'slab' if slab else 'fast' if shift < ONE_SIZE_SHIFT else shift}", bits, shift,
                           f"run of {length} equal depths at ordered position {rank}",
                           dict(longest_run=length, run_start=rank), slabs_fail=fails)
+
+
+# ------------------------------------------------------------------------------------------------ k_bin_build
+BUILD_COUNTS = (1, 64, 65, 1023, 1024, 1025, 16383, 16384)
+BUILD_GLOBAL_COUNTS = (1, 1023, 1024, 1025, 16385)
+BUILD_STREAMED = 70000
+
+
+def build_size(count, shift):
+    """k_bin_build's fullest bin holds exactly `count` candidates of distinct, scrambled depths, dealt round robin over the tiles
+    of bin (1, 1) of a frame of 2 x 2 bins of 2^shift tiles (GS_BIN_SHIFT: 512 x 512 at shift 4, 1024 x 1024 at shift 5; shift
+    3, 256 x 256, for the global path's k_bin_build<1, false>).  The other bins hold min(200, count - 1).
+    k_bin_build<R2, 1024, true> holds 16384 candidates AT LEVEL 0 and at every other bin-local level -- its capacity is not
+    sized by the level -- so every count up to 16384 stays at level 0 without a re-run (predict says the same).  16385 on
+    these frames: the bins can be halved, and the policy does that first (shift 4 -> 3 and k_bin_fast<16>, 5 -> 4), each of
+    the four smaller bins then holding a quarter."""
+    sc = _one_bin_scene(f"build_size/{count}@{shift}", _spread_bits(count), shift,
+                        f"candidates in the fullest bin of 2^{shift} tiles = {count}", {}, background=min(200, count - 1))
+    if count > BUILD_MAX and shift >= ONE_SIZE_SHIFT:
+        half = shift - 1
+        tx, ty = _bin_tiles(count, shift, 1, 1)
+        quarter = np.bincount(((ty >> half) & 1) * 2 + ((tx >> half) & 1), minlength=4)
+        sc.expect["fullest_bin"][half] = int(quarter.max())
+        sc.expect["bin_entries"][half] = sc.expect["n"]
+    return sc
+
+
+UNREFINABLE_FRAME = (4112, 256)                     # 257 x 16 tiles: bins of 16 x 16 tiles, 17 x 1 of them, and 33 x 2 of 8 x 8 do not fit
+
+
+def build_unrefinable(count):
+    """A frame that runs with bins of 16 x 16 tiles by itself (257 tiles across: no GS_BIN_SHIFT) and whose bins cannot be
+    halved: 17 x 1 bins, the last of them ONE tile wide (the partial bin: 16 real tiles of its 256 slots).  Bin 1 holds `count`
+    candidates, the one-tile-wide bin 16 holds 300 over its 16 tiles, every other bin 200."""
+    w, h = UNREFINABLE_FRAME
+    shift = 4
+    recs = []
+    for bx in range(17):
+        k = count if bx == 1 else 300 if bx == 16 else 200
+        tx, ty = _bin_tiles(k, shift, bx, 0)
+        if bx == 16:
+            j = np.arange(k, dtype=np.int64)
+            tx, ty = np.full(k, 256), j % 16
+        recs.append(_splats(_spread_bits(k, DEPTH_2 + 12345 * bx), tx, ty, w, h))
+    rec = np.concatenate(recs)
+    n = len(rec)
+    return LimitScene(f"build_unrefinable/{count}", rec, w, h, {}, f"{count} candidates in a bin of 16 x 16 tiles that cannot be halved",
+                      dict(n=n, visible=n, fullest_bin={shift: count}, bin_entries={shift: n},
+                           bin_counts={shift: {(1, 0): count, (16, 0): 300}}, tile_columns_of_the_last_bin=1))
+
+
+def build_one_tile(shift):
+    """16384 candidates, all of them in ONE tile of the bin: every chunk of the fill adds 64 to that tile's 16-bit count of the
+    round, every round moves its cursor by 1024, and the tile's list is 16384 long."""
+    s = 1 << shift
+    tile = (s + 5, s + 3)
+    return _one_bin_scene(f"build_one_tile@{shift}", _spread_bits(BUILD_MAX), shift, f"a tile list of {BUILD_MAX} from one bin of 2^{shift} tiles",
+                          dict(longest_tile_list=(tile, BUILD_MAX)), tile=tile)
+
+
+BOX_PROBES = ("whole_bin", "tile_row", "tile_column", "four_bins", "frame_edge")
+_BOX_PROBE_LANES = (5, 64 + 63, 200, 201, 3 * 64)  # of the bin's candidates, in id order: big_box's
+
+
+def _probe(one, ux, uy, tz, radius, w, h):
+    """Turn record `one` into a faint isotropic Gaussian centred on pixel (ux, uy) -- on the frame or off it -- whose radius is
+    exactly `radius`.  radius = ceil(3 sqrt(lambda)); with v = the (clamped) view-space slopes of the centre, the projected
+    covariance is s^2 (I + v v^T) + 0.3 I, so lambda = mid + sqrt(max(0.1, mid^2 - det)) with mid = s^2 (1 + |v|^2 / 2) + 0.3
+    and mid^2 - det = (s^2 |v|^2 / 2)^2."""
+    assert w == h
+    tan = np.tan(np.radians(FOV) / 2.0)
+    focal = w / (2.0 * tan)
+    nx, ny = _ndc(np.array([ux], np.float64), w), _ndc(np.array([uy], np.float64), h)
+    _place(one, nx, ny, np.array([tz]), FOV, w, h)
+    one[:, 2] = -np.float32(tz)
+    v2 = float((np.clip(nx * tan, -1.3 * tan, 1.3 * tan) ** 2 + np.clip(ny * tan, -1.3 * tan, 1.3 * tan) ** 2)[0])
+    lam = (radius - 0.5) ** 2 / 9.0
+    s2 = (lam - 0.3) / (1.0 + v2)
+    if s2 * v2 / 2.0 < np.sqrt(0.1):
+        s2 = (lam - 0.3 - np.sqrt(0.1)) / (1.0 + v2 / 2.0)
+        assert s2 * v2 / 2.0 < np.sqrt(0.1)
+    one[:, 55:58] = np.log(np.sqrt(s2) * tz / focal)
+    one[:, 54] = -4.0
+
+
+def build_boxes(shift):
+    """Bin (1, 1) of 2 x 2 bins of S x S tiles holds 2995 single-tile candidates and five faint probes (3000: three rounds), placed
+    like big_box's in lanes 5 and 63 of two waves, two neighbours and lane 0.  A tile box is a square around the centre, clamped
+    to the frame; the bin is the frame's lower right quarter, so a probe centred beyond the frame's edge covers ONE row or column:
+      whole_bin:    the S x S tiles of the bin and no other;
+      tile_row:     the bin's last tile row, all S tiles of it (centred below the frame);
+      tile_column:  the bin's last tile column (centred right of the frame);
+      four_bins:    6 x 6 tiles around the corner the four bins share: 3 x 3 in each, clipped at another pair of edges in each;
+      frame_edge:   4 x 6 tiles against the frame's right edge (the box would go on for two more columns).
+    Every box edge that is not the frame's is 7 px or more clear of moving."""
+    s = 1 << shift
+    sc = _one_bin_scene(f"build_boxes@{shift}", _spread_bits(3000), shift, f"boxes clipped to a bin of {s} x {s} tiles", {})
+    w = sc.width
+    first = sc.expect["n"] - 3000
+    big = 8.0 * s - 8.0
+    at = dict(whole_bin=(24.0 * s, 24.0 * s, big), tile_row=(24.0 * s, 32.0 * s + big - 8.0, big),
+              tile_column=(32.0 * s + big - 8.0, 24.0 * s, big), four_bins=(16.0 * s, 16.0 * s, 40.0),
+              frame_edge=(32.0 * s - 16.0, 16.0 * (s + 4), 40.0))
+    boxes = dict(whole_bin=(s, s, 2 * s, 2 * s), tile_row=(s, 2 * s - 1, 2 * s, 2 * s), tile_column=(2 * s - 1, s, 2 * s, 2 * s),
+                 four_bins=(s - 3, s - 3, s + 3, s + 3), frame_edge=(2 * s - 4, s + 1, 2 * s, s + 7))
+    pinned = {}
+    for j, (name, lane) in enumerate(zip(BOX_PROBES, _BOX_PROBE_LANES)):
+        ux, uy, radius = at[name]
+        _probe(sc.records[first + lane:first + lane + 1], ux, uy, 2.5 + 0.25 * j, radius, w, w)
+        pinned[first + lane] = boxes[name]
+    sc.expect["probe_tiles"] = pinned
+    sc.expect["bin_entries"][shift] += 3                          # four_bins lies in all four
+    sc.expect["instances"] = sc.expect["n"] - 5 + sum((c - a) * (d - b) for a, b, c, d in boxes.values())
+    return sc
 
 
 # ------------------------------------------------------------------------------------------------ crowded bucket
@@ -748,6 +880,23 @@ def measure(scene, ref):
         at = {int(g): k for k, g in enumerate(ids)}
         m["probes"] = {p: (int(x1[at[p]] - x0[at[p]]), int(y1[at[p]] - y0[at[p]])) for p in e["probes"]}
         m["largest_other_box"] = int(np.delete((x1 - x0) * (y1 - y0), [at[p] for p in e["probes"]]).max())
+    if "probe_tiles" in e:
+        box = ref["attr"]["aabb"].astype(np.int64)
+        m["probe_tiles"] = {p: tuple(int(v) for v in box[p]) for p in e["probe_tiles"]}
+        area = (box[:, 2] - box[:, 0]) * (box[:, 3] - box[:, 1])
+        m["largest_other_tile_box"] = int(np.delete(area, list(e["probe_tiles"])).max())
+    if "longest_tile_list" in e:
+        b = ref["boundaries"].astype(np.int64)
+        tx = tiles_across(scene.width)
+        lens = b[1::2] - b[0::2]
+        t = int(lens.argmax())
+        m["longest_tile_list"] = ((t % tx, t // tx), int(lens[t]))
+    if "bin_counts" in e:
+        m["bin_counts"] = {}
+        for s, bins in e["bin_counts"].items():
+            members = bin_members(ref, s)
+            m["bin_counts"][s] = {k: len(members.get(k, ())) for k in bins}
+            m["tile_columns_of_the_last_bin"] = tiles_across(scene.width) - ((tiles_across(scene.width) - 1) >> s << s)
     if "tile_lists" in e:
         b = ref["boundaries"].astype(np.int64)
         tx = tiles_across(scene.width)
@@ -800,25 +949,35 @@ def plan_slabs(counts):
     return sizes if len(sizes) <= MAX_SLABS else None
 
 
-def predict(scene, forced=False):
+def predict(scene, forced=False, sort_path=0):
     """What a FRESH renderer's stats say after one frame of the scene (gs_depth_policy.h, restated): the level it ends at, the
-    re-runs on the way, the bin edge, the fullest bin.  forced: gs_set_sort_path(2); "error" where that mode gives up."""
+    re-runs on the way, the bin edge, the fullest bin.  forced: gs_set_sort_path(2); "error" where that mode gives up, and
+    "bin too full" where it gives up over a bin of 16 x 16 tiles or more.  sort_path 1: gs_set_sort_path(1), the global path at once.
+    Bins of 16 x 16 tiles or more (shift >= 4) are ordered by k_bin_build at every bin-local level: such a bin fits a
+    bin-local level if and only if it holds <= 16384, at level 0 already, and one that does not has no level 4 to go to -- it
+    is refined or goes straight to the global path."""
     tx, ty = tiles_across(scene.width), tiles_across(scene.height)
     shift = base_shift(tx, ty, scene.min_shift)
-    level, retries, refined = 0, 0, False
+    level, retries, refined = (GLOBAL_LEVEL if sort_path == 1 else 0), 0, False
     while True:
         fullest = scene.expect["fullest_bin"][shift]
-        fits = level == GLOBAL_LEVEL or (fullest <= LEVEL_LIMITS[level] and not (level == SLAB_LEVEL and scene.slabs_fail))
+        one_size = shift >= ONE_SIZE_SHIFT
+        if one_size:
+            fits = level == GLOBAL_LEVEL or fullest <= BUILD_MAX
+        else:
+            fits = level == GLOBAL_LEVEL or (fullest <= LEVEL_LIMITS[level] and not (level == SLAB_LEVEL and scene.slabs_fail))
         if fits:
             return dict(sort_level=level, sort_path=1 if level == GLOBAL_LEVEL else 2, retries=retries, bin_tiles=1 << shift,
                         max_bin_entries=fullest, num_bin_entries=scene.expect["bin_entries"][shift])
         wanted = level + 1
         while wanted < GLOBAL_LEVEL and fullest > LEVEL_LIMITS[wanted]:
             wanted += 1
+        if one_size:
+            wanted = GLOBAL_LEVEL
         if wanted >= SLAB_LEVEL and not refined and can_refine(scene.width, scene.height, scene.min_shift):
             refined, shift, level = True, shift - 1, max(level, SLAB_LEVEL - 1)
         else:
             if forced and wanted >= GLOBAL_LEVEL:
-                return "error"
+                return "bin too full" if one_size else "error"
             level = max(level, wanted)
         retries += 1

@@ -60,6 +60,10 @@ int dp_overflowed(void* h, const uint32_t* frames, int count) {
     return static_cast<int>(static_cast<DepthPolicy*>(h)->frames_overflowed(q.data(), count));
 }
 void dp_retired(void* h, int ran_level, uint32_t max_bin) { static_cast<DepthPolicy*>(h)->frame_retired(ran_level, max_bin); }
+// the same for a frame that ran with bins of 2^bin_shift tiles (the renderer always says which)
+void dp_retired_at(void* h, int ran_level, uint32_t max_bin, int bin_shift) {
+    static_cast<DepthPolicy*>(h)->frame_retired(ran_level, max_bin, bin_shift);
+}
 
 int dp_verdict(int which) {  // 0 re-run, 1 "holds more candidates", 2 "too crowded"
     const DepthPolicy::Verdict v[3] = {DepthPolicy::kRerun, DepthPolicy::kBinTooFull, DepthPolicy::kDepthsTooCrowded};

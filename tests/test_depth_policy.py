@@ -12,6 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "3dgs.cpp_amd", "csrc")
 FIELDS = ("sort_mode", "level", "refined", "settle_level", "frames_since_fallback", "slab_hold", "slab_clean_frames", "min_bin_shift")
 HD, UHD = (1920, 1080), (3840, 2160)
+WIDE = (4112, 256)  # 257 x 16 tiles: bins of 16 x 16 tiles (33 bins of 8 do not fit across), which cannot be halved
 BIN_OVERFLOW = 2  # Counters::overflow bit 1: a bin outgrew the in-LDS order of its level (bit 0: a buffer's capacity)
 
 
@@ -32,6 +33,7 @@ def sim(tmp_path_factory):
     lib.dp_can_refine.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
     lib.dp_overflowed.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.c_int]
     lib.dp_retired.argtypes = [C.c_void_p, C.c_int, C.c_uint32]
+    lib.dp_retired_at.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_int]
     assert [lib.dp_limit(lv) for lv in range(5)] == [4096, 8192, 12288, 16384, 65535]
     return lib
 
@@ -82,9 +84,12 @@ class Policy:
         flat = [w for f in frames for w in f]
         return self.lib.dp_overflowed(self.h, (C.c_uint32 * len(flat))(*flat), len(frames))
 
-    def retired(self, max_bin, frames=1, level=None):
+    def retired(self, max_bin, frames=1, level=None, size=None):
         for _ in range(frames):
-            self.lib.dp_retired(self.h, self.frame_level() if level is None else level, max_bin)
+            if size is None:
+                self.lib.dp_retired(self.h, self.frame_level() if level is None else level, max_bin)
+            else:
+                self.lib.dp_retired_at(self.h, self.frame_level() if level is None else level, max_bin, self.geometry(size)[0])
 
 
 # ---- geometry ----
@@ -157,6 +162,67 @@ def test_beyond_the_refined_bins(sim):
     # where the grid cannot be refined the same sizes go straight to the slabs / the global path
     p = Policy(sim)
     assert p.overflowed(p.frame(20000, size=UHD)) == p.RERUN and (p.level, p.refined) == (4, False)
+
+
+# ---- bins of 16 x 16 tiles or more: one kernel, 16384 at every bin-local level, no slabs ----
+
+def test_a_large_bin_that_cannot_be_halved_goes_straight_to_the_global_path(sim):
+    p = Policy(sim, frames_since_fallback=9, slab_clean_frames=5)
+    assert p.geometry(WIDE) == (4, 17, 1, 5) and not p.can_refine(WIDE)
+    assert p.overflowed(p.frame(20000, size=WIDE)) == p.RERUN
+    # one re-run: not level 4 first (the same kernel with the same 16384), and nothing charged to the slabs
+    assert p.state() == Policy(sim, level=5, slab_clean_frames=5).state()
+    assert (p.slab_hold, p.slab_clean_frames, p.refined, p.settle_level) == (32, 5, False, False)
+    # the same from a level the policy had climbed to on another frame size, level 4 included
+    for lv in (1, 3, 4):
+        p = Policy(sim, level=lv, slab_clean_frames=5)
+        assert p.overflowed(p.frame(20000, size=WIDE)) == p.RERUN
+        assert (p.level, p.slab_hold, p.slab_clean_frames) == (5, 32, 5), lv
+    # bins of 32 x 32 tiles (8208 px: 513 tiles, 17 bins across, 33 of 16 would not fit) alike
+    p = Policy(sim)
+    assert p.geometry((8208, 256))[0] == 5 and not p.can_refine((8208, 256))
+    assert p.overflowed(p.frame(16385, size=(8208, 256))) == p.RERUN and (p.level, p.slab_hold) == (5, 32)
+
+
+def test_forced_bin_local_mode_reports_a_large_bin_as_too_full(sim):
+    before = dict(sort_mode=2, frames_since_fallback=7, slab_clean_frames=3)
+    p = Policy(sim, **before)
+    assert p.overflowed(p.frame(20000, size=WIDE)) == p.BIN_TOO_FULL  # not TOO_CROWDED: no slab ever saw this bin
+    assert p.state() == Policy(sim, **before).state()
+    p = Policy(sim, sort_mode=2, level=4)
+    assert p.overflowed(p.frame(20000, size=WIDE)) == p.BIN_TOO_FULL and (p.level, p.slab_hold) == (4, 32)
+
+
+def test_a_large_bin_is_still_halved_first(sim):
+    # GS_BIN_SHIFT=4 on a small frame: bins of 16 x 16 tiles that can be halved
+    p = Policy(sim, min_bin_shift=4)
+    assert p.geometry((512, 512)) == (4, 2, 2, 4) and p.can_refine((512, 512))
+    assert p.overflowed(p.frame(20000, size=(512, 512))) == p.RERUN
+    assert (p.refined, p.level, p.settle_level, p.slab_hold) == (True, 3, True, 32) and p.geometry((512, 512))[0] == 3
+    # 32 x 32 -> 16 x 16, and a bin of those beyond 16384 then has the global path only
+    p = Policy(sim, min_bin_shift=5)
+    assert p.overflowed(p.frame(70000, size=(1024, 1024))) == p.RERUN
+    assert (p.refined, p.level) == (True, 3) and p.geometry((1024, 1024))[0] == 4
+    assert p.overflowed(p.frame(17600, size=(1024, 1024))) == p.RERUN and (p.level, p.slab_hold, p.slab_clean_frames) == (5, 32, 0)
+    # the default bins of a frame up to 4096 px are untouched by any of this
+    p = Policy(sim)
+    assert p.overflowed(p.frame(20000, size=UHD)) == p.RERUN and (p.level, p.refined) == (4, False)
+
+
+def test_large_bins_leave_the_global_path_only_for_what_their_kernel_holds(sim):
+    """Without slabs below it, level 5 steps down when the fullest bin fits 7/8 of 16384 -- not 7/8 of the slabs' 65535, which
+    would send a bin of 20000 back into the overflow it came from every 32 frames."""
+    p = Policy(sim, level=5)
+    p.retired(20000, frames=100, size=WIDE)
+    assert (p.level, p.frames_since_fallback) == (5, 0)
+    p.retired(16384 * 7 // 8, frames=31, size=WIDE)
+    assert p.level == 5
+    p.retired(16384 * 7 // 8, size=WIDE)
+    assert p.level == 4
+    # bins that have slabs: as before
+    p = Policy(sim, level=5)
+    p.retired(20000, frames=32, size=HD)
+    assert p.level == 4
 
 
 # ---- slab hold ----

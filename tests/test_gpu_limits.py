@@ -4,8 +4,11 @@ image bit for bit in exp mode 2, the default blend (mode 3) within the guarded t
 re-runs, bin edge, fullest bin, candidates -- equal to what the restated policy predicts for a fresh renderer.  A case that is
 no longer on its edge FAILS: the pinned quantity is re-measured from the oracle's stages here too.
 
-Binning and blend: every capacity.  k_preprocess: every count of visible lanes of a wave at which its SH fetch, its run of slots
-in the dense lists or its record store changes shape, under every combination of SH storage, read order, dense lists and the
+Binning and blend: every capacity.  k_bin_build, the level-2 kernel of bins of 16 x 16 and 32 x 32 tiles and of every bin size on
+the global path, in its five instantiations: its one capacity (16384 at every bin-local level), the sort rounds of 1024, equal
+depths across a wave's run of the list, a tile that takes all 16384, boxes clipped to the bin, a bin cut by the frame's edge, the
+streamed lists of the global path up to 70000, and the list buffer running over inside the kernel.  k_preprocess: every count
+of visible lanes of a wave at which its SH fetch, its run of slots in the dense lists or its record store changes shape, under every combination of SH storage, read order, dense lists and the
 antialiased mode, and the dense lists full to their last slot.  The global depth order: every shape of its grid.
 
 Not covered, and why:
@@ -49,12 +52,16 @@ def _frame(pkg, oracle, monkeypatch, scene, extra_env=None):
     return gs, pkg.Renderer(gs), u, ref
 
 
-def _assert_frame(pkg, rend, u, ref, scene, want, label):
-    """One frame: stats as predicted, every stage and the mode-2 image exact, the default blend within the guarded tolerance."""
+def _assert_frame(pkg, rend, u, ref, scene, want, label, grows=False):
+    """One frame: stats as predicted, every stage and the mode-2 image exact, the default blend within the guarded tolerance.
+    grows: the buffers start too small -- at least one re-run more than predicted, everything else as predicted."""
     img, _ = rend.render_host(u)
     st = rend.stats()
     have = {k: getattr(st, k) for k in STAT_KEYS}
     print(f"{label}: {have}")
+    if want is not None and grows:
+        assert have["retries"] >= want["retries"] + 1, f"{label}: {have['retries']} re-runs with buffers that start too small"
+        have["retries"] = want["retries"]
     if want is not None:
         assert have == {k: want[k] for k in STAT_KEYS}, f"{label}: stats {have}, predicted {want}"
     assert st.num_visible == scene.expect["visible"] and st.num_gaussians == scene.expect["n"]
@@ -65,19 +72,26 @@ def _assert_frame(pkg, rend, u, ref, scene, want, label):
     return st
 
 
-def _run(pkg, oracle, monkeypatch, scene, forced=False, extra_env=None):
+BIN_TOO_FULL = "a bin holds more candidates than the bin-local sort can order"   # gs_renderer.cpp: DepthPolicy::kBinTooFull
+
+
+def _run(pkg, oracle, monkeypatch, scene, forced=False, extra_env=None, global_path=False, grows=False):
+    """global_path: gs_set_sort_path(1), the global depth order at once (level 5, no re-run, the scene's own bins)."""
     gs, rend, u, ref = _frame(pkg, oracle, monkeypatch, scene, extra_env)
     try:
-        want = ls.predict(scene, forced) if "fullest_bin" in scene.expect else None
-        rend.set_sort_path(2 if forced else 0)
-        label = f"{scene.name}{' forced' if forced else ''}{' ' + str(extra_env) if extra_env else ''}"
-        if want == "error":
+        assert not (forced and global_path)
+        want = ls.predict(scene, forced, sort_path=1 if global_path else 0) if "fullest_bin" in scene.expect else None
+        rend.set_sort_path(1 if global_path else 2 if forced else 0)
+        label = f"{scene.name}{' forced' if forced else ' global' if global_path else ''}{' ' + str(extra_env) if extra_env else ''}"
+        if want in ("error", "bin too full"):
             with pytest.raises(pkg.GsError) as e:
                 rend.render_host(u)
             assert e.value.code == -5
             print(f"{label}: raised {e.value}")
+            if want == "bin too full":
+                assert BIN_TOO_FULL in str(e.value), f"{label}: the error of another failure: {e.value}"
             return None
-        return _assert_frame(pkg, rend, u, ref, scene, want, label)
+        return _assert_frame(pkg, rend, u, ref, scene, want, label, grows)
     finally:
         rend.close()
         gs.close()
@@ -145,6 +159,91 @@ def test_equal_depth_run_in_a_slab(pkg, oracle, gpu, monkeypatch, length, place,
         assert (st.sort_path, st.sort_level, st.retries) == (2, 4, 1) and forced.sort_level == 4
     else:
         assert (st.sort_path, st.sort_level, st.retries) == (1, 5, 2) and forced is None
+
+
+# ------------------------------------------------------------------------------------------------ k_bin_build
+@pytest.mark.parametrize("shift", [4, 5])
+@pytest.mark.parametrize("count", ls.BUILD_COUNTS)
+def test_build_size_in_lds(pkg, oracle, gpu, monkeypatch, count, shift):
+    """k_bin_build<4 / 16, 1024, true>: one candidate, a chunk of 64 and one more, a sort round of 1024 one short, full and one
+    more (1025: two rounds, a wave owns 128 elements instead of 64), and its capacity -- 16383 and 16384, at LEVEL 0, since the
+    kernel holds 16384 at every level.  No re-run at any of them, in automatic and in forced mode."""
+    for forced in (False, True):
+        st = _run(pkg, oracle, monkeypatch, ls.build_size(count, shift), forced=forced)
+        assert (st.sort_path, st.sort_level, st.retries, st.max_bin_entries, st.bin_tiles) == (2, 0, 0, count, 1 << shift)
+
+
+@pytest.mark.parametrize("shift", [4, 5])
+def test_build_16385_refines_the_bins_first(pkg, oracle, gpu, monkeypatch, shift):
+    """One beyond k_bin_build's capacity where the bins can be halved: one re-run with bins of half the edge (k_bin_fast<16> below
+    shift 4, k_bin_build<4> below shift 5), a quarter of the candidates in each."""
+    for forced in (False, True):
+        st = _run(pkg, oracle, monkeypatch, ls.build_size(16385, shift), forced=forced)
+        assert (st.bin_tiles, st.sort_path, st.sort_level, st.retries, st.max_bin_entries) == (1 << (shift - 1), 2, 3, 1, 4097)
+
+
+@pytest.mark.parametrize("count", [16384, 16385])
+def test_build_capacity_where_the_bins_cannot_be_halved(pkg, oracle, gpu, monkeypatch, count):
+    """A frame 4112 px wide runs with bins of 16 x 16 tiles by itself, 17 x 1 of them (the last one tile wide), and they cannot be
+    halved.  16384 in a bin: level 0.  16385: such bins have no slabs -- level 4 is the same kernel with the same capacity -- so
+    the frame goes to the global path with ONE re-run, and forced bin-local mode says that the bin is too full (not that its
+    depths are too crowded: no slab ever saw it)."""
+    sc = ls.build_unrefinable(count)
+    st = _run(pkg, oracle, monkeypatch, sc)
+    forced = _run(pkg, oracle, monkeypatch, sc, forced=True)
+    if count == 16384:
+        assert (st.sort_path, st.sort_level, st.retries, st.bin_tiles) == (2, 0, 0, 16) and forced.sort_level == 0
+    else:
+        assert (st.sort_path, st.sort_level, st.retries, st.bin_tiles) == (1, 5, 1, 16) and forced is None
+
+
+@pytest.mark.parametrize("shift", [4, 5])
+def test_build_one_tile_takes_every_candidate(pkg, oracle, gpu, monkeypatch, shift):
+    """16384 candidates in one tile of the bin: every chunk adds 64 to that tile's 16-bit count of the round, every round of 16
+    chunks moves its ping-pong cursor by 1024, sixteen times over."""
+    for forced in (False, True):
+        st = _run(pkg, oracle, monkeypatch, ls.build_one_tile(shift), forced=forced)
+        assert (st.sort_path, st.sort_level, st.retries, st.max_bin_entries) == (2, 0, 0, 16384)
+    st = _run(pkg, oracle, monkeypatch, ls.build_one_tile(shift), global_path=True)
+    assert (st.sort_path, st.sort_level, st.retries) == (1, 5, 0)
+
+
+@pytest.mark.parametrize("shift", [4, 5])
+def test_build_boxes_clipped_to_the_bin(pkg, oracle, gpu, monkeypatch, shift):
+    """packed_cover_masks and the transpose over 256 and 1024 tile slots: a box that is the whole bin, one tile row of it, one tile
+    column, a box over the corner of four bins (clipped into each) and one cut by the frame's edge, among single-tile boxes --
+    with the boxes cached in LDS (R2 = 4) and recomputed (R2 = 16), sorted and streamed."""
+    for mode in (dict(), dict(forced=True), dict(global_path=True)):
+        st = _run(pkg, oracle, monkeypatch, ls.build_boxes(shift), **mode)
+        assert st.retries == 0 and st.max_bin_entries == 3000 and st.bin_tiles == 1 << shift
+
+
+@pytest.mark.parametrize("shift", [4, 5])
+@pytest.mark.parametrize("place", ls.RUN_PLACES)
+@pytest.mark.parametrize("length", [2, 100])
+def test_equal_depth_run_in_a_build_bin(pkg, oracle, gpu, monkeypatch, length, place, shift):
+    """k_bin_build has no tie step: its four passes are stable and its candidates arrive in id order, so equal depths must come
+    out in id order whatever their number -- at the list's start, its end, across the border between two waves' elements
+    (3000 candidates: three rounds, 192 elements per wave) and with the ids scattered over every wave.  No limit, no re-run."""
+    for forced in (False, True):
+        st = _run(pkg, oracle, monkeypatch, ls.equal_run(length, place, False, shift=shift), forced=forced)
+        assert (st.sort_path, st.sort_level, st.retries) == (2, 0, 0)
+
+
+@pytest.mark.parametrize("shift,count", [(s, c) for s in (3, 4, 5) for c in ls.BUILD_GLOBAL_COUNTS] + [(4, ls.BUILD_STREAMED), (5, ls.BUILD_STREAMED)])
+def test_build_size_streamed(pkg, oracle, gpu, monkeypatch, shift, count):
+    """k_bin_build<1 / 4 / 16, 1024, false>: the bin's list arrives ordered and is streamed, ids read back from LDS per fill round:
+    one candidate, a round one short, full and one more, and beyond every capacity of the sorted forms (16385; 70000)."""
+    st = _run(pkg, oracle, monkeypatch, ls.build_size(count, shift), global_path=True)
+    assert (st.sort_path, st.sort_level, st.retries, st.max_bin_entries, st.bin_tiles) == (1, 5, 0, count, 1 << shift)
+
+
+@pytest.mark.parametrize("shift,global_path", [(4, False), (5, False), (3, True), (4, True), (5, True)])
+def test_build_list_buffer_runs_over(pkg, oracle, gpu, monkeypatch, shift, global_path):
+    """Buffers that start at 256 entries: the candidate buffer grows first, then a frame overflows the list buffer INSIDE
+    k_bin_build -- saturated ranges, stores dropped by the bounded buffer resource -- and is re-run; the lists are exact."""
+    st = _run(pkg, oracle, monkeypatch, ls.build_size(1025, shift), global_path=global_path, extra_env={"GS_INITIAL_CAPACITY": "256"}, grows=True)
+    assert st.retries >= 1 and st.max_bin_entries == 1025 and st.sort_path == (1 if global_path else 2)
 
 
 # ------------------------------------------------------------------------------------------------ crowded bucket

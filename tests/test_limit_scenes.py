@@ -28,7 +28,7 @@ def _check(oracle, scene):
     for key, want in scene.expect.items():
         assert got[key] == want, f"{scene.name} ({scene.pins}): {key} is {got[key]}, the builder promises {want}"
     # every small splat covers one tile: the instance count is the candidate count wherever no probe is in the scene
-    if "probes" not in scene.expect:
+    if "probes" not in scene.expect and "probe_tiles" not in scene.expect:
         assert len(ref["keys"]) == got["visible"]
     return got, ref
 
@@ -68,6 +68,135 @@ def test_equal_run(oracle, length, place, slab):
     else:
         assert (p["sort_level"], p["retries"]) == ((4, 1) if length <= ls.TIE_RUN_MAX else (5, 2))
         assert (ls.predict(sc, forced=True) == "error") == (length > ls.TIE_RUN_MAX)
+
+
+# ------------------------------------------------------------------------------------------------ k_bin_build
+@pytest.mark.parametrize("shift", [4, 5])
+@pytest.mark.parametrize("count", ls.BUILD_COUNTS + (16385,))
+def test_build_size(oracle, count, shift):
+    """The fullest bin of 16 x 16 or 32 x 32 tiles holds exactly `count`; up to 16384 the frame stays at level 0 -- k_bin_build's
+    capacity is 16384 at every level -- and 16385 halves the bins first, a quarter of the candidates in each."""
+    sc = ls.build_size(count, shift)
+    assert (sc.width, sc.height) == ((512, 512) if shift == 4 else (1024, 1024)) and sc.env == {"GS_BIN_SHIFT": str(shift)}
+    got, ref = _check(oracle, sc)
+    assert got["fullest_bin"][shift] == count and ls.base_shift(2 << shift, 2 << shift, shift) == shift
+    # round robin over the bin's tiles: the lists of the bin differ by one at most, and every tile of it has one from S^2 on
+    b = ref["boundaries"].astype(np.int64)
+    lens = (b[1::2] - b[0::2]).reshape(2 << shift, 2 << shift)[1 << shift:, 1 << shift:]
+    assert lens.sum() == count and lens.max() - lens.min() <= 1
+    bits = ref["attr"]["depth"][-count:].view(np.uint32)
+    assert len(np.unique(bits)) == count and (count < 3 or (np.diff(bits.astype(np.int64)) < 0).any())   # distinct, not in id order
+    p = ls.predict(sc)
+    assert p == ls.predict(sc, forced=True)
+    if count <= ls.BUILD_MAX:
+        assert (p["sort_level"], p["retries"], p["bin_tiles"], p["max_bin_entries"]) == (0, 0, 1 << shift, count)
+    else:
+        assert ls.can_refine(sc.width, sc.height, shift) and sc.expect["fullest_bin"] == {shift: 16385, shift - 1: 4097}
+        assert (p["sort_level"], p["retries"], p["bin_tiles"], p["max_bin_entries"]) == (3, 1, 1 << (shift - 1), 4097)
+
+
+@pytest.mark.parametrize("shift,count", [(s, c) for s in (3, 4, 5) for c in ls.BUILD_GLOBAL_COUNTS] + [(4, ls.BUILD_STREAMED), (5, ls.BUILD_STREAMED)])
+def test_build_size_on_the_global_path(oracle, shift, count):
+    """The same scenes as the streamed forms run them (R2 = 1, 4, 16): level 5 at once, the scene's own bins, no re-run whatever
+    the count; 70000 single-tile splats are 70000 instances."""
+    sc = ls.build_size(count, shift)
+    got, ref = _check(oracle, sc)
+    assert got["fullest_bin"][shift] == count and len(ref["keys"]) == sc.expect["n"] <= 70600
+    assert ls.predict(sc, sort_path=1) == dict(sort_level=5, sort_path=1, retries=0, bin_tiles=1 << shift, max_bin_entries=count,
+                                               num_bin_entries=sc.expect["n"])
+    assert sc.width * sc.height <= 1 << 20
+
+
+@pytest.mark.parametrize("count", [16384, 16385])
+def test_build_unrefinable(oracle, count):
+    """4112 x 256: bins of 16 x 16 tiles by the frame's own size, 17 x 1 of them, the last one tile wide; they cannot be halved, so
+    the 16385th candidate sends the frame straight to the global path -- once -- or is `bin too full` where bin-local is forced."""
+    sc = ls.build_unrefinable(count)
+    tx, ty = ls.tiles_across(sc.width), ls.tiles_across(sc.height)
+    assert (tx, ty) == (257, 16) and ls.base_shift(tx, ty, 3) == 4 and not ls.can_refine(sc.width, sc.height, 3) and not sc.env
+    got, _ = _check(oracle, sc)
+    assert got["bin_counts"][4] == {(1, 0): count, (16, 0): 300} and got["tile_columns_of_the_last_bin"] == 1
+    p, forced = ls.predict(sc), ls.predict(sc, forced=True)
+    if count == 16384:
+        assert (p["sort_path"], p["sort_level"], p["retries"]) == (2, 0, 0) and forced == p
+    else:
+        assert (p["sort_path"], p["sort_level"], p["retries"], p["bin_tiles"]) == (1, 5, 1, 16) and forced == "bin too full"
+
+
+@pytest.mark.parametrize("shift", [4, 5])
+def test_build_one_tile(oracle, shift):
+    sc = ls.build_one_tile(shift)
+    got, ref = _check(oracle, sc)
+    s = 1 << shift
+    assert got["longest_tile_list"] == ((s + 5, s + 3), 16384) and got["fullest_bin"][shift] == 16384
+    # nothing else in that bin: its other tiles' lists are empty
+    b = ref["boundaries"].astype(np.int64)
+    lens = (b[1::2] - b[0::2]).reshape(2 * s, 2 * s)[s:, s:]
+    assert lens.sum() == 16384 and np.count_nonzero(lens) == 1
+    assert (ls.predict(sc)["sort_level"], ls.predict(sc)["retries"]) == (0, 0)
+
+
+@pytest.mark.parametrize("shift", [4, 5])
+def test_build_boxes(oracle, shift):
+    sc = ls.build_boxes(shift)
+    got, ref = _check(oracle, sc)
+    s = 1 << shift
+    boxes = dict(zip(ls.BOX_PROBES, [got["probe_tiles"][p] for p in sorted(got["probe_tiles"], key=list(sc.expect["probe_tiles"]).index)]))
+    assert boxes["whole_bin"] == (s, s, 2 * s, 2 * s)
+    assert boxes["tile_row"] == (s, 2 * s - 1, 2 * s, 2 * s) and boxes["tile_column"] == (2 * s - 1, s, 2 * s, 2 * s)
+    x0, y0, x1, y1 = boxes["four_bins"]
+    assert x0 < s < x1 and y0 < s < y1 and (x1 - x0, y1 - y0) == (6, 6)
+    x0, y0, x1, y1 = boxes["frame_edge"]
+    assert x1 == 2 * s == ls.tiles_across(sc.width) and (x1 - x0, y1 - y0) == (4, 6)
+    # off the frame's edge the box would go on: the clamp to the tile grid is what cuts it (preprocess.comp:161-164)
+    edge = list(sc.expect["probe_tiles"])[4]
+    assert (ref["attr"]["uv"][edge, 0] + ref["attr"]["color_radii"][edge, 3] + 15) // 16 > 2 * s
+    assert got["largest_other_tile_box"] == 1 and got["fullest_bin"][shift] == 3000 and got["instances"] == len(ref["keys"])
+    assert (ref["attr"]["conic_opacity"][list(sc.expect["probe_tiles"]), 3] < 0.02).all()     # faint
+    # the probes are among the bin's candidates at lanes 5 and 63, two neighbours and lane 0 of their chunks of 64
+    first = sc.expect["n"] - 3000
+    assert [(p - first) % 64 for p in sc.expect["probe_tiles"]] == [5, 63, 8, 9, 0]
+
+
+@pytest.mark.parametrize("shift", [4, 5])
+@pytest.mark.parametrize("place", ls.RUN_PLACES)
+@pytest.mark.parametrize("length", [2, 100])
+def test_equal_run_in_a_build_bin(oracle, length, place, shift):
+    """3000 candidates in all: three rounds, 192 elements of the list per wave; the straddling run crosses element 192."""
+    sc = ls.equal_run(length, place, False, shift=shift)
+    got, _ = _check(oracle, sc)
+    assert got["longest_run"] == length and got["fullest_bin"][shift] == 3000 and -(-3000 // ls.THREADS) * ls.WAVE == 192
+    if place == "straddle":
+        assert got["run_start"] < 192 <= got["run_start"] + length - 1 and (length < 31 or got["run_start"] == 192 - 30)
+    p = ls.predict(sc)
+    assert (p["sort_level"], p["retries"]) == (0, 0) and ls.predict(sc, forced=True) == p
+
+
+def test_build_scenes_notice_a_missed_edge(oracle):
+    """The re-measurement is sensitive: one candidate more or fewer in the fullest bin, a probe moved by a tile, a candidate of
+    the one-tile scene in the next tile, the run one element later -- and the pinned quantities no longer hold."""
+    sc = ls.build_size(16384, 4)
+    sc.records = sc.records[:-1]
+    with pytest.raises(AssertionError, match="the builder promises"):
+        _check(oracle, sc)
+    sc = ls.build_unrefinable(16385)
+    sc.records = np.concatenate([sc.records, sc.records[300:301]])         # (one more in bin 1)
+    with pytest.raises(AssertionError, match="the builder promises"):
+        _check(oracle, sc)
+    sc = ls.build_boxes(5)
+    row = list(sc.expect["probe_tiles"])[1]
+    sc.records[row, 1] -= np.float32(16.0 / (sc.width / (2.0 * np.tan(np.radians(ls.FOV) / 2.0))) * sc.records[row, 2])   # 16 px up
+    with pytest.raises(AssertionError, match="probe_tiles"):
+        _check(oracle, sc)
+    sc = ls.build_one_tile(4)
+    moved = ls._splats(sc.records[-1:, 2].copy().view(np.uint32) & np.uint32(0x7FFFFFFF), [22], [19], sc.width, sc.height)
+    sc.records[-1] = moved[0]
+    with pytest.raises(AssertionError, match="longest_tile_list"):
+        _check(oracle, sc)
+    sc = ls.equal_run(100, "straddle", False, shift=4)
+    sc.expect["run_start"] += 1
+    with pytest.raises(AssertionError, match="run_start"):
+        _check(oracle, sc)
 
 
 @pytest.mark.parametrize("k", [63, 64, 65, 66])
