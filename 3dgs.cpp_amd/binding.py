@@ -54,6 +54,7 @@ STAGES = dict(tiles=(0, np.uint32), depth=(1, np.float32), radius=(2, np.float32
 # every symbol include/gs3d_hip.h declares
 SYMBOLS = ["gs_last_error", "gs_device_count", "gs_read_ply", "gs_activate_records", "gs_scene_load_ply", "gs_scene_from_records",
            "gs_scene_from_vertices", "gs_scene_from_device_blob", "gs_scene_blob_floats", "gs_scene_blob",
+           "gs_scene_from_device_arrays", "gs_scene_update_from_device_arrays", "gs_debug_activation_expf_scan",
            "gs_scene_num_vertices", "gs_scene_quantize_sh", "gs_scene_sh_bits", "gs_scene_download_vertex_range",
            "gs_scene_download_vertices", "gs_scene_download_cov3d",
            "gs_scene_destroy", "gs_renderer_create", "gs_renderer_destroy", "gs_camera_uniforms",
@@ -90,6 +91,83 @@ def debug_expf_scan(first_bits, count, device=0):
     guard = np.zeros(4, np.float64)
     _check(lib().gs_debug_expf_scan(C.c_int(device), C.c_uint32(first_bits), C.c_uint64(count), _p(sums), C.c_uint64(blocks), _p(guard)))
     return sums, guard
+
+
+def debug_activation_expf_scan(first_bits, count, device=0):
+    """Test hook gs_debug_activation_expf_scan: block checksums (as debug_expf_scan forms them) of the exp() that the device-array
+    ingest activates scales and opacities with, over the bit patterns [first_bits, first_bits + count)."""
+    blocks = (count + (1 << 20) - 1) >> 20
+    sums = np.zeros(blocks, np.uint64)
+    _check(lib().gs_debug_activation_expf_scan(C.c_int(device), C.c_uint32(first_bits), C.c_uint64(count), _p(sums), C.c_uint64(blocks)))
+    return sums
+
+
+class DeviceArrays(C.Structure):
+    """gs_device_arrays: a trainer's six device arrays (include/gs3d_hip.h)."""
+    _fields_ = [("means", C.c_void_p), ("log_scales", C.c_void_p), ("quats", C.c_void_p), ("opacity_logits", C.c_void_p),
+                ("sh_dc", C.c_void_p), ("sh_rest", C.c_void_p), ("sh_rest_coeffs", C.c_uint32)]
+
+
+def _tensor_rows(name, t, trailing, device):
+    """Rows of device tensor `t` after checking it is what gs_device_arrays takes: float32, contiguous, on GPU `device`, of
+    shape (rows, *trailing) up to singleton axes (the Inria trainer keeps _features_dc as (N, 1, 3), _opacity as (N, 1)).
+    `trailing` None: (rows, k, 3) with k in {0, 3, 8, 15}; returns (rows, k) then."""
+    if not all(hasattr(t, a) for a in ("data_ptr", "shape", "dtype", "is_contiguous", "device")):
+        raise TypeError(f"{name}: a device tensor is needed (data_ptr, shape, dtype, is_contiguous, device), got {type(t).__name__}")
+    if str(t.dtype).rsplit(".", 1)[-1] != "float32":
+        raise TypeError(f"{name}: dtype must be float32, not {t.dtype}")
+    shape = tuple(int(d) for d in t.shape)
+    if len(shape) < 1:
+        raise ValueError(f"{name}: shape {shape} has no row axis")
+    if not t.is_contiguous():
+        raise ValueError(f"{name}: the tensor must be contiguous (dense rows); call .contiguous()")
+    rows, rest = shape[0], tuple(d for d in shape[1:] if d != 1) if trailing is not None else shape[1:]
+    if trailing is None:
+        if len(rest) != 2 or rest[1] != 3 or rest[0] not in (0, 3, 8, 15):
+            raise ValueError(f"{name}: shape {shape} is not (rows, k, 3) with k in 0, 3, 8, 15")
+        rows = (rows, rest[0])
+    elif rest != tuple(d for d in trailing if d != 1):
+        raise ValueError(f"{name}: shape {shape} is not (rows, {', '.join(map(str, trailing))})")
+    dev = t.device
+    kind, index = getattr(dev, "type", str(dev).split(":")[0]), getattr(dev, "index", None)
+    if kind == "cpu":
+        raise ValueError(f"{name}: the tensor is on the CPU; Scene.from_records takes host data")
+    if (0 if index is None else int(index)) != int(device):
+        raise ValueError(f"{name}: the tensor is on device {index}, the scene on device {device}")
+    return rows
+
+
+def _device_arrays(tensors, device, require):
+    """(DeviceArrays, rows) from {member: tensor or None}; every check of the tensors happens here, before C is called."""
+    trailing = dict(means=(3,), log_scales=(3,), quats=(4,), opacity_logits=(1,), sh_dc=(3,), sh_rest=None)
+    a, rows = DeviceArrays(), None
+    for name, t in tensors.items():
+        if t is None:
+            if require and name != "sh_rest":
+                raise TypeError(f"{name} is required")
+            continue
+        r = _tensor_rows(name, t, trailing[name], device)
+        if name == "sh_rest":
+            r, a.sh_rest_coeffs = r
+            if a.sh_rest_coeffs == 0:
+                continue  # (rows, 0, 3): degree 0, no pointer
+        if rows is not None and r != rows:
+            raise ValueError(f"{name} has {r} rows, the arrays before it {rows}")
+        rows = r
+        setattr(a, name, t.data_ptr() if r else None)
+    return a, (rows or 0)
+
+
+def _stream_handle(stream):
+    """hipStream_t for the C ABI: an int / None-able handle, a torch stream (its cuda_stream), or -- None -- torch's current
+    stream when torch is imported (work then orders itself behind the trainer's), else the default stream."""
+    import sys
+    if stream is None:
+        torch = sys.modules.get("torch")
+        if torch is None or not torch.cuda.is_available():
+            return None
+        stream = torch.cuda.current_stream()
+    return C.c_void_p(int(getattr(stream, "cuda_stream", stream)) or None)
 
 
 class GsError(RuntimeError):
@@ -213,6 +291,26 @@ class Scene:
         h = C.c_void_p()
         _check(lib().gs_scene_from_device_blob(C.c_void_p(ptr), C.c_uint64(n), C.c_int(device), C.byref(h)))
         return cls(h, keepalive)
+
+    @classmethod
+    def from_tensors(cls, means, log_scales, quats, opacity_logits, sh_dc, sh_rest=None, stream=None, device=0):
+        """A scene from a trainer's parameters as they lie on the GPU (gs_scene_from_device_arrays): float32, contiguous device
+        tensors (anything with data_ptr / shape / dtype / is_contiguous / device) -- means (n, 3), log_scales (n, 3), quats
+        (n, 4) w x y z, opacity_logits (n,) or (n, 1), sh_dc (n, 3) or (n, 1, 3), sh_rest (n, k, 3) with k in 0, 3, 8, 15 or
+        None.  Activated on the device, bit for bit as from_records activates; nothing is copied to the host."""
+        a, n = _device_arrays(dict(means=means, log_scales=log_scales, quats=quats, opacity_logits=opacity_logits, sh_dc=sh_dc,
+                                   sh_rest=sh_rest), device, require=True)
+        h = C.c_void_p()
+        _check(lib().gs_scene_from_device_arrays(C.byref(a), C.c_uint64(n), C.c_int(device), _stream_handle(stream), C.byref(h)))
+        return cls(h)
+
+    def update_from_tensors(self, first, means=None, log_scales=None, quats=None, opacity_logits=None, sh_dc=None, sh_rest=None,
+                            stream=None, device=0):
+        """Overwrite Gaussians [first, first + rows) in place from such tensors (gs_scene_update_from_device_arrays); None keeps
+        what the scene holds.  Synchronize every renderer of the scene first."""
+        a, rows = _device_arrays(dict(means=means, log_scales=log_scales, quats=quats, opacity_logits=opacity_logits, sh_dc=sh_dc,
+                                      sh_rest=sh_rest), device, require=False)
+        _check(lib().gs_scene_update_from_device_arrays(self._h, C.byref(a), C.c_uint64(first), C.c_uint64(rows), _stream_handle(stream)))
 
     @property
     def num_vertices(self):

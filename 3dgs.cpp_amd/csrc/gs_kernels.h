@@ -117,6 +117,11 @@ void launch_permute_blob(const float* src, const uint32_t* perm, float* dst, uin
 void launch_blob_checksum(const float* blob, uint64_t floats, uint64_t* out, hipStream_t s);
 // fp32 SH block of the blob -> binary16 (round to nearest even), n x 48 values
 void launch_sh_to_half(const float* blob, uint16_t* sh16, uint32_t n, uint32_t stride, hipStream_t s);
+// Gaussians [first, first + count) of the blob from a trainer's device arrays (row i of each array = Gaussian first + i), activated as
+// gs::host::activate_record activates a PLY record, bit for bit; a null member leaves what the blob holds (gs3d_hip.h: gs_device_arrays).
+// replace_rest: the SH bands above the DC term are written -- from sh_rest, zero beyond sh_rest_coeffs (0: all zero, sh_rest not read)
+void launch_ingest_arrays(const gs_device_arrays& a, float* blob, uint32_t stride, uint32_t first, uint32_t count, bool replace_rest,
+                          hipStream_t s);
 // counters (nullable): the kernel clears the frame's counters, so that a frame needs no memset node.
 // fp (nullable, device memory): read the uniforms / output pointers from it instead of the arguments (graph replay)
 // stamps (nullable, device memory, [ST_COUNT]): the frame's timeline, see FrameStamp

@@ -157,4 +157,129 @@ void launch_cov3d(const float* blob, float* cov3d, uint32_t n, uint32_t stride, 
     if (n == 0) return;
     hipLaunchKernelGGL(k_cov3d, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, blob, cov3d, n, stride);
 }
+
+// ---------------------------------------------------------------------------------------
+// A trainer's device arrays -> the blob (gs_scene_from_device_arrays / gs_scene_update_from_device_arrays): GSScene::load's
+// per-record conversion (GSScene.cpp:42-55, gs_host_math.h: activate_record) on the device, bit for bit.
+// ---------------------------------------------------------------------------------------
+// libm's expf on the WHOLE domain: gs_expf_libm_full (x <= 0, with glibc's underflow branch) continued to x > 0.  The general
+// path's sequence equals libm on every binary32 in [0, 0x42B17218] (oracle: expf_device_mismatches, tests/test_device_arrays_api.py)
+// but not above it, where glibc leaves through its overflow branch (e_expf.c: x > 0x1.62e42ep6f -> __math_oflowf): stated here.
+// NaN falls through both comparisons and comes out of the sequence as NaN.
+__device__ __forceinline__ float gs_expf_libm_domain(float x, const uint2* __restrict__ tab) {
+    return x > 0x1.62e42ep6f ? __uint_as_float(0x7F800000u) : gs_expf_libm_full(x, tab);
+}
+
+// One workgroup takes BLOCK consecutive Gaussians of the range: Gaussian i of the arrays is Gaussian first + i of the scene.
+//   * the [n][3] / [n][4] arrays are read as the runs of floats they are (lane-contiguous: the sources are only 4-byte
+//     aligned) into LDS and picked up per Gaussian -- a stride of 3 dwords is conflict-free on 32 banks, the quaternion is one
+//     16-byte ds_read_b128 per lane (contiguous, conflict-free; four ds_read_b32 at stride 4 would be 4-way);
+//   * the planes are written lane-contiguous;
+//   * the SH rows (192 bytes, 16-byte aligned in the blob) are written as whole 16-byte stores from scalar loads: float f of
+//     row g is dc[g][f] for f < 3, rest[g][f - 3] for f < 3 + 3 k, 0 beyond.  A member that is absent (DC / REST false: an
+//     update that keeps it) is read back from the row itself; without REST only the row's first 16 bytes are touched.
+//     REST with sh_rest_coeffs == 0 writes zeros and never reads sh_rest (degree 0: the pointer may be null).
+// A null plane member (uniform branch) leaves its planes alone.
+template <bool DC, bool REST>
+__device__ __forceinline__ void ingest_sh_rows(const gs_device_arrays& a, float* __restrict__ sh_rows, uint32_t g0, uint32_t count) {
+    const uint32_t in_block = min((uint32_t)BLOCK, count - g0);
+    const uint32_t k3 = 3u * a.sh_rest_coeffs;
+    const uint32_t chunks = REST ? 12u : 1u;  // 16-byte chunks of a row that change
+    for (uint32_t q = threadIdx.x; q < in_block * chunks; q += BLOCK) {
+        const uint32_t gl = q / chunks, c = q - gl * chunks;
+        const size_t g = (size_t)g0 + gl;
+        float* row = sh_rows + g * 48u;
+        float v[4];
+#pragma unroll
+        for (uint32_t i = 0; i < 4; ++i) {
+            const uint32_t f = 4u * c + i;
+            if (f < 3u) v[i] = DC ? a.sh_dc[g * 3u + f] : row[f];
+            else if (REST) v[i] = f - 3u < k3 ? a.sh_rest[g * k3 + (f - 3u)] : 0.0f;
+            else v[i] = row[f];
+        }
+        reinterpret_cast<float4*>(row)[c] = make_float4(v[0], v[1], v[2], v[3]);
+    }
+}
+
+template <bool DC, bool REST>
+__global__ __launch_bounds__(BLOCK) void k_ingest_arrays(gs_device_arrays a, float* __restrict__ blob, uint32_t stride, uint32_t first,
+                                                         uint32_t count) {
+    __shared__ float s_pos[3 * BLOCK], s_scale[3 * BLOCK];
+    __shared__ __attribute__((aligned(16))) float s_rot[4 * BLOCK];
+    const uint32_t g0 = blockIdx.x * BLOCK, t = threadIdx.x, i = g0 + t;  // g0 < count: the grid covers the range
+    const size_t N = stride;
+    const uint32_t left = count - g0;  // Gaussians from g0 on; the block holds min(BLOCK, left) of them
+    for (uint32_t k = 0; k < 4; ++k) {
+        const uint32_t j = k * BLOCK + t;
+        if (k < 3 && a.means && j < 3ull * left) s_pos[j] = a.means[(size_t)g0 * 3 + j];
+        if (k < 3 && a.log_scales && j < 3ull * left) s_scale[j] = a.log_scales[(size_t)g0 * 3 + j];
+        if (a.quats && j < 4ull * left) s_rot[j] = a.quats[(size_t)g0 * 4 + j];
+    }
+    __syncthreads();
+    if (i < count) {
+        const uint2* tab = reinterpret_cast<const uint2*>(kExpfTab);
+        float* out = blob + first + i;
+        if (a.means) {
+            for (int k = 0; k < 3; ++k) out[(P_POS + k) * N] = s_pos[3 * t + k];
+        }
+        if (a.log_scales) {
+            for (int k = 0; k < 3; ++k) out[(P_SCALE + k) * N] = gs_expf_libm_domain(s_scale[3 * t + k], tab);
+        }
+        if (a.quats) {
+            const float4 q = reinterpret_cast<const float4*>(s_rot)[t];
+            // glm::normalize(vec4): v * inversesqrt(dot(v, v)), dot<4> = (x*x + y*y) + (z*z + w*w)  (activate_record)
+            const float dot = (q.x * q.x + q.y * q.y) + (q.z * q.z + q.w * q.w);
+            const float inv = 1.0f / sqrtf(dot);  // both correctly rounded (hipcc's default; no fast-math in this build)
+            out[(P_ROT + 0) * N] = q.x * inv;
+            out[(P_ROT + 1) * N] = q.y * inv;
+            out[(P_ROT + 2) * N] = q.z * inv;
+            out[(P_ROT + 3) * N] = q.w * inv;
+        }
+        if (a.opacity_logits) out[P_OPACITY * N] = 1.0f / (1.0f + gs_expf_libm_domain(-a.opacity_logits[i], tab));
+    }
+    if (DC || REST) ingest_sh_rows<DC, REST>(a, blob + (size_t)P_SH * N + (size_t)first * 48u, g0, count);
+}
+
+void launch_ingest_arrays(const gs_device_arrays& a, float* blob, uint32_t stride, uint32_t first, uint32_t count, bool replace_rest,
+                          hipStream_t s) {
+    if (count == 0) return;
+    const dim3 grid((count + BLOCK - 1) / BLOCK), block(BLOCK);
+    if (a.sh_dc && replace_rest) hipLaunchKernelGGL((k_ingest_arrays<true, true>), grid, block, 0, s, a, blob, stride, first, count);
+    else if (a.sh_dc) hipLaunchKernelGGL((k_ingest_arrays<true, false>), grid, block, 0, s, a, blob, stride, first, count);
+    else if (replace_rest) hipLaunchKernelGGL((k_ingest_arrays<false, true>), grid, block, 0, s, a, blob, stride, first, count);
+    else hipLaunchKernelGGL((k_ingest_arrays<false, false>), grid, block, 0, s, a, blob, stride, first, count);
+}
+
+// ---- test hook: gs_expf_libm_domain over ranges of binary32 bit patterns, checksummed per block of 2^20 exactly as
+// gs_debug_expf_scan does for the blend's function (tests/test_gpu_device_arrays.py)
+__global__ __launch_bounds__(BLOCK) void k_activation_expf_scan(uint32_t first_bits, uint64_t count, unsigned long long* __restrict__ block_sums) {
+    const uint64_t base = (uint64_t)blockIdx.x << 20;
+    unsigned long long sum = 0;
+    for (uint32_t j = threadIdx.x; j < (1u << 20); j += BLOCK) {
+        const uint64_t at = base + j;
+        if (at >= count) break;
+        const uint32_t xb = first_bits + (uint32_t)at;
+        const float y = gs_expf_libm_domain(__uint_as_float(xb), reinterpret_cast<const uint2*>(kExpfTab));
+        sum += (unsigned long long)__float_as_uint(y) * (unsigned long long)((xb * 0x9E3779B1u) | 1u);
+    }
+    for (int d = 32; d >= 1; d >>= 1) sum += __shfl_xor(sum, d, WAVE);
+    if ((threadIdx.x & (WAVE - 1)) == 0) atomicAdd(&block_sums[blockIdx.x], sum);
+}
+
+extern "C" int gs_debug_activation_expf_scan(int device, uint32_t first_bits, uint64_t count, uint64_t* block_sums, uint64_t blocks_capacity) {
+    const uint64_t blocks = (count + (1u << 20) - 1) >> 20;
+    if (blocks == 0 || blocks > blocks_capacity || !block_sums || blocks > 0x7FFFFFFFull) return GS_ERR_INVALID;
+    if (hipSetDevice(device) != hipSuccess) return GS_ERR_DEVICE;
+    unsigned long long* d = nullptr;
+    if (hipMalloc(reinterpret_cast<void**>(&d), blocks * sizeof(unsigned long long)) != hipSuccess) return GS_ERR_NOMEM;
+    int rc = GS_OK;
+    if (hipMemset(d, 0, blocks * sizeof(unsigned long long)) != hipSuccess) rc = GS_ERR_DEVICE;
+    if (rc == GS_OK) {
+        hipLaunchKernelGGL(k_activation_expf_scan, dim3((uint32_t)blocks), dim3(BLOCK), 0, nullptr, first_bits, count, d);
+        if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) rc = GS_ERR_DEVICE;
+    }
+    if (rc == GS_OK && hipMemcpy(block_sums, d, blocks * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess) rc = GS_ERR_DEVICE;
+    (void)hipFree(d);
+    return rc;
+}
 }  // namespace gs

@@ -108,9 +108,87 @@ void activate_and_upload(gs_scene* s, const float* records, uint64_t n) {
     upload_vertices(s, verts.data(), n);
 }
 
+// What gs_scene_from_device_arrays / gs_scene_update_from_device_arrays refuse before any device is touched.
+// `build`: every member is required (sh_rest only with sh_rest_coeffs != 0); otherwise a null member means "keep".
+void check_device_arrays(const gs_device_arrays* a, uint64_t rows, bool build) {
+    if (!a) throw Error(GS_ERR_INVALID, "null argument");
+    const uint32_t k = a->sh_rest_coeffs;
+    if (k != 0 && k != 3 && k != 8 && k != 15) throw Error(GS_ERR_INVALID, "sh_rest_coeffs must be 0, 3, 8 or 15 (SH degree 0..3)");
+    const struct {
+        const float* p;
+        const char* name;
+        bool required;
+    } members[6] = {{a->means, "means", true},   {a->log_scales, "log_scales", true}, {a->quats, "quats", true}, {a->opacity_logits, "opacity_logits", true},
+                    {a->sh_dc, "sh_dc", true}, {a->sh_rest, "sh_rest", k != 0}};
+    for (const auto& m : members) {
+        if (build && m.required && !m.p && rows) throw Error(GS_ERR_INVALID, std::string("device array `") + m.name + "` is null");
+        if (reinterpret_cast<uintptr_t>(m.p) % 4 != 0) throw Error(GS_ERR_INVALID, std::string("device array `") + m.name + "` is not 4-byte aligned");
+    }
+}
+
+// gs_scene_update_from_device_arrays: the ingest over the range, then whatever is derived from the members that changed --
+// whole planes, into the buffers the scene's renderers already hold -- all on `stream`, which is synchronised at the end.
+void update_from_device_arrays(gs_scene* s, const gs_device_arrays& a, uint64_t first, uint64_t count, hipStream_t stream) {
+    HIP_CHECK(hipSetDevice(s->device));
+    const uint32_t n = static_cast<uint32_t>(s->n), st = static_cast<uint32_t>(gs::blob_stride(s->n));
+    gs_device_arrays in = a;
+    if (!in.sh_rest) in.sh_rest_coeffs = 0;
+    gs::launch_ingest_arrays(in, s->blob, st, static_cast<uint32_t>(first), static_cast<uint32_t>(count), in.sh_rest != nullptr, stream);
+    if (s->spatial_blob.p) gs::launch_permute_blob(s->blob, s->perm.p, s->spatial_blob.p, n, st, stream);  // the order stays
+    if (a.log_scales || a.quats) gs::launch_cov3d(s->render_blob(), s->cov3d.p, n, st, stream);
+    if (s->sh_half && (a.sh_dc || a.sh_rest)) gs::launch_sh_to_half(s->render_blob(), s->sh16.p, n, st, stream);
+    if (a.opacity_logits) {
+        DevBuf<uint32_t> beyond;
+        beyond.alloc(1);
+        HIP_CHECK(hipMemsetAsync(beyond.p, 0, sizeof(uint32_t), stream));
+        gs::launch_alpha_cut(s->render_blob(), s->acut.p, n, st, beyond.p, stream);
+        HIP_CHECK(hipGetLastError());
+        uint32_t flag = 0;
+        HIP_CHECK(hipMemcpyAsync(&flag, beyond.p, sizeof flag, hipMemcpyDeviceToHost, stream));
+        HIP_CHECK(hipStreamSynchronize(stream));
+        s->unit_opacity = flag == 0;
+    }
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(stream));
+}
+
 }  // namespace gs_host
 
 extern "C" {
+
+int gs_scene_from_device_arrays(const gs_device_arrays* a, uint64_t n, int device, void* stream, gs_scene** out) {
+    return guarded([&] {
+        if (!out) throw Error(GS_ERR_INVALID, "null argument");
+        if (n >= kMaxGaussians) throw Error(GS_ERR_INVALID, "too many Gaussians (limit 2^31)");
+        check_device_arrays(a, n, true);
+        select_device(device);
+        auto s = std::make_unique<gs_scene>();
+        s->device = device;
+        s->n = n;
+        s->owned_blob.alloc(gs::blob_floats(n));
+        s->blob = s->owned_blob.p;
+        const hipStream_t st = static_cast<hipStream_t>(stream);
+        // the planes' padding (up to 15 floats each) is part of the blob that gs_scene_blob hands out and gs_dist broadcasts: zero, as uploaded
+        const size_t stride = gs::blob_stride(n);
+        for (int p = 0; p < gs::P_SH && stride > n; ++p)
+            HIP_CHECK(hipMemsetAsync(s->blob + p * stride + n, 0, (stride - n) * sizeof(float), st));
+        gs::launch_ingest_arrays(*a, s->blob, static_cast<uint32_t>(stride), 0, static_cast<uint32_t>(n), true, st);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipStreamSynchronize(st));
+        s->finish_load();
+        *out = s.release();
+    });
+}
+
+int gs_scene_update_from_device_arrays(gs_scene* s, const gs_device_arrays* a, uint64_t first, uint64_t count, void* stream) {
+    return guarded([&] {
+        check_device_arrays(a, count, false);
+        if (!s) throw Error(GS_ERR_INVALID, "null argument");
+        if (first > s->n || count > s->n - first) throw Error(GS_ERR_INVALID, "Gaussian range out of bounds");
+        if (count == 0 || !(a->means || a->log_scales || a->quats || a->opacity_logits || a->sh_dc || a->sh_rest)) return;
+        update_from_device_arrays(s, *a, first, count, static_cast<hipStream_t>(stream));
+    });
+}
 
 int gs_activate_records(const float* records, uint64_t n, float* vertices) {
     return guarded([&] {

@@ -137,6 +137,43 @@ int gs_scene_from_device_blob(float* d_blob, uint64_t n, int device, gs_scene** 
 uint64_t gs_scene_blob_floats(uint64_t n);
 int gs_scene_blob(const gs_scene* s, float** d_blob, uint64_t* floats);
 
+/* A trainer's model as it lies in HBM: six dense fp32 arrays of n rows each, the layout of the Inria trainer's parameters
+ * (_xyz, _scaling, _rotation, _opacity, _features_dc (N,1,3), _features_rest (N,15,3)) and of gsplat's (means, scales, quats,
+ * opacities, sh0, shN).  Device pointers on the scene's device, 4-byte aligned and nothing more (a slice of a larger tensor
+ * is a legal argument).  The values are PLY-domain, i.e. not yet activated. */
+typedef struct {
+    const float* means;           /* [n][3]                                   */
+    const float* log_scales;      /* [n][3]   exp() is applied here           */
+    const float* quats;           /* [n][4]   w x y z, raw; normalised here   */
+    const float* opacity_logits;  /* [n]      sigmoid is applied here         */
+    const float* sh_dc;           /* [n][3]                                   */
+    const float* sh_rest;         /* [n][sh_rest_coeffs][3], RGB innermost    */
+    uint32_t     sh_rest_coeffs;  /* 0, 3, 8 or 15 (SH degree 0..3)           */
+} gs_device_arrays;
+
+/* GSScene::load's conversion loop and upload (GSScene.cpp:36-61) with the data ALREADY ON THE DEVICE: one kernel applies
+ * exp / sigmoid / normalize and lays the six arrays out as the scene's blob, device to device, then the load-time passes of
+ * every other way in run unchanged (cov3D, the alpha cuts, for large scenes the copy in spatial order).  No host copy of the
+ * model, no PCIe transfer.  The scene is BIT FOR BIT the one gs_scene_from_records builds from the same numbers (exp is
+ * libm's expf restated, division and square root are IEEE; a NaN stays a NaN, its sign and payload are the device's).
+ * SH bands beyond sh_rest_coeffs are zero; sh_rest may be NULL only with sh_rest_coeffs == 0; every other member is required.
+ * stream: a hipStream_t (NULL: the default stream).  The ingest is enqueued on it, behind whatever the caller has enqueued
+ * there (the trainer's optimiser step); the call returns after synchronising it.  The arrays are not referenced afterwards.
+ * GS_ERR_INVALID: a null argument, n >= 2^31, sh_rest_coeffs not in {0, 3, 8, 15}, a misaligned pointer. */
+int gs_scene_from_device_arrays(const gs_device_arrays* a, uint64_t n, int device, void* stream, gs_scene** out);
+/* Overwrite Gaussians [first, first + count) of a scene of ANY origin from such arrays (row i = Gaussian first + i), in
+ * place: the live view of a training run.  The Gaussian count is fixed (after densification: a new scene and a new
+ * renderer).  A NULL member means "keep what the scene holds"; sh_rest == NULL keeps the higher bands whatever
+ * sh_rest_coeffs says, a non-NULL sh_rest replaces all of them (zero beyond sh_rest_coeffs).  count == 0 or no member at
+ * all: a successful no-op.  Everything derived from what changed is redone on `stream` before the call returns (it
+ * synchronises the stream): cov3D, the alpha cuts and the opacity flag behind exp mode 3, the binary16 SH block of a
+ * quantised scene, the copy in spatial order.  The ORDER of that copy is not recomputed: it is the order of the positions
+ * the scene was built with, a matter of speed only (frames are identical in any order); a model that has moved far is
+ * better served by a new scene.  No device pointer a renderer holds changes, so the scene's renderers -- captured graphs
+ * included -- go on working.  The frames they have in flight read the scene while they run: call gs_synchronize on EVERY
+ * renderer of the scene first; a frame that straddles the update reads a mixture of both states. */
+int gs_scene_update_from_device_arrays(gs_scene* s, const gs_device_arrays* a, uint64_t first, uint64_t count, void* stream);
+
 /* GSScene::getNumVertices (GSScene.h:37-39). */
 uint64_t gs_scene_num_vertices(const gs_scene* s);
 /* Opt-in storage quantisation (no reference counterpart; the reference keeps fp32 SH, GSScene.h:41-46): the 48 SH
@@ -297,6 +334,10 @@ int gs_debug_download(gs_renderer* r, int stage, void* dst, uint64_t bytes);
  * [0] max over x in [-16, 0] of |v_exp_f32(fl(x log2e)) - expf(x)| / expf(x) - E1 |x|, [1] the same ratio's max over [-1, 0],
  * [2] the guard's E0 (must exceed [0] + 2^-23), [3] its E1. */
 int gs_debug_expf_scan(int device, uint32_t first_bits, uint64_t count, uint64_t* block_sums, uint64_t blocks_capacity, double* guard);
+/* Test hook (tests/test_gpu_device_arrays.py): the same checksums (block_sums[j] as defined above) of the exp() that
+ * gs_scene_from_device_arrays activates scales and opacities with -- libm's expf on the whole domain: the function above
+ * with glibc's overflow branch (x > 88.7228 -> +inf) in front -- so that the positive half is pinned on the device too. */
+int gs_debug_activation_expf_scan(int device, uint32_t first_bits, uint64_t count, uint64_t* block_sums, uint64_t blocks_capacity);
 /* Test hook (tests/test_gpu_antialiased.py): for every opacity with bit pattern in [first_bits, first_bits + count), compare ON
  * THE DEVICE the per-frame alpha cut of the antialiased mode with the load-time one (the full bisection); *mismatches = how
  * many differ, *first_mismatch = the lowest such pattern (0xFFFFFFFF if none). */

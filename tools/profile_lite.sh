@@ -17,6 +17,8 @@ cd /tmp && export TMPDIR=/tmp
 # counter passes: enough untimed frames ahead of the three counted ones that the renderer has settled -- the depth-order level (config C
 # refines its bins and steps down to k_bin_fast<12> on the first clean frame), and the blend's lockstep, which it measures over 55 to 125 frames
 PW=${GS_PROFILE_WARM:-200}
+# a step that fails -- a fault, a hang cut off by its time limit -- ends the collection: nothing more is started on that GPU
+step() { timeout -k 10 120 "$@" > /dev/null 2>&1; local rc=$?; [ $rc -eq 0 ] || { echo "step failed (exit $rc): $*"; exit $rc; }; }
 PMC="SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_VALU SQ_WAIT_ANY"
 for W in $WL; do
   case $W in
@@ -32,20 +34,21 @@ for W in $WL; do
   # The blend's lockstep is the renderer's own choice, measured over its first 60-130 frames -- frames a profiler would average into every
   # kernel's row.  One unprofiled run reads the choice (three in flight, as shipped); the profiled runs below are PINNED to it.
   unset GS_BLEND_LOCKSTEP
-  LS=$(timeout 120 $D --fif 3 --frames 200 2> /dev/null | grep "^fif" | tail -1 | grep -o "lockstep [A-Za-z]*" | cut -d" " -f2)
+  timeout -k 10 120 $D --fif 3 --frames 200 > "$O/unprofiled.txt" 2> /dev/null || { echo "step failed (exit $?): the unprofiled run of $W"; exit 1; }
+  LS=$(grep "^fif" "$O/unprofiled.txt" | tail -1 | grep -o "lockstep [A-Za-z]*" | cut -d" " -f2)
   case "$LS" in True) export GS_BLEND_LOCKSTEP=1;; False) export GS_BLEND_LOCKSTEP=0;; *) unset GS_BLEND_LOCKSTEP;; esac
   echo "${LS:-unknown}" > "$O/lockstep.txt"
-  timeout 120 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/serial" -o s -- $D --fif 1 --frames $FR --warm $PW --json-out "$O/serial/bench.json" > /dev/null 2>&1
-  timeout 120 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/default" -o d -- $D --fif 3 --frames $FR --warm $PW --json-out "$O/default/bench.json" > /dev/null 2>&1
-  timeout 120 rocprofv3 --kernel-trace --pmc $PMC --output-format csv -d "$O/pmc" -o p -- $D --fif 1 --frames 3 --warm $PW > /dev/null 2>&1
-  timeout 120 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d "$O/fetch" -o f -- $D --fif 1 --frames 3 --warm $PW > /dev/null 2>&1
-  timeout 120 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d "$O/write" -o w -- $D --fif 1 --frames 3 --warm $PW > /dev/null 2>&1
+  step rocprofv3 --kernel-trace --stats --output-format csv -d "$O/serial" -o s -- $D --fif 1 --frames $FR --warm $PW --json-out "$O/serial/bench.json"
+  step rocprofv3 --kernel-trace --stats --output-format csv -d "$O/default" -o d -- $D --fif 3 --frames $FR --warm $PW --json-out "$O/default/bench.json"
+  step rocprofv3 --kernel-trace --pmc $PMC --output-format csv -d "$O/pmc" -o p -- $D --fif 1 --frames 3 --warm $PW
+  step rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d "$O/fetch" -o f -- $D --fif 1 --frames 3 --warm $PW
+  step rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d "$O/write" -o w -- $D --fif 1 --frames 3 --warm $PW
   if [ "$W" = "B" ]; then  # the other blend modes' counters as well: exact (exp mode 2), unguarded v_exp_f32, and the opt-in fast blend
     mkdir -p "$O"/pmc_exact "$O"/pmc_hw "$O"/pmc_fast "$O"/serial_exact
-    timeout 120 rocprofv3 --kernel-trace --pmc $PMC --output-format csv -d "$O/pmc_exact" -o p -- $D --fif 1 --frames 3 --warm $PW --exp-mode 2 > /dev/null 2>&1
-    timeout 120 rocprofv3 --kernel-trace --pmc $PMC --output-format csv -d "$O/pmc_hw" -o p -- $D --fif 1 --frames 3 --warm $PW --exp-mode 1 > /dev/null 2>&1
-    timeout 120 rocprofv3 --kernel-trace --pmc $PMC --output-format csv -d "$O/pmc_fast" -o p -- $D --fif 1 --frames 3 --warm $PW --exp-mode 0 --contract 1 > /dev/null 2>&1
-    timeout 120 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/serial_exact" -o s -- $D --fif 1 --frames $FR --warm $PW --exp-mode 2 --json-out "$O/serial_exact/bench.json" > /dev/null 2>&1
+    step rocprofv3 --kernel-trace --pmc $PMC --output-format csv -d "$O/pmc_exact" -o p -- $D --fif 1 --frames 3 --warm $PW --exp-mode 2
+    step rocprofv3 --kernel-trace --pmc $PMC --output-format csv -d "$O/pmc_hw" -o p -- $D --fif 1 --frames 3 --warm $PW --exp-mode 1
+    step rocprofv3 --kernel-trace --pmc $PMC --output-format csv -d "$O/pmc_fast" -o p -- $D --fif 1 --frames 3 --warm $PW --exp-mode 0 --contract 1
+    step rocprofv3 --kernel-trace --stats --output-format csv -d "$O/serial_exact" -o s -- $D --fif 1 --frames $FR --warm $PW --exp-mode 2 --json-out "$O/serial_exact/bench.json"
   fi
 done
 # per-dispatch traces are large; the stats and counter CSVs are what is summarised
