@@ -55,6 +55,7 @@ STAGES = dict(tiles=(0, np.uint32), depth=(1, np.float32), radius=(2, np.float32
 SYMBOLS = ["gs_last_error", "gs_device_count", "gs_read_ply", "gs_activate_records", "gs_scene_load_ply", "gs_scene_from_records",
            "gs_scene_from_vertices", "gs_scene_from_device_blob", "gs_scene_blob_floats", "gs_scene_blob",
            "gs_scene_from_device_arrays", "gs_scene_update_from_device_arrays", "gs_debug_activation_expf_scan",
+           "gs_scene_transform", "gs_transform_sh_matrices", "gs_transform_camera",
            "gs_scene_num_vertices", "gs_scene_quantize_sh", "gs_scene_sh_bits", "gs_scene_download_vertex_range",
            "gs_scene_download_vertices", "gs_scene_download_cov3d",
            "gs_scene_destroy", "gs_renderer_create", "gs_renderer_destroy", "gs_camera_uniforms",
@@ -106,6 +107,19 @@ class DeviceArrays(C.Structure):
     """gs_device_arrays: a trainer's six device arrays (include/gs3d_hip.h)."""
     _fields_ = [("means", C.c_void_p), ("log_scales", C.c_void_p), ("quats", C.c_void_p), ("opacity_logits", C.c_void_p),
                 ("sh_dc", C.c_void_p), ("sh_rest", C.c_void_p), ("sh_rest_coeffs", C.c_uint32)]
+
+
+class Transform(C.Structure):
+    """gs_transform: x -> scale * R(rotation) x + translation (include/gs3d_hip.h)."""
+    _fields_ = [("rotation", C.c_float * 4), ("translation", C.c_float * 3), ("scale", C.c_float)]
+
+
+def _transform(rotation, translation, scale):
+    t = Transform()
+    t.rotation[:] = [float(v) for v in rotation]
+    t.translation[:] = [float(v) for v in translation]
+    t.scale = float(scale)
+    return t
 
 
 def _tensor_rows(name, t, trailing, device):
@@ -241,6 +255,23 @@ def camera_uniforms(cam, width, height):
     return out
 
 
+def transform_camera(cam, rotation=(1, 0, 0, 0), translation=(0, 0, 0), scale=1.0):
+    """The camera that sees a scene moved by Scene.transform(rotation, translation, scale) exactly as `cam` saw it before
+    (gs_transform_camera; host only)."""
+    t, out = _transform(rotation, translation, scale), np.zeros(1, CAMERA_DT)
+    cam = np.ascontiguousarray(cam, CAMERA_DT)
+    _check(lib().gs_transform_camera(C.byref(t), _p(cam), _p(out)))
+    return out
+
+
+def sh_rotation_matrices(rotation=(1, 0, 0, 0)):
+    """The matrices that rotate the SH bands 1, 2, 3 with the quaternion (w, x, y, z): float32 arrays of shape (3, 3), (5, 5),
+    (7, 7), c' = M @ c over a band's coefficients of one channel (gs_transform_sh_matrices; host only)."""
+    t, out = _transform(rotation, (0, 0, 0), 1.0), np.zeros(83, np.float32)
+    _check(lib().gs_transform_sh_matrices(C.byref(t), _p(out)))
+    return out[0:9].reshape(3, 3).copy(), out[9:34].reshape(5, 5).copy(), out[34:83].reshape(7, 7).copy()
+
+
 def activate_records(records):
     """GSScene::load's record conversion on the host (no GPU needed): (n, 62) -> (n, 60)."""
     records = np.ascontiguousarray(records, np.float32).reshape(-1, RECORD_FLOATS)
@@ -311,6 +342,15 @@ class Scene:
         a, rows = _device_arrays(dict(means=means, log_scales=log_scales, quats=quats, opacity_logits=opacity_logits, sh_dc=sh_dc,
                                       sh_rest=sh_rest), device, require=False)
         _check(lib().gs_scene_update_from_device_arrays(self._h, C.byref(a), C.c_uint64(first), C.c_uint64(rows), _stream_handle(stream)))
+
+    def transform(self, rotation=(1, 0, 0, 0), translation=(0, 0, 0), scale=1.0, first=0, count=None, stream=None):
+        """Move Gaussians [first, first + count) (count None: to the end) by x -> scale * R(rotation) x + translation, in place
+        on the device: positions, scales, rotations and the SH bands, rotated with the splats (gs_scene_transform).
+        rotation: quaternion (w, x, y, z), normalised by the library.  Synchronize every renderer of the scene first."""
+        t = _transform(rotation, translation, scale)
+        if count is None:
+            count = max(0, self.num_vertices - int(first))
+        _check(lib().gs_scene_transform(self._h, C.byref(t), C.c_uint64(first), C.c_uint64(count), _stream_handle(stream)))
 
     @property
     def num_vertices(self):

@@ -106,7 +106,8 @@ struct FrameParams {
 constexpr int kBinSortMax = 16384;  // the largest in-LDS order (gs_levels.h: kBinSortLimit[3])
 constexpr uint32_t kSlabDescBytes = 288, kSlabCapacity = 8192, kSlabWorkGroups = 512, kQueueWorkGroups = 256;
 
-void launch_cov3d(const float* blob, float* cov3d, uint32_t n, uint32_t stride, hipStream_t s);
+// cov3D of Gaussians [first, first + count) of the blob (6 planes of n floats; the other Gaussians' values stay)
+void launch_cov3d(const float* blob, float* cov3d, uint32_t n, uint32_t stride, uint32_t first, uint32_t count, hipStream_t s);
 // cut[i] = the most negative power <= 0 with !(min(0.99, opacity[i] * expf(power)) < 1/255)  (render.comp:77-78; +inf: none,
 // -inf: all), exact for libm's expf: the blend compares `power` with it instead of alpha with 1/255 (gs_device.h: alpha_cut)
 // *beyond_unit (device memory, nullable, zeroed by the caller): set to 1 if any opacity exceeds 1
@@ -115,13 +116,24 @@ void launch_alpha_cut(const float* blob, float* cut, uint32_t n, uint32_t stride
 void launch_permute_blob(const float* src, const uint32_t* perm, float* dst, uint32_t n, uint32_t stride, hipStream_t s);
 // *out (device) = sum of the blob's 32-bit patterns, as 64-bit integers (wrapping): what gs_dist_verify compares across ranks
 void launch_blob_checksum(const float* blob, uint64_t floats, uint64_t* out, hipStream_t s);
-// fp32 SH block of the blob -> binary16 (round to nearest even), n x 48 values
-void launch_sh_to_half(const float* blob, uint16_t* sh16, uint32_t n, uint32_t stride, hipStream_t s);
+// fp32 SH block of the blob -> binary16 (round to nearest even): the 48 values of each Gaussian in [first, first + count)
+void launch_sh_to_half(const float* blob, uint16_t* sh16, uint32_t stride, uint32_t first, uint32_t count, hipStream_t s);
 // Gaussians [first, first + count) of the blob from a trainer's device arrays (row i of each array = Gaussian first + i), activated as
 // gs::host::activate_record activates a PLY record, bit for bit; a null member leaves what the blob holds (gs3d_hip.h: gs_device_arrays).
 // replace_rest: the SH bands above the DC term are written -- from sh_rest, zero beyond sh_rest_coeffs (0: all zero, sh_rest not read)
 void launch_ingest_arrays(const gs_device_arrays& a, float* blob, uint32_t stride, uint32_t first, uint32_t count, bool replace_rest,
                           hipStream_t s);
+// gs_scene_transform: what k_scene_transform takes from the host (gs_sh_rotation.h: everything computed in binary64 and rounded
+// once), all of it wave-uniform.  x -> s R x + t; q = the normalised rotation; M = the SH band matrices M_1, M_2, M_3, row-major.
+struct SceneTransform {
+    float R[9];  // row-major
+    float t[3];
+    float s;
+    float q[4];  // w x y z
+    float M[9 + 25 + 49];
+};
+// Gaussians [first, first + count) of the blob moved by x, in place: positions, scales, rotations, SH bands 1..3 (gs3d_hip.h)
+void launch_scene_transform(const SceneTransform& x, float* blob, uint32_t stride, uint32_t first, uint32_t count, hipStream_t s);
 // counters (nullable): the kernel clears the frame's counters, so that a frame needs no memset node.
 // fp (nullable, device memory): read the uniforms / output pointers from it instead of the arguments (graph replay)
 // stamps (nullable, device memory, [ST_COUNT]): the frame's timeline, see FrameStamp

@@ -27,9 +27,10 @@ __device__ __forceinline__ M3 rotation_from_quaternion(float qw, float qx, float
 }
 
 __global__ __launch_bounds__(BLOCK) void k_cov3d(const float* __restrict__ blob, float* __restrict__ cov3d,
-                                                 uint32_t n, uint32_t stride) {
+                                                 uint32_t n, uint32_t stride, uint32_t first, uint32_t count) {
     uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= n) return;
+    if (i >= count) return;
+    i += first;  // < n: the caller's range lies inside the scene
     const size_t N = stride, NC = n;
     const float scale_factor = 1.0f;  // GSScene.cpp:176
     M3 S = {};
@@ -53,11 +54,11 @@ __global__ __launch_bounds__(BLOCK) void k_sh_to_half(const float* __restrict__ 
     const uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
     if (i < count) out[i] = __half_as_ushort(__float2half_rn(sh[i]));
 }
-void launch_sh_to_half(const float* blob, uint16_t* sh16, uint32_t n, uint32_t stride, hipStream_t s) {
-    if (n == 0) return;
-    const uint64_t count = 48ull * n;
-    hipLaunchKernelGGL(k_sh_to_half, dim3((uint32_t)((count + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s,
-                       blob + (size_t)P_SH * stride, sh16, count);
+void launch_sh_to_half(const float* blob, uint16_t* sh16, uint32_t stride, uint32_t first, uint32_t count, hipStream_t s) {
+    if (count == 0) return;
+    const uint64_t values = 48ull * count, at = 48ull * first;
+    hipLaunchKernelGGL(k_sh_to_half, dim3((uint32_t)((values + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s,
+                       blob + (size_t)P_SH * stride + at, sh16 + at, values);
 }
 
 // The alpha cut of every Gaussian (gs_device.h: alpha_cut), a function of its opacity alone: one plane of n floats beside cov3D.
@@ -153,9 +154,9 @@ void launch_blob_checksum(const float* blob, uint64_t floats, uint64_t* out, hip
                        reinterpret_cast<unsigned long long*>(out));
 }
 
-void launch_cov3d(const float* blob, float* cov3d, uint32_t n, uint32_t stride, hipStream_t s) {
-    if (n == 0) return;
-    hipLaunchKernelGGL(k_cov3d, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, blob, cov3d, n, stride);
+void launch_cov3d(const float* blob, float* cov3d, uint32_t n, uint32_t stride, uint32_t first, uint32_t count, hipStream_t s) {
+    if (count == 0) return;
+    hipLaunchKernelGGL(k_cov3d, dim3((count + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, blob, cov3d, n, stride, first, count);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -248,6 +249,116 @@ void launch_ingest_arrays(const gs_device_arrays& a, float* blob, uint32_t strid
     else if (a.sh_dc) hipLaunchKernelGGL((k_ingest_arrays<true, false>), grid, block, 0, s, a, blob, stride, first, count);
     else if (replace_rest) hipLaunchKernelGGL((k_ingest_arrays<false, true>), grid, block, 0, s, a, blob, stride, first, count);
     else hipLaunchKernelGGL((k_ingest_arrays<false, false>), grid, block, 0, s, a, blob, stride, first, count);
+}
+
+// ---------------------------------------------------------------------------------------
+// gs_scene_transform: Gaussians [first, first + count) moved by x -> s R x + t, in place (gs3d_hip.h).  No reference counterpart.
+// ---------------------------------------------------------------------------------------
+// A memory-bound pass: 55 floats in and 55 out per Gaussian (440 B) against ~330 multiply-adds.  One workgroup takes BLOCK
+// consecutive Gaussians of the range; Gaussian i of it is Gaussian first + i of the scene.
+//   * the ten planes (position, scale, rotation) are read and written lane-contiguous; the opacity plane is not touched;
+//   * the SH rows (192 bytes each; the range's first one is 16-byte aligned: 192 first) go through LDS: the workgroup's rows
+//     are ONE run of bytes, copied in and out as whole 16-byte accesses, lane-contiguous, while each lane picks up and puts back
+//     its own row as twelve 16-byte LDS accesses.  The LDS row stride is 52 dwords, not 48: at 48 the lanes of a 16-byte
+//     access's group start on only four different bank slots (48 l mod 64 is a multiple of 16), at 52 = 4 x 13 the 16
+//     lanes of a read group (banks mod 64) and the 8 of a write group (banks mod 32) each start on a slot of their own.
+//     The DC term (the row's first three floats) travels through unchanged.  The lane's accesses are volatile so that they STAY
+//     16-byte instructions (the binary holds 13 ds_read_b128 and 13 ds_write_b128: twelve per row, one per copy loop, and no other
+//     LDS instruction).  What conflicts remain are the copy loops' (measured: SQ_LDS_BANK_CONFLICT 80 of SQ_LDS_IDX_ACTIVE's 368
+//     cycles per wave): of consecutive 16-byte pieces, the one that starts a new row lies 4 dwords further on and meets a
+//     neighbour's banks.
+//   * R, s, t, q and the 83 entries of M are kernel arguments, wave-uniform.
+// ARITHMETIC (binary32, -ffp-contract=off: every product and sum below rounded on its own, in this order; the tolerances of
+// tests/test_gpu_scene_transform.py are derived from it):
+//     position'_k = s * ((R_k0 x + R_k1 y) + R_k2 z) + t_k
+//     scale'_k    = s * scale_k
+//     rotation'   = v * (1 / sqrt((v.w v.w + v.x v.x) + (v.y v.y + v.z v.z))),  v = q (x) rotation with each component's four
+//                   products added left to right in the order w x y z of q's components (division and square root IEEE)
+//     c'_i        = (..((M_i0 c_0 + M_i1 c_1) + M_i2 c_2) + ..) + M_i,2l c_2l     per band l and colour channel
+constexpr uint32_t kShRowLds = 52;  // dwords between two Gaussians' SH rows in LDS
+typedef float ShChunk __attribute__((ext_vector_type(4)));  // 16 bytes of a row, as one LDS access
+typedef volatile __attribute__((address_space(3))) ShChunk LdsShChunk;
+
+template <int M_DIM>
+__device__ __forceinline__ void sh_band_rotate(const float* __restrict__ M, const float* in, float* out, int j0) {
+    // coefficients j0 .. j0 + M_DIM - 1 of the three channels: in/out are a Gaussian's 48 floats, sh[3 j + channel]
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch)
+#pragma unroll
+        for (int i = 0; i < M_DIM; ++i) {
+            float acc = M[i * M_DIM] * in[3 * j0 + ch];
+#pragma unroll
+            for (int j = 1; j < M_DIM; ++j) acc = acc + M[i * M_DIM + j] * in[3 * (j0 + j) + ch];
+            out[3 * (j0 + i) + ch] = acc;
+        }
+}
+
+__global__ __launch_bounds__(BLOCK) void k_scene_transform(SceneTransform x, float* blob, uint32_t stride, uint32_t first, uint32_t count) {
+    __shared__ __attribute__((aligned(16))) float s_sh[BLOCK * kShRowLds];
+    const uint32_t g0 = blockIdx.x * BLOCK, t = threadIdx.x, i = g0 + t;  // g0 < count: the grid covers the range
+    const size_t N = stride;
+    const uint32_t chunks = min((uint32_t)BLOCK, count - g0) * 12u;  // 16-byte pieces of the workgroup's rows
+    float4* rows = reinterpret_cast<float4*>(blob + (size_t)P_SH * N + ((size_t)first + g0) * 48u);
+    for (uint32_t q = t; q < chunks; q += BLOCK) {
+        const uint32_t r = q / 12u, c = q - r * 12u;
+        reinterpret_cast<float4*>(s_sh + r * kShRowLds)[c] = rows[q];
+    }
+    if (i < count) {
+        float* p = blob + first + i;
+        const float px = p[(P_POS + 0) * N], py = p[(P_POS + 1) * N], pz = p[(P_POS + 2) * N];
+        const float sx = p[(P_SCALE + 0) * N], sy = p[(P_SCALE + 1) * N], sz = p[(P_SCALE + 2) * N];
+        const float bw = p[(P_ROT + 0) * N], bx = p[(P_ROT + 1) * N], by = p[(P_ROT + 2) * N], bz = p[(P_ROT + 3) * N];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) p[(P_POS + k) * N] = x.s * ((x.R[3 * k] * px + x.R[3 * k + 1] * py) + x.R[3 * k + 2] * pz) + x.t[k];
+        p[(P_SCALE + 0) * N] = x.s * sx;
+        p[(P_SCALE + 1) * N] = x.s * sy;
+        p[(P_SCALE + 2) * N] = x.s * sz;
+        const float aw = x.q[0], ax = x.q[1], ay = x.q[2], az = x.q[3];
+        const float vw = ((aw * bw - ax * bx) - ay * by) - az * bz;
+        const float vx = ((aw * bx + ax * bw) + ay * bz) - az * by;
+        const float vy = ((aw * by - ax * bz) + ay * bw) + az * bx;
+        const float vz = ((aw * bz + ax * by) - ay * bx) + az * bw;
+        const float dot = (vw * vw + vx * vx) + (vy * vy + vz * vz);
+        const float inv = 1.0f / sqrtf(dot);  // both correctly rounded (hipcc's default; no fast-math in this build)
+        p[(P_ROT + 0) * N] = vw * inv;
+        p[(P_ROT + 1) * N] = vx * inv;
+        p[(P_ROT + 2) * N] = vy * inv;
+        p[(P_ROT + 3) * N] = vz * inv;
+    }
+    __syncthreads();
+    if (i < count) {
+        // volatile: each access stays ONE 16-byte ds_read_b128 / ds_write_b128.  Left to itself the compiler drops the DC term's
+        // round trip, starts at dword 3 and emits 45 dwords as ds_read2_b32 / ds_write2_b32 pairs, whose 32-lane groups (banks
+        // mod 32) are 4-way conflicted at this stride.
+        // (the pointer carries the LDS address space itself: a volatile access through a generic pointer is a flat_load)
+        LdsShChunk* row = (LdsShChunk*)(s_sh + t * kShRowLds);
+        float in[48], out[48];
+#pragma unroll
+        for (int c = 0; c < 12; ++c) {
+            const ShChunk v = row[c];
+            in[4 * c] = v.x, in[4 * c + 1] = v.y, in[4 * c + 2] = v.z, in[4 * c + 3] = v.w;
+        }
+        out[0] = in[0], out[1] = in[1], out[2] = in[2];
+        sh_band_rotate<3>(x.M, in, out, 1);
+        sh_band_rotate<5>(x.M + 9, in, out, 4);
+        sh_band_rotate<7>(x.M + 34, in, out, 9);
+#pragma unroll
+        for (int c = 0; c < 12; ++c) {
+            ShChunk v;
+            v.x = out[4 * c], v.y = out[4 * c + 1], v.z = out[4 * c + 2], v.w = out[4 * c + 3];
+            row[c] = v;
+        }
+    }
+    __syncthreads();
+    for (uint32_t q = t; q < chunks; q += BLOCK) {
+        const uint32_t r = q / 12u, c = q - r * 12u;
+        rows[q] = reinterpret_cast<const float4*>(s_sh + r * kShRowLds)[c];
+    }
+}
+
+void launch_scene_transform(const SceneTransform& x, float* blob, uint32_t stride, uint32_t first, uint32_t count, hipStream_t s) {
+    if (count == 0) return;
+    hipLaunchKernelGGL(k_scene_transform, dim3((count + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, x, blob, stride, first, count);
 }
 
 // ---- test hook: gs_expf_libm_domain over ranges of binary32 bit patterns, checksummed per block of 2^20 exactly as

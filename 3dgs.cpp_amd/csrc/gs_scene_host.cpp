@@ -10,6 +10,7 @@
 #include <memory>
 
 #include "gs_internal.h"
+#include "gs_sh_rotation.h"
 
 using namespace gs_host;
 
@@ -28,7 +29,7 @@ void gs_scene::finish_load() {
         if (e.code != GS_ERR_NOMEM) throw;
         drop_spatial_copy();
     }
-    gs::launch_cov3d(render_blob(), cov3d.p, static_cast<uint32_t>(n), static_cast<uint32_t>(gs::blob_stride(n)), nullptr);
+    gs::launch_cov3d(render_blob(), cov3d.p, static_cast<uint32_t>(n), static_cast<uint32_t>(gs::blob_stride(n)), 0, static_cast<uint32_t>(n), nullptr);
     acut.alloc(n);
     DevBuf<uint32_t> beyond;
     beyond.alloc(1);
@@ -71,7 +72,7 @@ void quantize_sh(gs_scene* s) {  // gs_scene_quantize_sh; also run on the receiv
     if (s->sh_half) return;
     HIP_CHECK(hipSetDevice(s->device));
     s->sh16.alloc(48 * static_cast<size_t>(s->n));
-    gs::launch_sh_to_half(s->render_blob(), s->sh16.p, static_cast<uint32_t>(s->n), static_cast<uint32_t>(gs::blob_stride(s->n)), nullptr);
+    gs::launch_sh_to_half(s->render_blob(), s->sh16.p, static_cast<uint32_t>(gs::blob_stride(s->n)), 0, static_cast<uint32_t>(s->n), nullptr);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(nullptr));
     s->sh_half = true;  // read when a frame is enqueued: frames already in flight keep reading the fp32 block, which stays
@@ -135,8 +136,8 @@ void update_from_device_arrays(gs_scene* s, const gs_device_arrays& a, uint64_t 
     if (!in.sh_rest) in.sh_rest_coeffs = 0;
     gs::launch_ingest_arrays(in, s->blob, st, static_cast<uint32_t>(first), static_cast<uint32_t>(count), in.sh_rest != nullptr, stream);
     if (s->spatial_blob.p) gs::launch_permute_blob(s->blob, s->perm.p, s->spatial_blob.p, n, st, stream);  // the order stays
-    if (a.log_scales || a.quats) gs::launch_cov3d(s->render_blob(), s->cov3d.p, n, st, stream);
-    if (s->sh_half && (a.sh_dc || a.sh_rest)) gs::launch_sh_to_half(s->render_blob(), s->sh16.p, n, st, stream);
+    if (a.log_scales || a.quats) gs::launch_cov3d(s->render_blob(), s->cov3d.p, n, st, 0, n, stream);
+    if (s->sh_half && (a.sh_dc || a.sh_rest)) gs::launch_sh_to_half(s->render_blob(), s->sh16.p, st, 0, n, stream);
     if (a.opacity_logits) {
         DevBuf<uint32_t> beyond;
         beyond.alloc(1);
@@ -152,9 +153,61 @@ void update_from_device_arrays(gs_scene* s, const gs_device_arrays& a, uint64_t 
     HIP_CHECK(hipStreamSynchronize(stream));
 }
 
+// gs_scene_transform: the kernel over the range, then what is derived from scales, rotations and SH -- over the range alone
+// when the frames read the blob itself, whole planes when they read the copy in spatial order (a range of the scene is
+// scattered there) -- all on `stream`, which is synchronised at the end.  Opacities stay, so do the alpha cuts.
+void transform_scene(gs_scene* s, const gs_transform& t, uint64_t first, uint64_t count, hipStream_t stream) {
+    HIP_CHECK(hipSetDevice(s->device));
+    const ShRotation r = sh_rotation(t);
+    gs::SceneTransform x;
+    std::memcpy(x.R, r.R, sizeof x.R);
+    std::memcpy(x.t, t.translation, sizeof x.t);
+    x.s = t.scale;
+    std::memcpy(x.q, r.q, sizeof x.q);
+    std::memcpy(x.M, r.M, sizeof x.M);
+    const uint32_t n = static_cast<uint32_t>(s->n), st = static_cast<uint32_t>(gs::blob_stride(s->n));
+    uint32_t f = static_cast<uint32_t>(first), c = static_cast<uint32_t>(count);
+    gs::launch_scene_transform(x, s->blob, st, f, c, stream);
+    if (s->spatial_blob.p) {
+        gs::launch_permute_blob(s->blob, s->perm.p, s->spatial_blob.p, n, st, stream);  // the order stays
+        f = 0, c = n;
+    }
+    gs::launch_cov3d(s->render_blob(), s->cov3d.p, n, st, f, c, stream);
+    if (s->sh_half) gs::launch_sh_to_half(s->render_blob(), s->sh16.p, st, f, c, stream);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(stream));
+}
+
 }  // namespace gs_host
 
 extern "C" {
+
+int gs_scene_transform(gs_scene* s, const gs_transform* t, uint64_t first, uint64_t count, void* stream) {
+    return guarded([&] {
+        if (const char* fault = transform_fault(t)) throw Error(GS_ERR_INVALID, fault);
+        if (!s) throw Error(GS_ERR_INVALID, "null argument");
+        if (first > s->n || count > s->n - first) throw Error(GS_ERR_INVALID, "Gaussian range out of bounds");
+        if (count == 0) return;
+        transform_scene(s, *t, first, count, static_cast<hipStream_t>(stream));
+    });
+}
+
+int gs_transform_sh_matrices(const gs_transform* t, float out[83]) {
+    return guarded([&] {
+        if (const char* fault = transform_fault(t)) throw Error(GS_ERR_INVALID, fault);
+        if (!out) throw Error(GS_ERR_INVALID, "null argument");
+        const ShRotation r = sh_rotation(*t);
+        std::memcpy(out, r.M, sizeof r.M);
+    });
+}
+
+int gs_transform_camera(const gs_transform* t, const gs_camera* in, gs_camera* out) {
+    return guarded([&] {
+        if (const char* fault = transform_fault(t)) throw Error(GS_ERR_INVALID, fault);
+        if (!in || !out) throw Error(GS_ERR_INVALID, "null argument");
+        transform_camera(*t, *in, out);
+    });
+}
 
 int gs_scene_from_device_arrays(const gs_device_arrays* a, uint64_t n, int device, void* stream, gs_scene** out) {
     return guarded([&] {

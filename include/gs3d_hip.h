@@ -174,6 +174,43 @@ int gs_scene_from_device_arrays(const gs_device_arrays* a, uint64_t n, int devic
  * renderer of the scene first; a frame that straddles the update reads a mixture of both states. */
 int gs_scene_update_from_device_arrays(gs_scene* s, const gs_device_arrays* a, uint64_t first, uint64_t count, void* stream);
 
+/* A similarity of the world: x -> scale * R(rotation) x + translation.  No reference counterpart (GSScene only loads). */
+typedef struct {
+    float rotation[4];     /* quaternion w x y z, the convention of gs_camera.rotation; normalised here (binary64) */
+    float translation[3];
+    float scale;           /* uniform, finite, > 0 */
+} gs_transform;
+/* Move Gaussians [first, first + count) of a scene of ANY origin by t, in place and on the device: put a trained scene the
+ * right way up and at the right size, align two captures, let a rigid part of a scene follow an object from frame to frame.
+ * For every Gaussian of the range, with q_R the normalised rotation and R its matrix:
+ *     position' = scale * R position + translation          scales' = scale * scales (the activated ones)
+ *     rotation' = normalize(q_R (x) rotation)               (Hamilton product, q_R on the left; renormalised on every call, so
+ *                                                            that repeated transforms do not let the norm drift)
+ *     SH band l = 1, 2, 3 of each colour channel: c'_l = M_l(R) c_l, where M_l is defined by f'(d) = f(R^T d) for every unit d
+ *     and f is the colour function preprocess evaluates (its basis, signs and coefficient order; sh[3 j + channel]) -- a
+ *     rotated splat whose SH are left alone shows its colours from the wrong side.
+ * Opacity and the SH DC term keep their bits; so does everything outside the range, the planes' padding included.  binary32,
+ * one rounding per operation in the order k_scene_transform (gs_scene.hip) documents; R and M_l are computed in binary64 and
+ * rounded once.  What is derived is redone on `stream` (a hipStream_t, NULL: the default stream; the call is enqueued behind
+ * what the caller has enqueued there and returns after synchronising it): cov3D; the binary16 SH block of a quantised scene;
+ * the copy in spatial order if the scene has one (whole planes then; its ORDER is not recomputed, as in
+ * gs_scene_update_from_device_arrays).  Without that copy every pass covers the range only, so a small range is cheap.  The
+ * alpha cuts stay: opacity does not change.  No device pointer a renderer holds changes: renderers and their captured graphs go
+ * on working.  Frames in flight read the scene while they run: call gs_synchronize on EVERY renderer of the scene first.
+ * count == 0: a successful no-op.  The identity is not special-cased (rotations renormalise).
+ * GS_ERR_INVALID, before a device is selected: a null argument; a scale that is not finite or <= 0; a non-finite translation;
+ * a quaternion that is non-finite or of zero norm; a range out of bounds.
+ * Non-uniform scales and reflections are not similarities of a splat model (neither SH nor the quaternion form carry them). */
+int gs_scene_transform(gs_scene* s, const gs_transform* t, uint64_t first, uint64_t count, void* stream);
+/* Host only, no device: the three band matrices that rotate SH coefficients with R(t->rotation) -- M_1 3 x 3, M_2 5 x 5, M_3 7 x 7,
+ * row-major, back to back: 83 floats (binary64, rounded once).  c'[i] = sum_j M_l[i][j] c[j] over the band's coefficients of
+ * one channel, in the scene's coefficient order.  Translation and scale do not enter (they are validated all the same). */
+int gs_transform_sh_matrices(const gs_transform* t, float out[83]);
+/* Host only: the camera that sees the transformed scene exactly as `in` saw the original -- position scale * R p + translation,
+ * rotation q_R (x) q_cam, near and far planes times scale, fov kept.  Depths of that view are scale times the original's.
+ * in->rotation is used as it is, NOT normalised (gs_camera_uniforms does not normalise it either): the product has its norm. */
+int gs_transform_camera(const gs_transform* t, const gs_camera* in, gs_camera* out);
+
 /* GSScene::getNumVertices (GSScene.h:37-39). */
 uint64_t gs_scene_num_vertices(const gs_scene* s);
 /* Opt-in storage quantisation (no reference counterpart; the reference keeps fp32 SH, GSScene.h:41-46): the 48 SH
