@@ -58,6 +58,7 @@ SYMBOLS = ["gs_last_error", "gs_device_count", "gs_read_ply", "gs_activate_recor
            "gs_scene_transform", "gs_transform_sh_matrices", "gs_transform_camera",
            "gs_scene_num_vertices", "gs_scene_quantize_sh", "gs_scene_sh_bits", "gs_scene_download_vertex_range",
            "gs_scene_download_vertices", "gs_scene_download_cov3d",
+           "gs_deactivate_vertices", "gs_write_ply", "gs_scene_to_device_arrays", "gs_scene_download_records", "gs_scene_save_ply",
            "gs_scene_destroy", "gs_renderer_create", "gs_renderer_destroy", "gs_camera_uniforms",
            "gs_render", "gs_render_host", "gs_synchronize", "gs_set_timing", "gs_set_frames_in_flight", "gs_set_sort_path", "gs_set_exp_mode", "gs_set_graph_mode", "gs_set_blend_lockstep", "gs_get_blend_lockstep", "gs_set_blend_contraction", "gs_set_antialiased", "gs_get_antialiased", "gs_get_timing_totals",
            "gs_get_frame_intervals", "gs_get_stats", "gs_poll_stats", "gs_debug_download", "gs_debug_expf_scan", "gs_debug_alpha_cut_scan", "gs_renderer_stream",
@@ -289,25 +290,43 @@ def read_ply(path):
     return out
 
 
+def deactivate_vertices(vertices):
+    """The inverse of activate_records on the host (no GPU needed): (n, 60) -> (n, 62) PLY records (gs_deactivate_vertices)."""
+    v = np.ascontiguousarray(vertices, np.float32).reshape(-1, VERTEX_FLOATS)
+    out = np.zeros((len(v), RECORD_FLOATS), np.float32)
+    _check(lib().gs_deactivate_vertices(_p(v), C.c_uint64(len(v)), _p(out)))
+    return out
+
+
+def write_ply(path, records):
+    """(n, 62) records as the reference's binary PLY (host only; gs_write_ply)."""
+    records = np.ascontiguousarray(records, np.float32).reshape(-1, RECORD_FLOATS)
+    _check(lib().gs_write_ply(os.fsencode(path), _p(records), C.c_uint64(len(records))))
+
+
+SH_REST_COEFFS = {0: 0, 1: 3, 2: 8, 3: 15}  # SH degree -> coefficients above the DC term
+
+
 class Scene:
     """GSScene counterpart (SoA in HBM)."""
 
-    def __init__(self, handle, keepalive=None):
+    def __init__(self, handle, keepalive=None, device=0):
         self._h = handle
         self._keepalive = keepalive
+        self.device = device
 
     @classmethod
     def load_ply(cls, path, device=0):
         h = C.c_void_p()
         _check(lib().gs_scene_load_ply(os.fsencode(path), C.c_int(device), C.byref(h)))
-        return cls(h)
+        return cls(h, device=device)
 
     @classmethod
     def from_records(cls, records, device=0):
         records = np.ascontiguousarray(records, np.float32).reshape(-1, RECORD_FLOATS)
         h = C.c_void_p()
         _check(lib().gs_scene_from_records(_p(records), C.c_uint64(len(records)), C.c_int(device), C.byref(h)))
-        return cls(h)
+        return cls(h, device=device)
 
     @classmethod
     def from_vertices(cls, vertices, device=0):
@@ -315,13 +334,13 @@ class Scene:
         v = np.ascontiguousarray(vertices).view(np.float32).reshape(-1, VERTEX_FLOATS)
         h = C.c_void_p()
         _check(lib().gs_scene_from_vertices(_p(v), C.c_uint64(len(v)), C.c_int(device), C.byref(h)))
-        return cls(h)
+        return cls(h, device=device)
 
     @classmethod
     def from_device_blob(cls, ptr, n, device=0, keepalive=None):
         h = C.c_void_p()
         _check(lib().gs_scene_from_device_blob(C.c_void_p(ptr), C.c_uint64(n), C.c_int(device), C.byref(h)))
-        return cls(h, keepalive)
+        return cls(h, keepalive, device=device)
 
     @classmethod
     def from_tensors(cls, means, log_scales, quats, opacity_logits, sh_dc, sh_rest=None, stream=None, device=0):
@@ -333,7 +352,7 @@ class Scene:
                                    sh_rest=sh_rest), device, require=True)
         h = C.c_void_p()
         _check(lib().gs_scene_from_device_arrays(C.byref(a), C.c_uint64(n), C.c_int(device), _stream_handle(stream), C.byref(h)))
-        return cls(h)
+        return cls(h, device=device)
 
     def update_from_tensors(self, first, means=None, log_scales=None, quats=None, opacity_logits=None, sh_dc=None, sh_rest=None,
                             stream=None, device=0):
@@ -351,6 +370,47 @@ class Scene:
         if count is None:
             count = max(0, self.num_vertices - int(first))
         _check(lib().gs_scene_transform(self._h, C.byref(t), C.c_uint64(first), C.c_uint64(count), _stream_handle(stream)))
+
+    def to_tensors(self, first=0, count=None, sh_degree=3, stream=None, out=None):
+        """Gaussians [first, first + count) (count None: to the end) as the PLY-domain tensors from_tensors takes, on the scene's
+        device and without a host copy (gs_scene_to_device_arrays): a dict with from_tensors' keyword names -- means (count, 3),
+        log_scales (count, 3), quats (count, 4), opacity_logits (count,), sh_dc (count, 3), sh_rest (count, k, 3) with k = 0, 3,
+        8, 15 for sh_degree 0 .. 3 (higher bands are dropped).  Scales and opacities are the pre-activation values that
+        activate to the stored bits; the rotation is the stored, normalised one.
+        out: a dict of preallocated tensors under those names (float32, contiguous, on the scene's device, `count` rows each,
+        shapes as from_tensors takes them); a name it lacks is not exported, sh_degree is then sh_rest's.  Returns out."""
+        if count is None:
+            count = max(0, self.num_vertices - int(first))
+        if out is None:
+            if sh_degree not in SH_REST_COEFFS:
+                raise ValueError(f"sh_degree must be 0, 1, 2 or 3, not {sh_degree!r}")
+            import torch
+            shapes = dict(means=(count, 3), log_scales=(count, 3), quats=(count, 4), opacity_logits=(count,), sh_dc=(count, 3),
+                          sh_rest=(count, SH_REST_COEFFS[sh_degree], 3))
+            out = {k: torch.empty(shape, dtype=torch.float32, device=f"cuda:{self.device}") for k, shape in shapes.items()}
+        names = ("means", "log_scales", "quats", "opacity_logits", "sh_dc", "sh_rest")
+        unknown = sorted(set(out) - set(names))
+        if unknown:
+            raise TypeError(f"out: unknown member(s) {unknown}")
+        a, rows = _device_arrays({k: out.get(k) for k in names}, self.device, require=False)
+        given = [k for k in names if out.get(k) is not None and not (k == "sh_rest" and a.sh_rest_coeffs == 0)]
+        if given and rows != count:
+            raise ValueError(f"out: the tensors have {rows} rows, the range {count}")
+        _check(lib().gs_scene_to_device_arrays(self._h, C.byref(a), C.c_uint64(first), C.c_uint64(count), _stream_handle(stream)))
+        return out
+
+    def download_records(self, first=0, count=None):
+        """Gaussians [first, first + count) (count None: to the end) as (count, 62) PLY records on the host
+        (gs_scene_download_records): deactivate_vertices(download_vertex_range(first, count)), bit for bit."""
+        if count is None:
+            count = max(0, self.num_vertices - int(first))
+        out = np.zeros((count, RECORD_FLOATS), np.float32)
+        _check(lib().gs_scene_download_records(self._h, C.c_uint64(first), C.c_uint64(count), _p(out)))
+        return out
+
+    def save_ply(self, path):
+        """The scene as the reference's binary PLY, streamed from the device (gs_scene_save_ply)."""
+        _check(lib().gs_scene_save_ply(self._h, os.fsencode(path)))
 
     @property
     def num_vertices(self):

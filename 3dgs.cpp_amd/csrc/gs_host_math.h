@@ -183,6 +183,108 @@ inline void activate_record(const float* r, float* v) {
     }
 }
 
+// ---- the inverse of activate_record (gs_deactivate_vertices; on the device: k_scene_export, gs_scene.hip, bit for bit; in
+// numpy: tests/export_reference.py).  A stored scale s or opacity o is exported as the binary32 x whose activation is closest
+// to it -- on every image of the activation that is the stored bits themselves.  binary64 + - x / only, every operation
+// rounded on its own (-ffp-contract=off), no fma, no libm log:
+//   log64(v), v = m 2^e, m in [1/2, 1):  m < sqrt(1/2) -> m = 2 m, e = e - 1;  t = (m - 1) / (m + 1);  w = t t;
+//       p = 1/17;  p = p w + 1/15;  .. + 1/13, 1/11, 1/9, 1/7, 1/5, 1/3;  p = p w + 1      (each 1/k the binary64 quotient)
+//       log64 = (double)e * ln2 + (2 t) p,  ln2 = 0x1.62e42fefa39efp-1
+//   first guess x0, rounded once to binary32: log64(s);  log64(o / (1 - o)) with o, 1 - o and the quotient in binary64
+//   polish: x0 and its binary32 neighbours at distance 1 .. 4, in the order 0, -1, +1, -2, +2, -3, +3, -4, +4 (stepped across
+//       zero as nextafter steps; a non-finite candidate is skipped), each activated as activate_record activates; the first
+//       with the strictly smallest |(double)act - (double)stored| is the export, a NaN activation never is.  The search stops
+//       at a candidate that reproduces the stored value: distance 0 cannot be beaten, the result is the same.
+//   edges, without polish: s == 0 -> -inf, s == +inf -> +inf, s < 0 or NaN -> NaN;  o == 0 -> -inf, o == 1 -> +inf, o outside
+//       [0, 1] or NaN -> NaN.
+inline double export_log64(double v) {  // v: positive, finite, normal (every binary32 > 0 is, and so is o / (1 - o))
+    uint64_t b;
+    std::memcpy(&b, &v, sizeof b);
+    int e = static_cast<int>((b >> 52) & 0x7FFu) - 1022;
+    b = (b & 0x000FFFFFFFFFFFFFull) | 0x3FE0000000000000ull;
+    double m;
+    std::memcpy(&m, &b, sizeof m);
+    if (m < 0x1.6a09e667f3bcdp-1) {
+        m = 2.0 * m;
+        e = e - 1;
+    }
+    const double t = (m - 1.0) / (m + 1.0), w = t * t;
+    double p = 1.0 / 17.0;
+    p = p * w + 1.0 / 15.0;
+    p = p * w + 1.0 / 13.0;
+    p = p * w + 1.0 / 11.0;
+    p = p * w + 1.0 / 9.0;
+    p = p * w + 1.0 / 7.0;
+    p = p * w + 1.0 / 5.0;
+    p = p * w + 1.0 / 3.0;
+    p = p * w + 1.0;
+    return static_cast<double>(e) * 0x1.62e42fefa39efp-1 + (2.0 * t) * p;
+}
+
+// the binary32 value d steps from x in the order of the reals (+-0 is one value; a step from it lands on a subnormal)
+inline float export_neighbour(float x, int d) {
+    uint32_t b;
+    std::memcpy(&b, &x, sizeof b);
+    int64_t key = (b & 0x80000000u) ? -static_cast<int64_t>(b & 0x7FFFFFFFu) : static_cast<int64_t>(b);
+    key += d;
+    b = key < 0 ? (0x80000000u | static_cast<uint32_t>(-key)) : static_cast<uint32_t>(key);
+    std::memcpy(&x, &b, sizeof x);
+    return x;
+}
+
+template <bool OPACITY>
+inline float export_polish(float x0, float stored) {
+    float best = x0;
+    double best_err = std::numeric_limits<double>::infinity();
+    for (int k = 0; k < 9; ++k) {
+        const float c = export_neighbour(x0, (k & 1) ? -((k + 1) >> 1) : (k >> 1));
+        if (!std::isfinite(c)) continue;
+        const float act = OPACITY ? 1.0f / (1.0f + std::exp(-c)) : std::exp(c);
+        const double diff = static_cast<double>(act) - static_cast<double>(stored);
+        const double err = diff < 0.0 ? -diff : diff;
+        if (err < best_err) best = c, best_err = err;  // (false for a NaN)
+        if (err == 0.0) break;
+    }
+    return best;
+}
+
+inline float export_log_scale(float s) {
+    if (!(s > 0.0f)) return s == 0.0f ? -std::numeric_limits<float>::infinity() : std::numeric_limits<float>::quiet_NaN();
+    if (s == std::numeric_limits<float>::infinity()) return s;
+    return export_polish<false>(static_cast<float>(export_log64(static_cast<double>(s))), s);
+}
+
+inline float export_opacity_logit(float o) {
+    if (o == 0.0f) return -std::numeric_limits<float>::infinity();
+    if (o == 1.0f) return std::numeric_limits<float>::infinity();
+    if (!(o > 0.0f && o < 1.0f)) return std::numeric_limits<float>::quiet_NaN();
+    const double od = static_cast<double>(o), rest = 1.0 - od;
+    return export_polish<true>(static_cast<float>(export_log64(od / rest)), o);
+}
+
+// One activated vertex -> one PLY record.  Positions, the rotation AS STORED (normalised: a reload renormalises it, which may
+// move each component by a few 2^-24 relative; gs3d_hip.h) and the 48 SH coefficients are copies of bits, the normals are 0.
+inline void deactivate_vertex(const float* v, float* r) {
+    r[0] = v[0];
+    r[1] = v[1];
+    r[2] = v[2];
+    r[3] = r[4] = r[5] = 0.0f;
+    const float* in = v + 12;
+    float* shs = r + 6;
+    shs[0] = in[0];
+    shs[1] = in[1];
+    shs[2] = in[2];
+    constexpr int SH_N = 16;
+    for (int j = 1; j < SH_N; ++j) {  // interleaved RGB per coefficient -> planar RRR..GGG..BBB
+        shs[(j - 1) + 3] = in[j * 3 + 0];
+        shs[(j - 1) + SH_N + 2] = in[j * 3 + 1];
+        shs[(j - 1) + SH_N * 2 + 1] = in[j * 3 + 2];
+    }
+    r[54] = export_opacity_logit(v[7]);
+    for (int k = 0; k < 3; ++k) r[55 + k] = export_log_scale(v[4 + k]);
+    for (int k = 0; k < 4; ++k) r[58 + k] = v[8 + k];
+}
+
 // ---- the order the per-frame kernels read a large scene in (gs_scene::make_spatial_copy): ascending Morton code of the
 // position, ties by id.
 //   * per axis the finite coordinates' bounding box [lo, hi] is cut into 2^21 cells: cell = min(2^21 - 1, floor(t 2^21)) with

@@ -15,6 +15,7 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <functional>
 #include <new>
 #include <stdexcept>
 #include <string>
@@ -142,6 +143,10 @@ namespace gs_host {
 void quantize_sh(gs_scene* s);  // gs_scene_quantize_sh; also run on the receiving ranks of a quantised scene's broadcast
 void upload_vertices(gs_scene* s, const float* vertices, uint64_t n);
 void activate_and_upload(gs_scene* s, const float* records, uint64_t n);
+// Gaussians [first, first + count) as 62-float PLY records (gs::launch_scene_export_records), chunk by chunk and in order:
+// sink(records, rows) is handed pinned host memory that holds `rows` records for the duration of the call.  Two device and two
+// pinned buffers of GS_EXPORT_CHUNK records (default 2^18, 65 MB each): chunk c + 1 is produced and copied while c is consumed.
+void export_records_streamed(const gs_scene* s, uint64_t first, uint64_t count, const std::function<void(const float*, uint64_t)>& sink);
 
 // gs_ply.cpp
 std::vector<float> read_ply(const std::string& path, uint64_t* n_out);

@@ -134,6 +134,11 @@ struct SceneTransform {
 };
 // Gaussians [first, first + count) of the blob moved by x, in place: positions, scales, rotations, SH bands 1..3 (gs3d_hip.h)
 void launch_scene_transform(const SceneTransform& x, float* blob, uint32_t stride, uint32_t first, uint32_t count, hipStream_t s);
+// Gaussians [first, first + count) of the blob as PLY-domain values, the inverse of launch_ingest_arrays (gs3d_hip.h:
+// gs_scene_to_device_arrays): into the trainer's arrays (row i = Gaussian first + i; a null member is skipped), or as
+// 62-float PLY records (records[i] = Gaussian first + i).  Nothing of the blob changes.
+void launch_scene_export(const gs_device_arrays_out& a, const float* blob, uint32_t stride, uint32_t first, uint32_t count, hipStream_t s);
+void launch_scene_export_records(float* records, const float* blob, uint32_t stride, uint32_t first, uint32_t count, hipStream_t s);
 // counters (nullable): the kernel clears the frame's counters, so that a frame needs no memset node.
 // fp (nullable, device memory): read the uniforms / output pointers from it instead of the arguments (graph replay)
 // stamps (nullable, device memory, [ST_COUNT]): the frame's timeline, see FrameStamp

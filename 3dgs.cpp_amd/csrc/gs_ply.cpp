@@ -5,6 +5,7 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
+#include <cstdio>
 #include <cstring>
 #include <fstream>
 #include <memory>
@@ -186,6 +187,51 @@ struct MappedPly {
     MappedPly& operator=(const MappedPly&) = delete;
 };
 
+// The reference's PLY, written: the header parse_ply_header calls `standard` and the records as they are.  A file that could
+// not be written whole does not stay: any failure removes it (GS_ERR_IO).
+class PlyWriter {
+public:
+    PlyWriter(const std::string& path, uint64_t n) : path_(path), f_(std::fopen(path.c_str(), "wb")) {
+        if (!f_) throw Error(GS_ERR_IO, "cannot create " + path);
+        std::string h = "ply\nformat binary_little_endian 1.0\nelement vertex " + std::to_string(n) + "\n";
+        for (const char* name : {"x", "y", "z", "nx", "ny", "nz", "f_dc_0", "f_dc_1", "f_dc_2"}) h += std::string("property float ") + name + "\n";
+        for (int k = 0; k < 45; ++k) h += "property float f_rest_" + std::to_string(k) + "\n";
+        h += "property float opacity\n";
+        for (int k = 0; k < 3; ++k) h += "property float scale_" + std::to_string(k) + "\n";
+        for (int k = 0; k < 4; ++k) h += "property float rot_" + std::to_string(k) + "\n";
+        h += "end_header\n";
+        put(h.data(), h.size());
+    }
+    ~PlyWriter() {
+        if (f_) discard();  // not closed: an exception is on its way
+    }
+    PlyWriter(const PlyWriter&) = delete;
+    PlyWriter& operator=(const PlyWriter&) = delete;
+    void records(const float* rec, uint64_t rows) { put(rec, static_cast<size_t>(rows) * gs::host::kRecordFloats * sizeof(float)); }
+    void close() {
+        std::FILE* f = f_;
+        f_ = nullptr;
+        if (std::fclose(f) != 0) {
+            std::remove(path_.c_str());
+            throw Error(GS_ERR_IO, "cannot write " + path_);
+        }
+    }
+
+private:
+    void put(const void* p, size_t bytes) {
+        if (bytes && std::fwrite(p, 1, bytes, f_) != bytes) {
+            discard();
+            throw Error(GS_ERR_IO, "cannot write " + path_);
+        }
+    }
+    void discard() {
+        std::fclose(f_);
+        f_ = nullptr;
+        std::remove(path_.c_str());
+    }
+    std::string path_;
+    std::FILE* f_;
+};
 
 }  // namespace
 
@@ -290,6 +336,24 @@ int gs_read_ply(const char* path, float* records, uint64_t capacity, uint64_t* n
     });
 }
 
+
+int gs_write_ply(const char* path, const float* records, uint64_t n) {
+    return guarded([&] {
+        if (!path || (!records && n)) throw Error(GS_ERR_INVALID, "null argument");
+        PlyWriter w(path, n);
+        w.records(records, n);
+        w.close();
+    });
+}
+
+int gs_scene_save_ply(const gs_scene* s, const char* path) {
+    return guarded([&] {
+        if (!s || !path) throw Error(GS_ERR_INVALID, "null argument");
+        PlyWriter w(path, s->n);
+        export_records_streamed(s, 0, s->n, [&](const float* rec, uint64_t rows) { w.records(rec, rows); });
+        w.close();
+    });
+}
 
 int gs_scene_load_ply(const char* path, int device, gs_scene** out) {
     return guarded([&] {

@@ -361,6 +361,206 @@ void launch_scene_transform(const SceneTransform& x, float* blob, uint32_t strid
     hipLaunchKernelGGL(k_scene_transform, dim3((count + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, x, blob, stride, first, count);
 }
 
+// ---------------------------------------------------------------------------------------
+// Export (gs_scene_to_device_arrays, gs_scene_download_records, gs_scene_save_ply): the blob -> PLY-domain values, the inverse
+// of k_ingest_arrays.  No reference counterpart (GSScene only loads).
+// ---------------------------------------------------------------------------------------
+// THE INVERSE ACTIVATION, bit for bit gs_host_math.h's export_log_scale / export_opacity_logit (tests/export_reference.py
+// restates it in numpy).  ARITHMETIC (binary64 + - x /, -ffp-contract=off: every operation below rounded on its own, in this
+// order; no fma, no library log):
+//     log64(v), v = m 2^e with m in [1/2, 1):   if m < 0x1.6a09e667f3bcdp-1:  m = 2 m, e = e - 1
+//         t = (m - 1) / (m + 1);   w = t t
+//         p = 1/17;  p = p w + 1/15;  p = p w + 1/13;  .. 1/11, 1/9, 1/7, 1/5, 1/3;  p = p w + 1    (1/k: the binary64 quotient)
+//         log64 = (double)e * 0x1.62e42fefa39efp-1 + (2 t) p
+//     x0 = (float)log64(s)   |   x0 = (float)log64(o / (1 - o)),  o, 1 - o and the quotient in binary64
+//     candidates x0 and its binary32 neighbours in the order 0, -1, +1, -2, +2, -3, +3, -4, +4 (non-finite ones skipped), each
+//         activated exactly as k_ingest_arrays activates (gs_expf_libm_domain; 1.0f / (1.0f + exp(-x)));  the export is the first
+//         with the strictly smallest |(double)act - (double)stored|;  a NaN activation never wins.
+//     The loop stops at a candidate whose activation IS the stored value: distance 0 cannot be beaten, so the result is the one
+//     the full window gives, and on images of the activation (every scene that was loaded, not transformed) a scale costs one
+//     exp and an opacity at most five instead of nine each.
+//     s == 0 -> -inf;  s == +inf -> +inf;  s < 0 or NaN -> NaN;   o == 0 -> -inf;  o == 1 -> +inf;  o outside [0, 1] or NaN -> NaN.
+__device__ __forceinline__ double export_log64(double v) {  // v: positive, finite, normal
+    const uint64_t b = (uint64_t)__double_as_longlong(v);
+    int e = (int)((b >> 52) & 0x7FFu) - 1022;
+    double m = __longlong_as_double((long long)((b & 0x000FFFFFFFFFFFFFull) | 0x3FE0000000000000ull));
+    if (m < 0x1.6a09e667f3bcdp-1) {
+        m = 2.0 * m;
+        e = e - 1;
+    }
+    const double t = (m - 1.0) / (m + 1.0), w = t * t;
+    double p = 1.0 / 17.0;
+    p = p * w + 1.0 / 15.0;
+    p = p * w + 1.0 / 13.0;
+    p = p * w + 1.0 / 11.0;
+    p = p * w + 1.0 / 9.0;
+    p = p * w + 1.0 / 7.0;
+    p = p * w + 1.0 / 5.0;
+    p = p * w + 1.0 / 3.0;
+    p = p * w + 1.0;
+    return (double)e * 0x1.62e42fefa39efp-1 + (2.0 * t) * p;
+}
+
+// the binary32 value d steps from x in the order of the reals (+-0 is one value; a step from it lands on a subnormal)
+__device__ __forceinline__ float export_neighbour(float x, int d) {
+    const uint32_t b = __float_as_uint(x);
+    const int64_t key = ((b & 0x80000000u) ? -(int64_t)(b & 0x7FFFFFFFu) : (int64_t)b) + d;
+    return __uint_as_float(key < 0 ? (0x80000000u | (uint32_t)(-key)) : (uint32_t)key);
+}
+
+template <bool OPACITY>
+__device__ __forceinline__ float export_polish(float x0, float stored, const uint2* __restrict__ tab) {
+    float best = x0;
+    double best_err = __longlong_as_double(0x7FF0000000000000ll);
+    for (int k = 0; k < 9; ++k) {
+        const float c = export_neighbour(x0, (k & 1) ? -((k + 1) >> 1) : (k >> 1));
+        if ((__float_as_uint(c) & 0x7F800000u) == 0x7F800000u) continue;
+        const float act = OPACITY ? 1.0f / (1.0f + gs_expf_libm_domain(-c, tab)) : gs_expf_libm_domain(c, tab);
+        const double diff = (double)act - (double)stored;
+        const double err = diff < 0.0 ? -diff : diff;
+        if (err < best_err) best = c, best_err = err;  // (false for a NaN)
+        if (err == 0.0) break;
+    }
+    return best;
+}
+
+__device__ __forceinline__ float export_log_scale(float s, const uint2* __restrict__ tab) {
+    if (!(s > 0.0f)) return __uint_as_float(s == 0.0f ? 0xFF800000u : 0x7FC00000u);
+    if (s == __uint_as_float(0x7F800000u)) return s;
+    return export_polish<false>((float)export_log64((double)s), s, tab);
+}
+
+__device__ __forceinline__ float export_opacity_logit(float o, const uint2* __restrict__ tab) {
+    if (o == 0.0f) return __uint_as_float(0xFF800000u);
+    if (o == 1.0f) return __uint_as_float(0x7F800000u);
+    if (!(o > 0.0f && o < 1.0f)) return __uint_as_float(0x7FC00000u);
+    const double od = (double)o, rest = 1.0 - od;
+    return export_polish<true>((float)export_log64(od / rest), o, tab);
+}
+
+// k_scene_export, the mirror of k_ingest_arrays: one workgroup takes BLOCK consecutive Gaussians of the range; Gaussian i of the
+// output is Gaussian first + i of the scene.  Two output forms over ONE body: the trainer's six arrays (RECORDS false; a null
+// member is a wave-uniform branch that skips its loads and its arithmetic) and 62-float PLY records (RECORDS true).
+//   * the planes are read lane-contiguous; each lane inverts its own Gaussian's three scales and its opacity;
+//   * every packed output -- [n][3], [n][4], [n][k][3], the 62-float rows -- is a run of floats whose start is only 4-byte
+//     aligned: the values are assembled in LDS and the run is written dword by dword, lane-contiguous.  Position and scale sit
+//     at a stride of 3 dwords (conflict-free on 32 banks), the quaternion is put down as one 16-byte ds_write_b128 per lane
+//     (contiguous), as the ingest picks it up;
+//   * the SH rows (192 bytes, 16-byte aligned in the blob; the workgroup's rows are one run of bytes) are read as whole
+//     16-byte loads into LDS at kShRowLds dwords per row (k_scene_transform: why 52 and not 48).  sh_rest takes floats
+//     3 .. 3 + 3 k of each row, consecutive lanes consecutive dwords; a record's planar f_rest takes float 3 + 3 j + channel
+//     for consecutive j, a stride of 3 dwords.  When only the DC term is wanted only the rows' first 16 bytes are read.
+// It writes nothing but the outputs and reads the fp32 SH block whatever the scene renders from.
+// COST: DESIGN.md section 3b (tools/scene_export_rate.py, profiles/r13_scene_export.txt).
+struct SceneExport {
+    gs_device_arrays_out a;  // RECORDS false
+    float* records;          // RECORDS true: [count][62]
+};
+
+template <bool RECORDS>
+__global__ __launch_bounds__(BLOCK) void k_scene_export(SceneExport x, const float* __restrict__ blob, uint32_t stride, uint32_t first,
+                                                        uint32_t count) {
+    __shared__ float s_pos[3 * BLOCK], s_scale[3 * BLOCK], s_op[BLOCK];
+    __shared__ __attribute__((aligned(16))) float s_rot[4 * BLOCK];
+    __shared__ __attribute__((aligned(16))) float s_sh[BLOCK * kShRowLds];
+    const gs_device_arrays_out& a = x.a;
+    const uint32_t g0 = blockIdx.x * BLOCK, t = threadIdx.x, i = g0 + t;  // g0 < count: the grid covers the range
+    const size_t N = stride;
+    const uint32_t left = count - g0, in_block = min((uint32_t)BLOCK, left);  // Gaussians from g0 on; those of this workgroup
+    const uint32_t k3 = RECORDS ? 45u : (a.sh_rest ? 3u * a.sh_rest_coeffs : 0u);
+    const bool want_pos = RECORDS || a.means, want_scale = RECORDS || a.log_scales, want_rot = RECORDS || a.quats;
+    const bool want_op = RECORDS || a.opacity_logits, want_sh = RECORDS || a.sh_dc || k3 != 0u;
+
+    if (want_sh) {
+        // whole rows (12 pieces of 16 bytes each, one run of bytes over the workgroup), or each row's first piece alone; the
+        // loads are issued together and put down once they have arrived
+        const bool whole = k3 != 0u;
+        const uint32_t pieces = in_block * (whole ? 12u : 1u);
+        const float4* rows = reinterpret_cast<const float4*>(blob + (size_t)P_SH * N + ((size_t)first + g0) * 48u);
+        // (q is clamped: a lane beyond the end repeats the last piece, load and store, so that neither is conditional -- under
+        // a condition the compiler sinks each load to its store and the twelve wait for one another)
+        float4 v[12];
+#pragma unroll
+        for (uint32_t k = 0; k < 12; ++k) {
+            const uint32_t q = min(k * BLOCK + t, pieces - 1u);
+            v[k] = rows[whole ? q : 12u * q];
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < 12; ++k) {
+            const uint32_t q = min(k * BLOCK + t, pieces - 1u), r = whole ? q / 12u : q, c = whole ? q - r * 12u : 0u;
+            reinterpret_cast<float4*>(s_sh + r * kShRowLds)[c] = v[k];
+        }
+    }
+    if (i < count) {
+        const uint2* tab = reinterpret_cast<const uint2*>(kExpfTab);
+        const float* p = blob + first + i;
+        // every plane's load is issued before the first inversion waits for one
+        float sc[3] = {0.0f, 0.0f, 0.0f}, o = 0.0f;
+        if (want_scale) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) sc[k] = p[(P_SCALE + k) * N];
+        }
+        if (want_op) o = p[P_OPACITY * N];
+        if (want_pos) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) s_pos[3 * t + k] = p[(P_POS + k) * N];
+        }
+        if (want_rot)
+            reinterpret_cast<float4*>(s_rot)[t] = make_float4(p[(P_ROT + 0) * N], p[(P_ROT + 1) * N], p[(P_ROT + 2) * N], p[(P_ROT + 3) * N]);
+        if (want_scale) {
+            for (int k = 0; k < 3; ++k) s_scale[3 * t + k] = export_log_scale(sc[k], tab);
+        }
+        if (want_op) {
+            const float logit = export_opacity_logit(o, tab);
+            if (RECORDS) s_op[t] = logit;
+            else a.opacity_logits[i] = logit;
+        }
+    }
+    __syncthreads();
+    if (RECORDS) {
+        float* out = x.records + (size_t)g0 * 62u;
+#pragma unroll 2
+        for (uint32_t j = t; j < in_block * 62u; j += BLOCK) {
+            const uint32_t g = j / 62u, f = j - g * 62u;
+            float v;
+            if (f < 3u) v = s_pos[3u * g + f];
+            else if (f < 6u) v = 0.0f;  // normals
+            else if (f < 9u) v = s_sh[g * kShRowLds + (f - 6u)];
+            else if (f < 54u) {  // planar f_rest: 15 R, 15 G, 15 B  <-  sh[3 j + channel]  (activate_record, inverted)
+                const uint32_t ch = (f - 9u) / 15u, c = (f - 9u) - ch * 15u;
+                v = s_sh[g * kShRowLds + 3u + 3u * c + ch];
+            } else if (f == 54u) v = s_op[g];
+            else if (f < 58u) v = s_scale[3u * g + (f - 55u)];
+            else v = s_rot[4u * g + (f - 58u)];
+            out[j] = v;
+        }
+        return;
+    }
+    for (uint32_t j = t; j < in_block * 4u; j += BLOCK) {
+        if (a.means && j < in_block * 3u) a.means[(size_t)g0 * 3u + j] = s_pos[j];
+        if (a.log_scales && j < in_block * 3u) a.log_scales[(size_t)g0 * 3u + j] = s_scale[j];
+        if (a.quats) a.quats[(size_t)g0 * 4u + j] = s_rot[j];
+        if (a.sh_dc && j < in_block * 3u) a.sh_dc[(size_t)g0 * 3u + j] = s_sh[(j / 3u) * kShRowLds + (j - (j / 3u) * 3u)];
+    }
+#pragma unroll 3
+    for (uint32_t j = t; j < in_block * k3; j += BLOCK) {
+        const uint32_t g = j / k3;
+        a.sh_rest[(size_t)g0 * k3 + j] = s_sh[g * kShRowLds + 3u + (j - g * k3)];
+    }
+}
+
+void launch_scene_export(const gs_device_arrays_out& a, const float* blob, uint32_t stride, uint32_t first, uint32_t count, hipStream_t s) {
+    if (count == 0) return;
+    SceneExport x = {a, nullptr};
+    hipLaunchKernelGGL(k_scene_export<false>, dim3((count + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, x, blob, stride, first, count);
+}
+void launch_scene_export_records(float* records, const float* blob, uint32_t stride, uint32_t first, uint32_t count, hipStream_t s) {
+    if (count == 0) return;
+    SceneExport x = {};
+    x.records = records;
+    hipLaunchKernelGGL(k_scene_export<true>, dim3((count + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, x, blob, stride, first, count);
+}
+
 // ---- test hook: gs_expf_libm_domain over ranges of binary32 bit patterns, checksummed per block of 2^20 exactly as
 // gs_debug_expf_scan does for the blend's function (tests/test_gpu_device_arrays.py)
 __global__ __launch_bounds__(BLOCK) void k_activation_expf_scan(uint32_t first_bits, uint64_t count, unsigned long long* __restrict__ block_sums) {

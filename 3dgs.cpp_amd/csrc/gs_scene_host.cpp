@@ -178,9 +178,110 @@ void transform_scene(gs_scene* s, const gs_transform& t, uint64_t first, uint64_
     HIP_CHECK(hipStreamSynchronize(stream));
 }
 
+// What gs_scene_to_device_arrays refuses before any device is touched (the twin of check_device_arrays; every member is optional).
+void check_device_arrays_out(const gs_device_arrays_out* a) {
+    if (!a) throw Error(GS_ERR_INVALID, "null argument");
+    const uint32_t k = a->sh_rest_coeffs;
+    if (k != 0 && k != 3 && k != 8 && k != 15) throw Error(GS_ERR_INVALID, "sh_rest_coeffs must be 0, 3, 8 or 15 (SH degree 0..3)");
+    const struct {
+        const float* p;
+        const char* name;
+    } members[6] = {{a->means, "means"}, {a->log_scales, "log_scales"}, {a->quats, "quats"}, {a->opacity_logits, "opacity_logits"},
+                    {a->sh_dc, "sh_dc"}, {a->sh_rest, "sh_rest"}};
+    for (const auto& m : members)
+        if (reinterpret_cast<uintptr_t>(m.p) % 4 != 0) throw Error(GS_ERR_INVALID, std::string("device array `") + m.name + "` is not 4-byte aligned");
+}
+
+void export_records_streamed(const gs_scene* s, uint64_t first, uint64_t count, const std::function<void(const float*, uint64_t)>& sink) {
+    if (count == 0) return;
+    HIP_CHECK(hipSetDevice(s->device));
+    uint64_t chunk = 1ull << 18;
+    if (const char* e = std::getenv("GS_EXPORT_CHUNK")) chunk = std::max<uint64_t>(1, std::strtoull(e, nullptr, 10));
+    chunk = std::min(chunk, count);
+    const size_t floats = static_cast<size_t>(chunk) * gs::host::kRecordFloats;
+    const uint32_t st = static_cast<uint32_t>(gs::blob_stride(s->n));
+    DevBuf<float> dev[2];
+    float* pinned[2] = {nullptr, nullptr};
+    hipEvent_t arrived[2] = {nullptr, nullptr};
+    hipStream_t down = nullptr;
+    auto cleanup = [&] {
+        if (down) (void)hipStreamSynchronize(down);  // (nothing may still be writing into what is freed)
+        for (int k = 0; k < 2; ++k) {
+            if (pinned[k]) (void)hipHostFree(pinned[k]);
+            if (arrived[k]) (void)hipEventDestroy(arrived[k]);
+        }
+        if (down) (void)hipStreamDestroy(down);
+    };
+    try {
+        HIP_CHECK(hipStreamCreateWithFlags(&down, hipStreamNonBlocking));
+        for (int k = 0; k < 2; ++k) {
+            dev[k].alloc(floats);
+            HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&pinned[k]), floats * sizeof(float), hipHostMallocDefault));
+            HIP_CHECK(hipEventCreateWithFlags(&arrived[k], hipEventDisableTiming));
+        }
+        const uint64_t chunks = (count + chunk - 1) / chunk;
+        auto rows_of = [&](uint64_t c) { return std::min(chunk, count - c * chunk); };
+        for (uint64_t c = 0; c <= chunks; ++c) {  // chunk c is enqueued, then chunk c - 1 consumed: its buffers are free again for c + 1
+            if (c < chunks) {
+                const uint64_t rows = rows_of(c);
+                gs::launch_scene_export_records(dev[c & 1].p, s->blob, st, static_cast<uint32_t>(first + c * chunk), static_cast<uint32_t>(rows), down);
+                HIP_CHECK(hipGetLastError());
+                HIP_CHECK(hipMemcpyAsync(pinned[c & 1], dev[c & 1].p, static_cast<size_t>(rows) * gs::host::kRecordFloats * sizeof(float),
+                                         hipMemcpyDeviceToHost, down));
+                HIP_CHECK(hipEventRecord(arrived[c & 1], down));
+            }
+            if (c >= 1) {
+                HIP_CHECK(hipEventSynchronize(arrived[(c - 1) & 1]));
+                sink(pinned[(c - 1) & 1], rows_of(c - 1));
+            }
+        }
+    } catch (...) {
+        cleanup();
+        throw;
+    }
+    cleanup();
+}
+
 }  // namespace gs_host
 
 extern "C" {
+
+int gs_deactivate_vertices(const float* vertices, uint64_t n, float* records) {
+    return guarded([&] {
+        if ((!vertices || !records) && n) throw Error(GS_ERR_INVALID, "null argument");
+        parallel_for(n, [&](uint64_t lo, uint64_t hi) {
+            for (uint64_t i = lo; i < hi; ++i)
+                gs::host::deactivate_vertex(vertices + i * gs::host::kVertexFloats, records + i * gs::host::kRecordFloats);
+        });
+    });
+}
+
+int gs_scene_to_device_arrays(const gs_scene* s, const gs_device_arrays_out* a, uint64_t first, uint64_t count, void* stream) {
+    return guarded([&] {
+        check_device_arrays_out(a);
+        if (!s) throw Error(GS_ERR_INVALID, "null argument");
+        if (first > s->n || count > s->n - first) throw Error(GS_ERR_INVALID, "Gaussian range out of bounds");
+        if (count == 0 || !(a->means || a->log_scales || a->quats || a->opacity_logits || a->sh_dc || (a->sh_rest && a->sh_rest_coeffs))) return;
+        HIP_CHECK(hipSetDevice(s->device));
+        const hipStream_t st = static_cast<hipStream_t>(stream);
+        gs::launch_scene_export(*a, s->blob, static_cast<uint32_t>(gs::blob_stride(s->n)), static_cast<uint32_t>(first),
+                                static_cast<uint32_t>(count), st);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipStreamSynchronize(st));
+    });
+}
+
+int gs_scene_download_records(const gs_scene* s, uint64_t first, uint64_t count, float* records) {
+    return guarded([&] {
+        if (!s || (!records && count)) throw Error(GS_ERR_INVALID, "null argument");
+        if (first > s->n || count > s->n - first) throw Error(GS_ERR_INVALID, "Gaussian range out of bounds");
+        float* out = records;
+        export_records_streamed(s, first, count, [&](const float* rec, uint64_t rows) {
+            std::memcpy(out, rec, static_cast<size_t>(rows) * gs::host::kRecordFloats * sizeof(float));
+            out += rows * gs::host::kRecordFloats;
+        });
+    });
+}
 
 int gs_scene_transform(gs_scene* s, const gs_transform* t, uint64_t first, uint64_t count, void* stream) {
     return guarded([&] {

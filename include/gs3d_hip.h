@@ -211,6 +211,58 @@ int gs_transform_sh_matrices(const gs_transform* t, float out[83]);
  * in->rotation is used as it is, NOT normalised (gs_camera_uniforms does not normalise it either): the product has its norm. */
 int gs_transform_camera(const gs_transform* t, const gs_camera* in, gs_camera* out);
 
+/* ---- export: the scene back out, as PLY-domain values.  No reference counterpart (GSScene only loads). -------------------
+ * The inverse of the activation.  Positions, the rotation AS STORED and the 48 SH coefficients are copies of bits (the
+ * record's planar f_rest is the exact inverse of gs_activate_records' reorder; normals are 0).  A scale s and an opacity o are
+ * exported as the binary32 pre-activation value whose activation -- exp, 1 / (1 + exp(-x)), evaluated as every way into a
+ * scene evaluates them -- is closest to the stored value: a first guess log(s), log(o / (1 - o)) computed in binary64 and
+ * rounded once, then the best of that value and its binary32 neighbours at distance <= 4 (ties: the order 0, -1, +1, -2, ..).
+ * The rule is stated operation by operation in gs_host_math.h and gs_scene.hip; host and device give the same bits.
+ *   - A stored value that IS an image of the activation (every scene that was loaded and not transformed) re-activates to
+ *     exactly the stored bits: a scene that is saved and reloaded has the same positions, scales, opacities and SH, bit for
+ *     bit.  Measured over 6e7 scales exp(x), x in [-103, 88], and 5.8e7 opacities sigmoid(x), x in [-100, 17]: every one; the
+ *     scales never needed a neighbour, the opacities one at distance <= 2.
+ *   - A stored value that is not an image (a transformed scale, a subnormal) gets the nearest image: the rule, not an error.
+ *   - s == 0 -> -inf, s == +inf -> +inf, s < 0 or NaN -> NaN;  o == 0 -> -inf, o == 1 -> +inf, o outside [0, 1] or NaN -> NaN.
+ *   - ROTATIONS round-trip to within a bound, NOT bit for bit: the stored quaternion is normalised and a reload normalises
+ *     it again; its dot product is 1 +- a few 2^-24, so each component may move by up to 8 * 2^-24 relative (measured
+ *     <= 4.8 * 2^-24, on 36 % of rows) -- and with it cov3D and the frame, by rounding noise.
+ * gs_deactivate_vertices: host only, no device: the inverse of gs_activate_records; n x 60 floats -> n x 62 floats.
+ * gs_write_ply: host only: n records as the reference's binary PLY (little endian, the 62 float properties x y z nx ny nz
+ *   f_dc_0..2 f_rest_0..44 opacity scale_0..2 rot_0..3), which gs_read_ply takes as the records they are and the reference
+ *   loads.  An I/O error removes the partly written file: GS_ERR_IO. */
+int gs_deactivate_vertices(const float* vertices, uint64_t n, float* records);
+int gs_write_ply(const char* path, const float* records, uint64_t n);
+/* Where gs_scene_to_device_arrays puts the model: gs_device_arrays with writable members (device pointers on the scene's
+ * device, 4-byte aligned and nothing more; n rows each). */
+typedef struct {
+    float* means;           /* [n][3]                                          */
+    float* log_scales;      /* [n][3]   log of the stored scale (see above)    */
+    float* quats;           /* [n][4]   w x y z, as stored (normalised)        */
+    float* opacity_logits;  /* [n]      logit of the stored opacity            */
+    float* sh_dc;           /* [n][3]                                          */
+    float* sh_rest;         /* [n][sh_rest_coeffs][3], RGB innermost           */
+    uint32_t sh_rest_coeffs; /* 0, 3, 8 or 15: higher bands are dropped        */
+} gs_device_arrays_out;
+/* Gaussians [first, first + count) of a scene of ANY origin as the six arrays gs_scene_from_device_arrays accepts, device
+ * to device (row i = Gaussian first + i): masking, concatenating, pruning and re-ordering scenes is then tensor work on
+ * the device, and a trainer can start from a PLY loaded and aligned here.  A NULL member is skipped (sh_rest == NULL: the
+ * caller does not want the higher bands, whatever sh_rest_coeffs says); count == 0 is a successful no-op.  It reads the
+ * scene's canonical blob -- id order, never the copy in spatial order -- and the fp32 SH block even when the scene is
+ * quantised (gs_scene_quantize_sh keeps that block; the binary16 one is not exported).  Nothing in the scene changes.  The
+ * work is enqueued on `stream` (a hipStream_t, NULL: the default stream) and the call returns after synchronising it.
+ * GS_ERR_INVALID, before a device is selected: a null argument, a range out of bounds, sh_rest_coeffs not in {0, 3, 8, 15},
+ * a misaligned pointer. */
+int gs_scene_to_device_arrays(const gs_scene* s, const gs_device_arrays_out* a, uint64_t first, uint64_t count, void* stream);
+/* Gaussians [first, first + count) as PLY records (62 floats each) in host memory: the PLY-domain twin of
+ * gs_scene_download_vertex_range, equal to gs_deactivate_vertices of it bit for bit. */
+int gs_scene_download_records(const gs_scene* s, uint64_t first, uint64_t count, float* records);
+/* The whole scene as a PLY, byte for byte what gs_write_ply writes from gs_scene_download_records: streamed in chunks (the
+ * kernel fills one of two device buffers with records, an asynchronous copy moves them to pinned host memory, the file is
+ * written from there while the next chunk is produced; 64-bit offsets), so no host copy of the scene is made.  An I/O error
+ * removes the partly written file: GS_ERR_IO. */
+int gs_scene_save_ply(const gs_scene* s, const char* path);
+
 /* GSScene::getNumVertices (GSScene.h:37-39). */
 uint64_t gs_scene_num_vertices(const gs_scene* s);
 /* Opt-in storage quantisation (no reference counterpart; the reference keeps fp32 SH, GSScene.h:41-46): the 48 SH
