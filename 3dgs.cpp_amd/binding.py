@@ -24,7 +24,7 @@ BLOB_PLANES = 59
 
 # the device code of libgs3d_hip.so: one translation unit per stage + the shared device headers
 KERNEL_SOURCES = ("gs_device.h", "gs_bin.h", "gs_scene.hip", "gs_preprocess.hip", "gs_radix.hip", "gs_bin_l1.hip", "gs_bin_l2.hip",
-                  "gs_blend.hip", "gs_kernels.h")
+                  "gs_blend.hip", "gs_contrib.hip", "gs_kernels.h")
 
 
 def library_source_hash():
@@ -61,7 +61,7 @@ SYMBOLS = ["gs_last_error", "gs_device_count", "gs_read_ply", "gs_activate_recor
            "gs_deactivate_vertices", "gs_write_ply", "gs_scene_to_device_arrays", "gs_scene_download_records", "gs_scene_save_ply",
            "gs_scene_destroy", "gs_renderer_create", "gs_renderer_destroy", "gs_camera_uniforms",
            "gs_render", "gs_render_host", "gs_synchronize", "gs_set_timing", "gs_set_frames_in_flight", "gs_set_sort_path", "gs_set_exp_mode", "gs_set_graph_mode", "gs_set_blend_lockstep", "gs_get_blend_lockstep", "gs_set_blend_contraction", "gs_set_antialiased", "gs_get_antialiased", "gs_get_timing_totals",
-           "gs_get_frame_intervals", "gs_get_stats", "gs_poll_stats", "gs_debug_download", "gs_debug_expf_scan", "gs_debug_alpha_cut_scan", "gs_renderer_stream",
+           "gs_get_frame_intervals", "gs_get_stats", "gs_poll_stats", "gs_debug_download", "gs_accumulate_contributions", "gs_debug_expf_scan", "gs_debug_alpha_cut_scan", "gs_renderer_stream",
            "gs_dist_unique_id", "gs_dist_create", "gs_dist_rank", "gs_dist_world", "gs_dist_pose_count",
            "gs_dist_broadcast_scene", "gs_dist_broadcast_scene_ex", "gs_dist_verify", "gs_dist_destroy"]
 
@@ -171,6 +171,32 @@ def _device_arrays(tensors, device, require):
         rows = r
         setattr(a, name, t.data_ptr() if r else None)
     return a, (rows or 0)
+
+
+class Contributions(C.Structure):
+    """gs_contributions: the mask and the three outputs of gs_accumulate_contributions (include/gs3d_hip.h)."""
+    _fields_ = [("mask", C.c_void_p), ("weight", C.c_void_p), ("pixels", C.c_void_p), ("top_id", C.c_void_p)]
+
+
+def _tensor_exact(name, t, dtypes, shape, device):
+    """data_ptr of device tensor `t` after checking it is what gs_contributions takes: one of `dtypes`, contiguous, on GPU
+    `device`, of exactly `shape` (a None extent is not checked)."""
+    if not all(hasattr(t, a) for a in ("data_ptr", "shape", "dtype", "is_contiguous", "device")):
+        raise TypeError(f"{name}: a device tensor is needed (data_ptr, shape, dtype, is_contiguous, device), got {type(t).__name__}")
+    if str(t.dtype).rsplit(".", 1)[-1] not in dtypes:
+        raise TypeError(f"{name}: dtype must be {' or '.join(dtypes)}, not {t.dtype}")
+    got = tuple(int(d) for d in t.shape)
+    if len(got) != len(shape) or any(w is not None and g != w for g, w in zip(got, shape)):
+        raise ValueError(f"{name}: shape {got} is not ({', '.join('?' if w is None else str(w) for w in shape)})")
+    if not t.is_contiguous():
+        raise ValueError(f"{name}: the tensor must be contiguous; call .contiguous()")
+    dev = t.device
+    kind, index = getattr(dev, "type", str(dev).split(":")[0]), getattr(dev, "index", None)
+    if kind == "cpu":
+        raise ValueError(f"{name}: the tensor is on the CPU; the arrays of Renderer.contributions live on the renderer's device")
+    if (0 if index is None else int(index)) != int(device):
+        raise ValueError(f"{name}: the tensor is on device {index}, the renderer on device {device}")
+    return t.data_ptr() if all(got) else None
 
 
 def _stream_handle(stream):
@@ -464,11 +490,34 @@ class Renderer:
     def __init__(self, scene):
         self.scene = scene
         self._h = C.c_void_p()
+        self._frame_hw = None  # (height, width) of the last frame handed to render / render_host: what contributions() checks against
         _check(lib().gs_renderer_create(scene._h, C.byref(self._h)))
 
     def render(self, uniforms, rgba_ptr=0, bgra_ptr=0):
         """Enqueue one frame into device buffers (raw pointers, e.g. tensor.data_ptr())."""
         _check(lib().gs_render(self._h, _p(uniforms), C.c_void_p(rgba_ptr), C.c_void_p(bgra_ptr)))
+        self._frame_hw = (int(uniforms["height"][0]), int(uniforms["width"][0]))
+
+    def contributions(self, weight=None, pixels=None, top_id=None, mask=None):
+        """What every Gaussian contributed to the last frame (gs_accumulate_contributions), into torch tensors on the renderer's
+        device, contiguous: weight int64 (N,) and pixels int32 (N,) are ADDED to -- the sum over the counted pixels that blend a
+        Gaussian of q = round(alpha T 2^24), and the number of those pixels; top_id int32 (H, W) is overwritten with the scene id
+        of the Gaussian of largest alpha T at each pixel, -1 where nothing was blended or the mask is 0; mask uint8 or bool
+        (H, W): only pixels where it is not 0 are counted.  N = the scene's Gaussians, (H, W) = the last frame.  The arithmetic
+        is the reference's (exp mode 2) whatever mode the frame was blended in.  Returns synchronised."""
+        n = int(self.scene.num_vertices)
+        h, w = self._frame_hw if self._frame_hw is not None else (None, None)
+        dev = self.scene.device
+        c = Contributions()
+        if weight is not None:
+            c.weight = _tensor_exact("weight", weight, ("int64",), (n,), dev)
+        if pixels is not None:
+            c.pixels = _tensor_exact("pixels", pixels, ("int32",), (n,), dev)
+        if top_id is not None:
+            c.top_id = _tensor_exact("top_id", top_id, ("int32",), (h, w), dev)
+        if mask is not None:
+            c.mask = _tensor_exact("mask", mask, ("uint8", "bool"), (h, w), dev)
+        _check(lib().gs_accumulate_contributions(self._h, C.byref(c)))
 
     def render_host(self, uniforms, want_rgba=True, want_bgra=False):
         h, w = int(uniforms["height"][0]), int(uniforms["width"][0])
@@ -476,6 +525,7 @@ class Renderer:
         bgra = np.zeros((h, w, 4), np.uint8) if want_bgra else None
         _check(lib().gs_render_host(self._h, _p(uniforms), _p(rgba) if want_rgba else None,
                                     _p(bgra) if want_bgra else None))
+        self._frame_hw = (h, w)
         return rgba, bgra
 
     def synchronize(self):

@@ -1,4 +1,4 @@
-// gs_kernels.h -- launch wrappers of the gfx950 kernels (gs_scene / gs_preprocess / gs_radix / gs_bin_l1 / gs_bin_l2 / gs_blend .hip).
+// gs_kernels.h -- launch wrappers of the gfx950 kernels (gs_scene / gs_preprocess / gs_radix / gs_bin_l1 / gs_bin_l2 / gs_blend / gs_contrib .hip).
 // Host-side declarations only; everything takes raw device pointers + a stream.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -232,5 +232,12 @@ void launch_blend(const uint32_t* ranges, const uint32_t* sorted_gid, const uint
                   bool lockstep /* the four waves of a tile take every chunk of its list together (s_barrier): gs_blend.hip */,
                   uint64_t* stamps /* nullable: [ST_BLEND] = the kernel's start */,
                   hipStream_t s);
+
+// gs_accumulate_contributions (gs3d_hip.h; gs_contrib.hip): a second walk of a finished frame's per-tile lists with the reference's
+// arithmetic.  Reads ranges / sorted_gid / rec of that frame, writes the caller's arrays only: weight[g] += sum of q, pixels[g] +=
+// blended pixels (integer atomics), top_id[pixel] = the dominant id.  mask, weight, pixels, top_id: nullable, device memory.
+void launch_contributions(const uint32_t* ranges, const uint32_t* sorted_gid, const uint32_t* tile_order, const AttrRecord* rec,
+                          uint32_t width, uint32_t height, const uint8_t* mask, uint64_t* weight, uint32_t* pixels, uint32_t* top_id,
+                          hipStream_t s);
 
 }  // namespace gs

@@ -165,7 +165,8 @@ struct gs_renderer {
     int num_sets = 1;
     uint32_t capacity = 0;       // tile instances (D) the list buffers hold
     uint32_t cand_capacity = 0;  // level-1 candidates (E1) the candidate buffers hold
-    FrameBuffers* last_set = nullptr;  // buffers of the most recently enqueued frame (stage taps)
+    FrameBuffers* last_set = nullptr;  // buffers of the most recently enqueued frame (stage taps, gs_accumulate_contributions)
+    uint32_t last_width = 0, last_height = 0;  // ... and that frame's size
 
     // frames in flight: a ring of descriptors, all enqueued on `stream` (so device buffers are
     // reused in stream order); the host only waits when the ring is full or on gs_synchronize.
@@ -367,6 +368,8 @@ struct gs_renderer {
         }
         // (after any drain above: retiring may re-run frames through enqueue, which would leave another set's buffers here)
         last_set = &fb;
+        last_width = u.width;
+        last_height = u.height;
         const int tune_shape = tuners.select(u.width, u.height);  // this frame shape's own tuner (a new shape measures afresh)
         const BlendTuner& tuner = tuners.current();
         const bool lockstep = tuner.current();
@@ -1006,6 +1009,25 @@ int gs_debug_download(gs_renderer* r, int stage, void* dst, uint64_t bytes) {
         }
         if (bytes < size) throw Error(GS_ERR_INVALID, "destination too small for stage buffer");
         if (size) HIP_CHECK(hipMemcpy(dst, src, size, hipMemcpyDeviceToHost));
+    });
+}
+
+int gs_accumulate_contributions(gs_renderer* r, const gs_contributions* c) {
+    return guarded([&] {
+        if (!r || !c) throw Error(GS_ERR_INVALID, "null argument");
+        // (by the pointer's value alone: nothing is dereferenced here)
+        if (reinterpret_cast<uintptr_t>(c->weight) % 8 != 0) throw Error(GS_ERR_INVALID, "weight must be 8-byte aligned");
+        if (reinterpret_cast<uintptr_t>(c->pixels) % 4 != 0) throw Error(GS_ERR_INVALID, "pixels must be 4-byte aligned");
+        if (reinterpret_cast<uintptr_t>(c->top_id) % 4 != 0) throw Error(GS_ERR_INVALID, "top_id must be 4-byte aligned");
+        r->drain();  // queued frames retire; an overflowed one is re-run: the lists below are the last frame's, complete
+        if (!r->have_frame || !r->last_set) throw Error(GS_ERR_INVALID, "no frame rendered yet");
+        if (!c->weight && !c->pixels && !c->top_id) return;
+        HIP_CHECK(hipSetDevice(r->scene->device));
+        const FrameBuffers& fb = *r->last_set;
+        gs::launch_contributions(fb.ranges.p, fb.sorted.p, r->tile_order.p, fb.rec.p, r->last_width, r->last_height, c->mask, c->weight,
+                                 c->pixels, c->top_id, fb.stream);
+        HIP_CHECK(hipGetLastError());
+        fb.sync();
     });
 }
 

@@ -415,6 +415,48 @@ int gs_poll_stats(gs_renderer* r, gs_frame_stats* out, uint64_t* frames_retired)
  * GS_STAGE_SORTED_GID / _SORTED_TILE / _RANGES present them laid end to end in tile order, i.e. as the reference's
  * sorted payload, the tile half of its sorted keys and its tileBoundaryBuffer. */
 int gs_debug_download(gs_renderer* r, int stage, void* dst, uint64_t bytes);
+/* What every Gaussian contributed to the LAST frame: its weight, the pixels it was blended in, and per pixel the Gaussian that
+ * dominates it -- for pruning by significance over a set of views, brush / lasso selection (mask) and click-to-pick (top_id).
+ * No reference counterpart.  One more kernel (gs_contrib.hip) walks the per-tile lists and attribute records the frame left in
+ * HBM; it reads ranges, lists and records of that frame and writes the four arrays below and nothing the renderer owns: the
+ * next frame, the stage taps and captured graphs are unaffected.
+ *
+ * Per pixel the tile's list is walked exactly as render.comp:61-89 walks it: `power > 0` skips an entry (:68), `alpha < 1/255`
+ * skips it (:78), `T (1 - alpha) < 1e-4` ends the walk (:83).  An entry that reaches :87 is BLENDED at that pixel with
+ *     w = fl32(alpha * T)        alpha, T: the binary32 values of :87 (T before :88 updates it)
+ *     q = w * 2^24 rounded to the nearest integer, ties to even        (the scaling is exact; 6 <= q < 2^24)
+ * A pixel is COUNTED if it lies inside the image and mask (if given) is not 0 there.  Then
+ *     weight[g] += sum of q over the counted pixels that blend g        (unit: 2^-24 of a pixel's full weight)
+ *     pixels[g] += the number of those pixels
+ *     top_id[p]  = the id with the largest w at p, the earlier list entry on equal w; 0xFFFFFFFF where nothing was blended
+ *                  or p is not counted
+ * weight and pixels are ADDED to (zero them once, call after each of many views); top_id is overwritten.  The sums are integers,
+ * so they do not depend on the order the adds arrive in: two calls give the same bits.  The mask gates what is recorded, never
+ * a pixel's T.
+ *
+ * The arithmetic is ALWAYS the reference's -- `power` with every product and sum rounded on its own, exp() = glibc's expf
+ * restated (exp mode 2), :78 decided on `power` against the record's alpha cut -- whatever gs_set_exp_mode,
+ * gs_set_blend_contraction and gs_set_blend_lockstep say.  The default blend (exp mode 3) takes the same decisions by
+ * construction, so the counts describe the frame it rendered; the weights are the reference's and differ from what its
+ * v_exp_f32 accumulated by rounding noise.  With gs_set_blend_contraction(1) the pass STAYS UNCONTRACTED: where the contracted
+ * `power` of the frame fell on the other side of a cut, the pass reports the reference's decision, not the frame's.  With
+ * gs_set_antialiased(1) the records carry opacity' and its cut, and the pass follows them.
+ *
+ * Ids are SCENE ids, also for a scene that is read through its copy in spatial order (the lists hold scene ids).
+ *
+ * All four members are device pointers on the renderer's device, each nullable: mask [height][width] bytes; weight [N] 64-bit,
+ * 8-byte aligned; pixels [N] 32-bit and top_id [height][width] 32-bit, 4-byte aligned.  N = gs_scene_num_vertices, width and
+ * height those of the last frame.  The call synchronizes like gs_debug_download (queued frames retire, an overflowed frame is
+ * re-run), enqueues on the last frame's stream and returns when the arrays are written.  GS_ERR_INVALID: r or c NULL (checked
+ * before any device is touched), no frame rendered yet, a misaligned pointer (judged by its value alone).  All three outputs
+ * NULL: nothing is launched. */
+typedef struct {
+    const uint8_t* mask;
+    uint64_t* weight;
+    uint32_t* pixels;
+    uint32_t* top_id;
+} gs_contributions;
+int gs_accumulate_contributions(gs_renderer* r, const gs_contributions* c);
 /* Test hook (tests/test_gpu_expf.py): evaluate the blend's exp() implementations ON THE DEVICE over the binary32 values with
  * bit patterns [first_bits, first_bits + count) (the negative floats run from 0x80000000 = -0 to 0xFF800000 = -inf).
  * block_sums[j] = sum over block j of 2^20 consecutive patterns of  bits(expf(x)) * ((bits(x) * 0x9E3779B1) | 1)  mod 2^64,
