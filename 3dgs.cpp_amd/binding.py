@@ -24,7 +24,7 @@ BLOB_PLANES = 59
 
 # the device code of libgs3d_hip.so: one translation unit per stage + the shared device headers
 KERNEL_SOURCES = ("gs_device.h", "gs_bin.h", "gs_scene.hip", "gs_preprocess.hip", "gs_radix.hip", "gs_bin_l1.hip", "gs_bin_l2.hip",
-                  "gs_blend.hip", "gs_contrib.hip", "gs_kernels.h")
+                  "gs_blend.hip", "gs_contrib.hip", "gs_features.hip", "gs_kernels.h")
 
 
 def library_source_hash():
@@ -61,7 +61,7 @@ SYMBOLS = ["gs_last_error", "gs_device_count", "gs_read_ply", "gs_activate_recor
            "gs_deactivate_vertices", "gs_write_ply", "gs_scene_to_device_arrays", "gs_scene_download_records", "gs_scene_save_ply",
            "gs_scene_destroy", "gs_renderer_create", "gs_renderer_destroy", "gs_camera_uniforms",
            "gs_render", "gs_render_host", "gs_synchronize", "gs_set_timing", "gs_set_frames_in_flight", "gs_set_sort_path", "gs_set_exp_mode", "gs_set_graph_mode", "gs_set_blend_lockstep", "gs_get_blend_lockstep", "gs_set_blend_contraction", "gs_set_antialiased", "gs_get_antialiased", "gs_get_timing_totals",
-           "gs_get_frame_intervals", "gs_get_stats", "gs_poll_stats", "gs_debug_download", "gs_accumulate_contributions", "gs_debug_expf_scan", "gs_debug_alpha_cut_scan", "gs_renderer_stream",
+           "gs_get_frame_intervals", "gs_get_stats", "gs_poll_stats", "gs_debug_download", "gs_accumulate_contributions", "gs_blend_features", "gs_debug_expf_scan", "gs_debug_alpha_cut_scan", "gs_renderer_stream",
            "gs_dist_unique_id", "gs_dist_create", "gs_dist_rank", "gs_dist_world", "gs_dist_pose_count",
            "gs_dist_broadcast_scene", "gs_dist_broadcast_scene_ex", "gs_dist_verify", "gs_dist_destroy"]
 
@@ -178,9 +178,18 @@ class Contributions(C.Structure):
     _fields_ = [("mask", C.c_void_p), ("weight", C.c_void_p), ("pixels", C.c_void_p), ("top_id", C.c_void_p)]
 
 
-def _tensor_exact(name, t, dtypes, shape, device):
-    """data_ptr of device tensor `t` after checking it is what gs_contributions takes: one of `dtypes`, contiguous, on GPU
-    `device`, of exactly `shape` (a None extent is not checked)."""
+class FeatureMaps(C.Structure):
+    """gs_feature_maps: the per-Gaussian channels and the four per-pixel outputs of gs_blend_features (include/gs3d_hip.h)."""
+    _fields_ = [("features", C.c_void_p), ("channels", C.c_uint32), ("out_features", C.c_void_p), ("out_alpha", C.c_void_p),
+                ("out_depth", C.c_void_p), ("out_depth_median", C.c_void_p)]
+
+
+FEATURE_CHANNELS_MAX = 256  # GS_FEATURE_CHANNELS_MAX
+
+
+def _tensor_exact(name, t, dtypes, shape, device, owner="Renderer.contributions"):
+    """data_ptr of device tensor `t` after checking it is what gs_contributions / gs_feature_maps take: one of `dtypes`,
+    contiguous, on GPU `device`, of exactly `shape` (a None extent is not checked)."""
     if not all(hasattr(t, a) for a in ("data_ptr", "shape", "dtype", "is_contiguous", "device")):
         raise TypeError(f"{name}: a device tensor is needed (data_ptr, shape, dtype, is_contiguous, device), got {type(t).__name__}")
     if str(t.dtype).rsplit(".", 1)[-1] not in dtypes:
@@ -193,7 +202,7 @@ def _tensor_exact(name, t, dtypes, shape, device):
     dev = t.device
     kind, index = getattr(dev, "type", str(dev).split(":")[0]), getattr(dev, "index", None)
     if kind == "cpu":
-        raise ValueError(f"{name}: the tensor is on the CPU; the arrays of Renderer.contributions live on the renderer's device")
+        raise ValueError(f"{name}: the tensor is on the CPU; the arrays of {owner} live on the renderer's device")
     if (0 if index is None else int(index)) != int(device):
         raise ValueError(f"{name}: the tensor is on device {index}, the renderer on device {device}")
     return t.data_ptr() if all(got) else None
@@ -518,6 +527,47 @@ class Renderer:
         if mask is not None:
             c.mask = _tensor_exact("mask", mask, ("uint8", "bool"), (h, w), dev)
         _check(lib().gs_accumulate_contributions(self._h, C.byref(c)))
+
+    def feature_maps(self, features=None, out=None, alpha=None, depth=None, median_depth=None):
+        """Per-pixel maps of the last frame (gs_blend_features), into float32 torch tensors on the renderer's device, contiguous:
+        out (H, W, C) = the rows of features (N, C) blended exactly as the colour is, alpha (H, W) = 1 - T, depth (H, W) = the
+        expected view-space depth (NOT normalised: divide by alpha where alpha > 0), median_depth (H, W) = the depth of the entry
+        that takes T below one half, +inf where none does.  Each output is a tensor to fill, True to have it allocated, or None
+        to skip; all are overwritten.  N = the scene's Gaussians, (H, W) = the last frame, C <= 256.  The arithmetic is the
+        reference's (exp mode 2) whatever mode the frame was blended in.  Returns synchronised, with a dict of the outputs
+        that were asked for (keys out, alpha, depth, median_depth)."""
+        owner = "Renderer.feature_maps"
+        n = int(self.scene.num_vertices)
+        dev = self.scene.device
+        asked = dict(out=out, alpha=alpha, depth=depth, median_depth=median_depth)
+        if self._frame_hw is None and any(v is True for v in asked.values()):
+            _check(lib().gs_blend_features(self._h, C.byref(FeatureMaps())))  # (refuses: there is no frame to size an output by)
+        h, w = self._frame_hw if self._frame_hw is not None else (None, None)
+        m = FeatureMaps()
+        channels = 0
+        if features is not None:
+            m.features = _tensor_exact("features", features, ("float32",), (n, None), dev, owner)
+            channels = int(features.shape[1])
+            if channels > FEATURE_CHANNELS_MAX:
+                raise ValueError(f"features: {channels} channels, at most {FEATURE_CHANNELS_MAX} are blended in one call")
+            if out is None:
+                raise ValueError("out: features are given but no output for them (pass a tensor or True)")
+        elif out is not None:
+            raise ValueError("out: an output for blended features needs features")
+        m.channels = channels
+        shapes = dict(out=(h, w, channels), alpha=(h, w), depth=(h, w), median_depth=(h, w))
+        members = dict(out="out_features", alpha="out_alpha", depth="out_depth", median_depth="out_depth_median")
+        result = {}
+        for name, t in asked.items():
+            if t is None:
+                continue
+            if t is True:
+                import torch
+                t = torch.empty(shapes[name], dtype=torch.float32, device=f"cuda:{int(dev)}")
+            setattr(m, members[name], _tensor_exact(name, t, ("float32",), shapes[name], dev, owner))
+            result[name] = t
+        _check(lib().gs_blend_features(self._h, C.byref(m)))
+        return result
 
     def render_host(self, uniforms, want_rgba=True, want_bgra=False):
         h, w = int(uniforms["height"][0]), int(uniforms["width"][0])

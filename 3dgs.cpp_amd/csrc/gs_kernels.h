@@ -1,4 +1,4 @@
-// gs_kernels.h -- launch wrappers of the gfx950 kernels (gs_scene / gs_preprocess / gs_radix / gs_bin_l1 / gs_bin_l2 / gs_blend / gs_contrib .hip).
+// gs_kernels.h -- launch wrappers of the gfx950 kernels (gs_scene / gs_preprocess / gs_radix / gs_bin_l1 / gs_bin_l2 / gs_blend / gs_contrib / gs_features .hip).
 // Host-side declarations only; everything takes raw device pointers + a stream.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -239,5 +239,14 @@ void launch_blend(const uint32_t* ranges, const uint32_t* sorted_gid, const uint
 void launch_contributions(const uint32_t* ranges, const uint32_t* sorted_gid, const uint32_t* tile_order, const AttrRecord* rec,
                           uint32_t width, uint32_t height, const uint8_t* mask, uint64_t* weight, uint32_t* pixels, uint32_t* top_id,
                           hipStream_t s);
+
+// gs_blend_features (gs3d_hip.h; gs_features.hip): the same second walk, per pixel: `channels` caller-supplied per-Gaussian floats
+// blended as the colour is (features [N][channels] -> out_features [height][width][channels]), alpha = 1 - T, expected and median
+// depth.  Channels go in groups of kFeatureGroup, one launch per group on `s`, each walking the lists again; the first launch (or a
+// channel-less one) writes alpha and the depths.  Every output is nullable; with out_features null no channel is blended.
+constexpr int kFeatureGroup = 16;
+void launch_features(const uint32_t* ranges, const uint32_t* sorted_gid, const uint32_t* tile_order, const AttrRecord* rec,
+                     uint32_t width, uint32_t height, const float* features, uint32_t channels, float* out_features, float* out_alpha,
+                     float* out_depth, float* out_median, hipStream_t s);
 
 }  // namespace gs

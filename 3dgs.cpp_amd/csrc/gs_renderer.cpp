@@ -1031,6 +1031,32 @@ int gs_accumulate_contributions(gs_renderer* r, const gs_contributions* c) {
     });
 }
 
+int gs_blend_features(gs_renderer* r, const gs_feature_maps* m) {
+    return guarded([&] {
+        if (!r || !m) throw Error(GS_ERR_INVALID, "null argument");
+        // (all by the members' values alone: nothing is dereferenced and no device is touched before they pass)
+        if (m->channels > GS_FEATURE_CHANNELS_MAX) throw Error(GS_ERR_INVALID, "channels exceeds GS_FEATURE_CHANNELS_MAX (256)");
+        if (m->channels > 0 && !m->features) throw Error(GS_ERR_INVALID, "channels > 0 needs features");
+        if (m->channels > 0 && !m->out_features) throw Error(GS_ERR_INVALID, "features given without out_features");
+        const struct { const void* p; const char* what; } ptrs[] = {
+            {m->features, "features must be 4-byte aligned"},         {m->out_features, "out_features must be 4-byte aligned"},
+            {m->out_alpha, "out_alpha must be 4-byte aligned"},       {m->out_depth, "out_depth must be 4-byte aligned"},
+            {m->out_depth_median, "out_depth_median must be 4-byte aligned"}};
+        for (const auto& q : ptrs)
+            if (reinterpret_cast<uintptr_t>(q.p) % 4 != 0) throw Error(GS_ERR_INVALID, q.what);
+        r->drain();  // queued frames retire; an overflowed one is re-run: the lists below are the last frame's, complete
+        if (!r->have_frame || !r->last_set) throw Error(GS_ERR_INVALID, "no frame rendered yet");
+        float* out_features = m->channels > 0 ? m->out_features : nullptr;  // channels == 0: that output is not touched
+        if (!out_features && !m->out_alpha && !m->out_depth && !m->out_depth_median) return;
+        HIP_CHECK(hipSetDevice(r->scene->device));
+        const FrameBuffers& fb = *r->last_set;
+        gs::launch_features(fb.ranges.p, fb.sorted.p, r->tile_order.p, fb.rec.p, r->last_width, r->last_height, m->features, m->channels,
+                            out_features, m->out_alpha, m->out_depth, m->out_depth_median, fb.stream);
+        HIP_CHECK(hipGetLastError());
+        fb.sync();
+    });
+}
+
 void* gs_renderer_stream(gs_renderer* r) { return r ? r->sets[0].stream : nullptr; }
 
 }  // extern "C"

@@ -457,6 +457,62 @@ typedef struct {
     uint32_t* top_id;
 } gs_contributions;
 int gs_accumulate_contributions(gs_renderer* r, const gs_contributions* c);
+/* Per-pixel maps of the LAST frame: caller-supplied per-Gaussian channels blended exactly as render.comp:87 blends the colour
+ * (labels, language or DINO features, normals, a heat map of gs_accumulate_contributions' weights, per-Gaussian error), the
+ * pixel's coverage, and its expected and median depth -- for compositing over a background or another renderer's output,
+ * occlusion against meshes, TSDF fusion and picking a 3D point.  No reference counterpart.  The sibling of
+ * gs_accumulate_contributions: one more kernel (gs_features.hip) walks the per-tile lists and attribute records the frame left in
+ * HBM; it reads ranges, lists and records of that frame and the caller's `features`, and writes the caller's four arrays and
+ * nothing the renderer owns: the next frame, the stage taps and captured graphs are unaffected.
+ *
+ * Per pixel the tile's list is walked exactly as gs_accumulate_contributions documents it (render.comp:61-89): `power > 0` skips
+ * an entry (:68), `alpha < 1/255` skips it (:78), `T (1 - alpha) < 1e-4` ends the walk (:83) -- ALWAYS with the reference's
+ * arithmetic: `power` with every product and sum rounded on its own, exp() = glibc's expf restated (exp mode 2), :78 decided on
+ * `power` against the record's alpha cut, whatever gs_set_exp_mode, gs_set_blend_contraction and gs_set_blend_lockstep say the
+ * frame ran with.  With gs_set_antialiased(1) the records carry opacity' and its cut, and the pass follows them.
+ *
+ * An entry of Gaussian g that reaches :87 adds, with that line's binary32 alpha and T (T before :88 updates it), starting from
+ * F = 0, D = 0, M unset:
+ *     F[c] = F[c] + (features[g][c] * alpha) * T     for every channel c            (the order of :87)
+ *     D    = D    + (depth[g]       * alpha) * T     depth[g]: the view-space depth of the frame's record (GS_STAGE_DEPTH)
+ *     M    = depth[g]   if M is still unset and T * (1 - alpha) < 0.5     (the first blended entry that takes T below one half)
+ * and at the walk's end the pixel gets
+ *     out_features     = F
+ *     out_depth        = D                 the EXPECTED depth, NOT normalised: divide by out_alpha where that is > 0
+ *     out_alpha        = fl32(1 - T)       T when the walk ends; a break at :83 leaves T as it was before the breaking entry
+ *     out_depth_median = M, or +inf if M is unset
+ * All outputs are OVERWRITTEN, never added to.  A pixel with an empty list gets 0, 0, 0, +inf.  Nothing is written for positions
+ * outside the image.  Each pixel adds in list order on one lane: the outputs are defined bit for bit, there are no atomics, and
+ * two calls give the same bits.  A feature row takes part only at the pixels that blend its Gaussian: a NaN in the row of a
+ * Gaussian that is in no tile list reaches no output.  Two facts that follow from the definition:
+ *   - While T >= 0.5, :83 cannot fire (alpha <= 0.99 gives T (1 - alpha) >= 0.005), so no walk ends before M is set once T can
+ *     fall below one half: out_depth_median is finite exactly where the final T < 0.5.
+ *   - With features[g] = (r, g, b) of the frame's records, out_features is the exp-mode-2 image's RGB bit for bit.
+ *
+ * Ids are SCENE ids, also for a scene that is read through its copy in spatial order: features[g] is the row of scene Gaussian g.
+ *
+ * Channels are processed in groups of 16 per launch, each launch walking the lists again (the sums of different channels do not
+ * depend on one another, so grouping changes no bit); the first also writes alpha and the depths.  Cost: INTEGRATION.md, 3e.
+ *
+ * features [N][channels] row-major; out_features [height][width][channels], channel innermost; out_alpha, out_depth,
+ * out_depth_median [height][width].  All are device pointers to floats on the renderer's device, 4-byte aligned and nothing
+ * more; each output is nullable; features may be NULL only with channels == 0.  N = gs_scene_num_vertices, width and height
+ * those of the last frame, channels 0 .. GS_FEATURE_CHANNELS_MAX.  The call synchronizes like gs_accumulate_contributions (queued
+ * frames retire, an overflowed frame is re-run), enqueues on the last frame's stream and returns when the arrays are written.
+ * GS_ERR_INVALID, checked before any device is touched: r or m NULL; channels > GS_FEATURE_CHANNELS_MAX; channels > 0 with
+ * features NULL, or with out_features NULL while features is given (rejected rather than ignored); a misaligned pointer (judged
+ * by its value alone).  GS_ERR_INVALID also when no frame has been rendered yet.  All four outputs NULL: success, nothing is
+ * launched.  channels == 0 with out_features given: that output is not touched. */
+#define GS_FEATURE_CHANNELS_MAX 256
+typedef struct {
+    const float* features;      /* [N][channels] row-major, device; may be NULL only with channels == 0 */
+    uint32_t     channels;      /* 0 .. GS_FEATURE_CHANNELS_MAX */
+    float* out_features;        /* [height][width][channels], channel innermost */
+    float* out_alpha;           /* [height][width] */
+    float* out_depth;           /* [height][width]  expected depth, NOT normalised */
+    float* out_depth_median;    /* [height][width] */
+} gs_feature_maps;
+int gs_blend_features(gs_renderer* r, const gs_feature_maps* m);
 /* Test hook (tests/test_gpu_expf.py): evaluate the blend's exp() implementations ON THE DEVICE over the binary32 values with
  * bit patterns [first_bits, first_bits + count) (the negative floats run from 0x80000000 = -0 to 0xFF800000 = -inf).
  * block_sums[j] = sum over block j of 2^20 consecutive patterns of  bits(expf(x)) * ((bits(x) * 0x9E3779B1) | 1)  mod 2^64,
