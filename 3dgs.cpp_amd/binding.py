@@ -60,7 +60,7 @@ SYMBOLS = ["gs_last_error", "gs_device_count", "gs_read_ply", "gs_activate_recor
            "gs_scene_download_vertices", "gs_scene_download_cov3d",
            "gs_deactivate_vertices", "gs_write_ply", "gs_scene_to_device_arrays", "gs_scene_download_records", "gs_scene_save_ply",
            "gs_scene_destroy", "gs_renderer_create", "gs_renderer_destroy", "gs_camera_uniforms",
-           "gs_render", "gs_render_host", "gs_synchronize", "gs_set_timing", "gs_set_frames_in_flight", "gs_set_sort_path", "gs_set_exp_mode", "gs_set_graph_mode", "gs_set_blend_lockstep", "gs_get_blend_lockstep", "gs_set_blend_contraction", "gs_set_antialiased", "gs_get_antialiased", "gs_get_timing_totals",
+           "gs_render", "gs_render_host", "gs_synchronize", "gs_set_timing", "gs_set_frames_in_flight", "gs_set_sort_path", "gs_set_exp_mode", "gs_set_graph_mode", "gs_set_blend_lockstep", "gs_get_blend_lockstep", "gs_set_level1_fused", "gs_get_level1_fused", "gs_set_blend_contraction", "gs_set_antialiased", "gs_get_antialiased", "gs_get_timing_totals",
            "gs_get_frame_intervals", "gs_get_stats", "gs_poll_stats", "gs_debug_download", "gs_accumulate_contributions", "gs_blend_features", "gs_debug_expf_scan", "gs_debug_alpha_cut_scan", "gs_renderer_stream",
            "gs_dist_unique_id", "gs_dist_create", "gs_dist_rank", "gs_dist_world", "gs_dist_pose_count",
            "gs_dist_broadcast_scene", "gs_dist_broadcast_scene_ex", "gs_dist_verify", "gs_dist_destroy"]
@@ -628,6 +628,17 @@ class Renderer:
         if now < 0:
             _check(now)
         return bool(now), bool(settled.value)
+
+    def set_level1_fused(self, mode):
+        """-1 by rule, 0 off, 1 on: k_preprocess files the level-1 candidates itself (gs_set_level1_fused; GS_L1_FUSED at creation)."""
+        _check(lib().gs_set_level1_fused(self._h, C.c_int(int(mode))))
+
+    def level1_fused(self):
+        """True: the most recently enqueued frame took the one-pass level 1 (gs_get_level1_fused)."""
+        now = lib().gs_get_level1_fused(self._h)
+        if now < 0:
+            _check(now)
+        return bool(now)
 
     def set_sort_path(self, mode):
         """0 automatic, 1 global depth order, 2 bin-local (gs_set_sort_path)."""

@@ -47,7 +47,41 @@ struct BuildArgs {
     uint32_t slab_capacity;
     uint32_t epoch;        // k_bin_queue: see BinLaunch::slab_epoch
     uint64_t* stamps;      // nullable: the frame's timeline (the level's first kernel stamps ST_L2)
+    const uint32_t* l1_words;  // non-null: level 1 ran inside k_preprocess (gs_kernels.h: L1Fused), and l1_cap is a bin region's size
+    uint32_t l1_cap;
 };
+
+// A bin's run of candidates in either form of level 1.  Three kernels: count and offset from k_l1_scan and the scatter's block 0.
+// One pass (a.l1_words): the count is where the bin's cursor ended, the offset its region's start.  There the candidates of a bin
+// arrive in an order that differs from run to run -- which no list depends on: every kernel reachable on this path (k_bin_fast,
+// the slab and queue levels) orders a bin's candidates by (depth bits, id), a total order (ids are unique within a bin), before
+// anything is derived from their positions; the same guarantee k_l1_scatter_any_order has relied on since round 2.
+__device__ __forceinline__ uint32_t bin_candidates(const BuildArgs& a, uint32_t bin) {
+    return a.l1_words ? a.l1_words[(size_t)(kL1FusedCursor0 + bin) * kL1FusedStride] : a.bin_count[bin];
+}
+__device__ __forceinline__ uint32_t bin_offset(const BuildArgs& a, uint32_t bin) {
+    return a.l1_words ? ((bin >> a.g.grid_shift) * a.g.bins_x + (bin & ((1u << a.g.grid_shift) - 1u))) * a.l1_cap : a.bin_count[kBinOffsets + bin];
+}
+// One pass: the closing values the scatter's block 0 used to produce -- E1 and the fullest bin, one atomic each per bin workgroup
+// -- and the overflow of a region (c: the bin's TRUE count; a region that ran over is skipped and the frame re-run).  Once per bin.
+__device__ __forceinline__ void bin_close_one_pass(const BuildArgs& a, uint32_t& c, int tid) {
+    if (!a.l1_words) return;
+    if (tid == 0 && c != 0) {
+        atomicAdd(&a.counters->bin_entries, c);
+        atomicMax(&a.counters->max_bin, c);
+    }
+    if (c > a.l1_cap) {
+        if (tid == 0) atomicOr(&a.counters->overflow, 1u);
+        c = 0;
+    }
+}
+// One pass: V = the sum of k_preprocess's strided counters of visible Gaussians (the level's first workgroup; four atomics)
+__device__ __forceinline__ void one_pass_visible(const BuildArgs& a) {
+    if (!a.l1_words || blockIdx.x != 0 || threadIdx.x >= kVisRegions) return;
+    uint32_t v = a.l1_words[(size_t)threadIdx.x * kL1FusedStride];
+    for (int o = WAVE / 2; o != 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o);
+    if ((threadIdx.x & (WAVE - 1)) == 0 && v != 0) atomicAdd(&a.counters->visible, v);
+}
 
 // candidate's tile box clipped to the bin, in bin-local tile coordinates (upper bounds exclusive), packed like l1_item's
 __device__ __forceinline__ uint32_t bin_local_box(const BinGrid& g, uint32_t bin, ushort4 box) {
@@ -91,6 +125,7 @@ struct BuildLayout {
 template <int R2, int THREADS, bool SORT>
 __global__ __launch_bounds__(THREADS) void k_bin_build(BuildArgs a) {
     frame_stamp(a.stamps, ST_L2);
+    one_pass_visible(a);
     BUILD_ROW(blockIdx.x);
     using L = BuildLayout<R2, THREADS, SORT>;
     constexpr int NW = L::NW, MAXC = L::MAXC, SS = L::SS, PER = kBuildSlots / NW;  // PER chunks per wave and round
@@ -110,8 +145,9 @@ __global__ __launch_bounds__(THREADS) void k_bin_build(BuildArgs a) {
     BUILD_T(0);
     uint32_t c, off;
     // this bin's count and offset (k_l1_scan, the scatter's block 0); block-uniform: scalar loads
-    c = a.bin_count[bin];
-    off = a.bin_count[kBinOffsets + bin];
+    c = bin_candidates(a, bin);
+    off = bin_offset(a, bin);
+    bin_close_one_pass(a, c, tid);
     if ((uint64_t)off + c > a.cand_capacity) c = 0;  // candidate overflow (flagged by k_l1_scatter): the frame is re-run
     if (SORT && c > (uint32_t)MAXC) {
         if (tid == 0) atomicOr(&a.counters->overflow, 2u);
@@ -452,6 +488,7 @@ __device__ __forceinline__ void bin_fast_body(const BuildArgs& a) {
 
     BUILD_ROW(MODE == 2 ? 1023u : blockIdx.x);
     if constexpr (MODE != 2) frame_stamp(a.stamps, ST_L2);  // (k_slab_work is the level's second launch)
+    if constexpr (MODE != 2) one_pass_visible(a);
     int tid = threadIdx.x, lane = tid & (WAVE - 1), w = tid / WAVE;  // (MODE 3 re-derives them per item: see there)
     // one workgroup per ON-SCREEN bin (the grid is bins_x * bins_y: with the padding of the bin grid in it, workgroups
     // that exit at once upset the dispatcher's placement and a few CUs end up with three of the real ones)
@@ -463,8 +500,9 @@ __device__ __forceinline__ void bin_fast_body(const BuildArgs& a) {
     auto bin_extent = [&]() {  // this bin's count and offset (k_l1_scan and the scatter's block 0 wrote them): block-uniform, two scalar loads
         // -- telling the compiler so keeps everything derived from them (loop bounds, the record buffer's descriptor) in scalar
         // registers; a descriptor it believes divergent is "waterfalled": every load wrapped in a readfirstlane loop with a full s_waitcnt
-        c_total = (uint32_t)__builtin_amdgcn_readfirstlane((int)a.bin_count[bin]);
-        off = (uint32_t)__builtin_amdgcn_readfirstlane((int)a.bin_count[kBinOffsets + bin]);
+        c_total = (uint32_t)__builtin_amdgcn_readfirstlane((int)bin_candidates(a, bin));
+        off = (uint32_t)__builtin_amdgcn_readfirstlane((int)bin_offset(a, bin));
+        bin_close_one_pass(a, c_total, tid);
         if ((uint64_t)off + c_total > a.cand_capacity) c_total = 0;  // candidate overflow (flagged by the scatter): the frame is re-run
         if (c_total > kMaxInBin) {
             if (tid == 0) atomicOr(&a.counters->overflow, 2u);
@@ -1224,7 +1262,7 @@ __device__ __forceinline__ void bin_fast_body(const BuildArgs& a) {
         const uint32_t n_bins = a.g.bins_x * a.g.bins_y;  // <= 1024
         {   // the on-screen bins, fullest first: rank by counting (<= 1024 broadcast reads per thread, once per workgroup)
             uint32_t* const cnt = smem;  // (LDS is free until the first item starts)
-            const uint32_t mine = (uint32_t)tid < n_bins ? a.bin_count[screen_bin((uint32_t)tid)] : 0u;
+            const uint32_t mine = (uint32_t)tid < n_bins ? bin_candidates(a, screen_bin((uint32_t)tid)) : 0u;
             cnt[tid] = mine;
             if (tid == 0) q_planned = 0;
             __syncthreads();
@@ -1433,6 +1471,8 @@ void launch_bin_level2(const BinLaunch& b, int level, hipStream_t s) {
     a.slab_capacity = b.slab_capacity;
     a.epoch = b.slab_epoch;
     a.stamps = b.stamps;
+    a.l1_words = b.l1_fused_words;
+    a.l1_cap = b.l1_fused_cap;
     const uint32_t bins = b.bins_x * b.bins_y;  // on-screen bins: the kernels map the block index onto the padded grid
     const bool sort = level < kBinSortLevels;
     if (sort && b.bin_shift <= 3) {  // bins of 4 x 4 or 8 x 8 tiles: the all-in-LDS kernel, sized by the level

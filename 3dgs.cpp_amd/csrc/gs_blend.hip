@@ -746,8 +746,12 @@ static void launch_blend_as(const uint32_t* ranges, const uint32_t* sorted_gid, 
 
 // The frame's end on its timeline: one wave behind the blend (a dependent dispatch starts when the last workgroup of the kernel before it
 // has retired) stamps the clock and hands the stamps to the host -- pinned memory, visible to it once the frame's completion event has fired.
-__global__ __launch_bounds__(WAVE) void k_frame_end(uint64_t* __restrict__ stamps, uint64_t* host_stamps, const FrameParams* __restrict__ fp) {
+__global__ __launch_bounds__(WAVE) void k_frame_end(uint64_t* __restrict__ stamps, uint64_t* host_stamps, const FrameParams* __restrict__ fp,
+                                                   uint32_t* __restrict__ l1_words, uint32_t l1_counters) {
     if (fp) host_stamps = fp->host_stamps;
+    // the one-pass level 1's counters (L1Fused::words): k_preprocess of the next frame on these buffers starts from zero
+    if (l1_words)
+        for (uint32_t k = threadIdx.x; k < l1_counters; k += WAVE) l1_words[(size_t)k * kL1FusedStride] = 0;
     const uint64_t now = wall_clock64();
     const int t = threadIdx.x;
     if (t < ST_COUNT) {
@@ -756,9 +760,9 @@ __global__ __launch_bounds__(WAVE) void k_frame_end(uint64_t* __restrict__ stamp
         if (host_stamps) host_stamps[t] = v;
     }
 }
-void launch_frame_end(uint64_t* stamps, uint64_t* host_stamps, const FrameParams* fp, hipStream_t s) {
+void launch_frame_end(uint64_t* stamps, uint64_t* host_stamps, const FrameParams* fp, uint32_t* l1_words, uint32_t l1_counters, hipStream_t s) {
     if (!stamps) return;
-    hipLaunchKernelGGL(k_frame_end, dim3(1), dim3(WAVE), 0, s, stamps, host_stamps, fp);
+    hipLaunchKernelGGL(k_frame_end, dim3(1), dim3(WAVE), 0, s, stamps, host_stamps, fp, l1_words, l1_counters);
 }
 
 void launch_blend(const uint32_t* ranges, const uint32_t* sorted_gid, const uint32_t* tile_order, const AttrView& av,

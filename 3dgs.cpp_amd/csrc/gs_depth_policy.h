@@ -172,4 +172,69 @@ struct DepthPolicy {
     }
 };
 
+// When k_preprocess files the level-1 candidates itself (gs_kernels.h: L1Fused) instead of the three level-1
+// kernels.  Every bin owns cap = cand_capacity / on-screen bins records of the candidate buffer; the path costs one device atomic
+// per (workgroup, bin the workgroup touches), so it pays where a workgroup's Gaussians are neighbours on the screen too.
+struct L1FusedPolicy {
+    static constexpr uint32_t kHold = 32;        // frames on the three-kernel path after a bin's region ran over (as slab_hold starts)
+    static constexpr uint32_t kGrowCeiling = 4;  // the candidate buffer may grow to this many times its default size for the path
+    // Wide splats: E1 / V (bins per visible Gaussian) beyond which the same-address atomics cost more than the launches they replace.
+    // profiles/r16_atomic_rate_sparse.txt: a workgroup reserving in k bins adds 1.8 us (k = 8), 7.8 us (k = 16), 25 us (k = 32) to
+    // the kernel; the three launches take 24.4 us, so the crossover is k ~ 31 bins per workgroup.  A Morton block of small splats
+    // spans ~2 x 2 bins (k = 4.3 at E1 / V = 1.5); splats of m x m bins widen that to ~(m + 1)^2: k = 31 at m = 4.6, E1 / V = 21.
+    // The path is left at 8 (k ~ 15, 7 us of atomics): beyond it the gain is within the noise, well short of the crossover.
+    static constexpr uint32_t kWideRatio = 8;
+
+    int mode = -1;      // -1 by rule, 0 off, 1 on wherever the frame's structure allows (the hold after an overflow still applies)
+    uint32_t hold = 0;  // frames left on the three-kernel path
+    // the last retired frame, and its shape
+    bool have_last = false;
+    uint32_t last_width = 0, last_height = 0, last_max_bin = 0, last_e1 = 0, last_v = 0;
+    int last_bin_shift = -1;
+
+    static uint32_t region_cap(uint32_t cand_capacity, uint32_t bins) { return bins ? cand_capacity / bins : 0u; }
+    // cap is at least 5/4 of the fullest bin
+    static bool cap_suffices(uint32_t cap, uint32_t max_bin) { return 4ull * cap >= 5ull * max_bin; }
+    bool knows(uint32_t width, uint32_t height, int bin_shift) const {
+        return have_last && width == last_width && height == last_height && bin_shift == last_bin_shift;
+    }
+
+    enum Verdict { kEngage = 0, kSwitchedOff, kNotAnyOrder, kDenseRegime, kNoSpatialCopy, kHeld, kCapTooSmall, kWideSplats };
+    // any_order: the frame is bin-local with bins of <= 8 x 8 tiles; planes_regime: the scene is below dense_min
+    Verdict decide(bool any_order, bool planes_regime, bool spatial_copy, uint32_t width, uint32_t height, int bin_shift,
+                   uint32_t cand_capacity, uint32_t bins) const {
+        if (mode == 0) return kSwitchedOff;
+        if (!any_order) return kNotAnyOrder;
+        if (!planes_regime) return kDenseRegime;
+        if (hold != 0) return kHeld;
+        const uint32_t cap = region_cap(cand_capacity, bins);
+        if (cap == 0) return kCapTooSmall;
+        if (mode == 1) return kEngage;
+        if (!spatial_copy) return kNoSpatialCopy;
+        if (knows(width, height, bin_shift)) {  // (no frame of this shape has retired yet: engage, the frame tells)
+            if ((uint64_t)last_e1 > (uint64_t)kWideRatio * last_v) return kWideSplats;
+            if (!cap_suffices(cap, last_max_bin)) return kCapTooSmall;
+        }
+        return kEngage;
+    }
+    // The candidates the buffer should hold for the path to engage, when `cap` alone keeps the frame on the three-kernel path
+    // (decide() == kCapTooSmall by rule); 0: leave the buffer alone (nothing to gain, or beyond the ceiling).
+    uint32_t grow_to(Verdict v, uint32_t width, uint32_t height, int bin_shift, uint32_t cand_capacity, uint32_t bins,
+                     uint32_t default_cand_capacity) const {
+        if (v != kCapTooSmall || mode != -1 || !knows(width, height, bin_shift)) return 0;
+        const uint64_t cap = ((uint64_t)last_max_bin * 5 + 3) / 4 + last_max_bin / 4;  // 5/4, and as much again as head-room: a moving camera
+        const uint64_t want = cap * bins;
+        if (want <= cand_capacity || want > (uint64_t)kGrowCeiling * default_cand_capacity) return 0;
+        return (uint32_t)want;
+    }
+    void frame_retired(uint32_t width, uint32_t height, int bin_shift, uint32_t max_bin, uint32_t e1, uint32_t v) {
+        if (hold != 0) --hold;
+        have_last = true;
+        last_width = width, last_height = height, last_bin_shift = bin_shift;
+        last_max_bin = max_bin, last_e1 = e1, last_v = v;
+    }
+    // a frame that ran the one-pass level 1 came back with a region overflow: the queued frames re-run on the three kernels
+    void region_overflowed() { hold = kHold; }
+};
+
 }  // namespace gs_host

@@ -54,6 +54,7 @@ struct AttrView {
     uint32_t* tiles;     // tiles_overlap (0 = culled)      } written by k_preprocess only when `vis` is null (the plane-input
     float* depth;        //                                 } level 1, the global path, bins of >= 16 x 16 tiles read them);
     ushort4* aabb;       //                                 } with the dense lists: rebuilt on demand for the stage taps
+                         // (nor are they written by a frame of the one-pass level 1, L1Fused below: rebuilt from its records)
     AttrRecord* rec;     // written for visible Gaussians only
     // Optional (null: not written): the frame's visible Gaussians as DENSE lists in any order, 16 bytes each --
     // {id, depth bits, tile box x0 | y0 << 16, x1 | y1 << 16} -- which the level-1 kernels of the bin-local path stream
@@ -69,6 +70,26 @@ struct AttrView {
 constexpr uint32_t kVisRegions = 256, kVisCounterStride = 32;  // a counter per 128 bytes
 // slots per list for a scene of n Gaussians: what the workgroups (of 256) that append to it can hold, a whole number of level-1 blocks
 uint32_t vis_region_slots(uint32_t n);
+
+// The ONE-PASS level 1 (round 16; bin-local path, bins of <= 8 x 8 tiles, scenes below dense_min that have their spatial copy):
+// k_preprocess files its visible Gaussians' candidate records itself, and k_l1_hist / k_l1_scan / k_l1_scatter_any_order are not
+// launched.  Bin b -- counted over the ON-SCREEN bins, row by row -- owns the region [b cap, (b + 1) cap) of the candidate buffer,
+// cap = cand_capacity / on-screen bins; a workgroup counts its Gaussians per bin in LDS and takes its run of every bin it touches
+// with one returning atomic add on that bin's cursor.  The scene's spatial (Morton) copy is what makes this cheap: 256 consecutive
+// Gaussians touch 4 bins or so, not 100 (profiles/r16_atomic_rate_sparse.txt).  `words`: one counter per 128 bytes -- kVisRegions
+// counters of visible Gaussians (V, summed by level 2), then the cursor of every padded bin; the frame's last kernel (k_frame_end)
+// zeroes them for the buffer set's next frame.  Such a frame's k_preprocess writes no tiles / depth / aabb planes (nothing of the
+// frame reads them; the stage taps rebuild them: launch_records_to_planes).  A cursor ends at the bin's TRUE count whatever its region holds: level 2 reads its
+// bin's count there (and b cap as its offset), flags a region that ran over, and adds up E1 and the fullest bin.
+constexpr uint32_t kL1FusedStride = 32, kL1FusedCursor0 = kVisRegions, kL1FusedWords = (kVisRegions + 1024) * kL1FusedStride;
+struct L1Fused {
+    uint32_t* words;  // null: the three level-1 kernels run
+    uint32_t* cand;
+    uint32_t cap;     // records per bin region
+    uint64_t* vis_mask;  // [ceil(n / 64)] bit j % 64 of word j / 64: the j-th Gaussian in the order read is visible (instead of the planes)
+    uint32_t tiles_x, tiles_y, bins_x, bins_y;
+    int bin_shift, grid_shift;
+};
 
 // Device-resident frame counters.
 struct Counters {
@@ -145,9 +166,10 @@ void launch_scene_export_records(float* records, const float* blob, uint32_t str
 // antialiased: the records carry opacity * sqrt(det(cov2D) / det(cov2D + 0.3 I)) and that opacity's alpha cut, taken per
 // frame (gs_set_antialiased); sv.acut is not read.  Everything else the kernel writes is the same either way.
 void launch_preprocess(const SceneView& sv, const gs_uniforms& u, const AttrView& av, Counters* counters,
-                       const FrameParams* fp, uint64_t* stamps, bool antialiased, hipStream_t s);
-// behind the frame's last kernel: stamps[ST_END] = now, the stamps copied to host_stamps (pinned; fp non-null: fp->host_stamps)
-void launch_frame_end(uint64_t* stamps, uint64_t* host_stamps, const FrameParams* fp, hipStream_t s);
+                       const FrameParams* fp, uint64_t* stamps, bool antialiased, const L1Fused& lf, hipStream_t s);
+// behind the frame's last kernel: stamps[ST_END] = now, the stamps copied to host_stamps (pinned; fp non-null: fp->host_stamps);
+// l1_words (nullable): the first l1_counters counters of L1Fused::words are zeroed for the next frame on these buffers
+void launch_frame_end(uint64_t* stamps, uint64_t* host_stamps, const FrameParams* fp, uint32_t* l1_words, uint32_t l1_counters, hipStream_t s);
 
 // Stable LSD radix pass on (u32 key, u32 value) pairs, 8-bit digit at `shift` (the global depth order).
 //   first != 0: the input is (key = bits(depth[i]), value = i) for every i < n_static with tiles[i] != 0
@@ -194,6 +216,8 @@ struct BinLaunch {
     Counters* counters;
     uint32_t capacity;          // tile instances the lists hold
     uint32_t cand_capacity;     // level-1 candidates the candidate buffer holds
+    const uint32_t* l1_fused_words;  // non-null: level 1 ran inside k_preprocess (L1Fused) -- a bin's count is its cursor, its offset
+    uint32_t l1_fused_cap;           // (on-screen index) x this; level 2 produces V, E1, the fullest bin and the overflow flag
     void* slabs;                // [slab_capacity] 288-byte depth-slab descriptors (level 4)
     uint32_t slab_capacity;
     uint32_t slab_epoch;        // != 0: level 4 as ONE launch (k_bin_queue); a value no earlier launch on these descriptors carried
@@ -206,6 +230,9 @@ struct BinLaunch {
 // tiles / depth / aabb of the visible Gaussians rebuilt from the dense lists of the frame that just ran (stage taps: k_preprocess
 // writes no planes when level 1 streams the lists); av.vis must be the lists of that frame
 void launch_vis_to_planes(const AttrView& av, uint32_t n, hipStream_t s);
+// the same after a frame of the one-pass level 1 (L1Fused): from its visibility bits and records; perm: SceneView::perm of that frame
+void launch_records_to_planes(const uint64_t* vis_mask, const uint32_t* perm, const AttrView& av, uint32_t n, uint32_t width, uint32_t height,
+                              hipStream_t s);
 uint32_t bin_level1_blocks(uint32_t n_items);
 uint32_t bin_level1_columns(uint32_t n_items);  // columns of the hist table: level-1 blocks over the planes or over the dense lists, whichever is more
 void bin_debug_occupancy();

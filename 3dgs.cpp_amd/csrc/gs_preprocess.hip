@@ -1,10 +1,11 @@
 // gs_preprocess.hip -- k_preprocess: cull, EWA conic, radius, tile box, SH -> RGB; one lane per Gaussian.
+// Optionally (k_preprocess<*, 4 / 16>) level 1 of the tile binning in the same pass: the candidate records of the bins a Gaussian touches.
 //
 // Part of libgs3d_hip.so (gfx950 only).  Built with -ffp-contract=off: the floating-point contract of this path is "IEEE
 // binary32, one rounding per operation, in the order the reference shader writes it" (DESIGN.md section 3); fused
 // multiply-adds appear only where written explicitly.
 // Reference restated (paths relative to /root/reference/src/shaders): preprocess.comp:34-183
-#include "gs_device.h"
+#include "gs_bin.h"
 
 namespace gs {
 
@@ -23,6 +24,14 @@ struct PreUniforms {
     Counters* counters;      // nullable
     const FrameParams* fp;   // nullable: the uniforms live there (graph replay)
     uint64_t* stamps;        // nullable: the frame's timeline
+};
+
+// The one-pass level 1 (R1 != 0; gs_kernels.h: L1Fused): the workgroup's table of its bins -- first how many of its Gaussians touch each
+// bin, then (the same words) the next free slot of its run in each bin's region of the candidate buffer -- and its count of visible ones.
+template <int R1>
+struct PreBins {
+    uint32_t tbl[R1 ? 64 * R1 : 1];
+    uint32_t vis;
 };
 
 // Wave-private LDS of k_preprocess: the attribute records of a wave's 64 Gaussians on their way to HBM, four planes of
@@ -101,9 +110,11 @@ struct ShFromLds16 {
 // wave-cooperative parts).  stage: this wave's kPreStage float4 of LDS.
 // AA: the antialiased mode (gs_set_antialiased) -- the record carries the opacity scaled by the view-dependent factor that pays
 // for the 0.3 dilation, and that opacity's own alpha cut; nothing else of the frame changes.
-template <bool AA>
+// R1 != 0: the one-pass level 1 -- the workgroup files its visible Gaussians' candidate records itself (every thread of the workgroup
+// is in here: workgroup barriers); bins = its table, 64 R1 bins as in the level-1 kernels.
+template <bool AA, int R1>
 __device__ __forceinline__ void preprocess_one(const SceneView& sv, const gs_uniforms& u, const AttrView& av, uint32_t i,
-                                               bool valid, float4* __restrict__ stage) {
+                                               bool valid, float4* __restrict__ stage, const L1Fused& lf, PreBins<R1>& bins) {
     const size_t N = sv.stride, NC = sv.n;
     const float* __restrict__ blob = sv.blob;
     const uint32_t lane = threadIdx.x & (WAVE - 1);
@@ -240,6 +251,45 @@ __device__ __forceinline__ void preprocess_one(const SceneView& sv, const gs_uni
             vis_base = region * av.vis_region_slots + atomicAdd(av.vis_count + region * kVisCounterStride, (uint32_t)__popcll(m));
     }
 
+    // ---- one-pass level 1, first half: count per bin in LDS, then ONE returning atomic per (workgroup, bin it touches) reserves the
+    // workgroup's run in the bin's region; the round trip rides behind the SH fetch, as the dense lists' does.  No workgroup ever waits
+    // for another: a reservation is an atomic add, nothing is polled.
+    uint32_t bb = 0;  // the Gaussian's box in bins, packed as l1_item packs it (0: covers nothing)
+    uint32_t fbase[R1 ? (64 * R1) / BLOCK : 1];
+    if constexpr (R1 != 0) {
+        constexpr int NB = 64 * R1;
+        const int tid = threadIdx.x;
+        if (vis) {
+            const uint32_t x0 = (uint32_t)bx0 >> lf.bin_shift, y0 = (uint32_t)by0 >> lf.bin_shift;
+            const uint32_t x1 = (((uint32_t)bx1 - 1u) >> lf.bin_shift) + 1u, y1 = (((uint32_t)by1 - 1u) >> lf.bin_shift) + 1u;
+            bb = x0 | (y0 << 8) | (x1 << 16) | (y1 << 24);
+        }
+        __syncthreads();  // the table is zeroed (k_preprocess, at its start)
+        {
+            const uint32_t x0 = bb & 255u, y0 = (bb >> 8) & 255u, x1 = (bb >> 16) & 255u, y1 = bb >> 24;
+            const bool big = (x1 - x0) * (y1 - y0) > kL1BigBox;  // spread over the wave, as k_l1_hist does
+            if (!big)
+                for (uint32_t y = y0; y < y1; ++y)
+                    for (uint32_t x = x0; x < x1; ++x) atomicAdd(&bins.tbl[(y << lf.grid_shift) | x], 1u);
+            for (uint64_t bm = __ballot(big); bm != 0; bm &= bm - 1) {
+                const uint32_t b1 = (uint32_t)__builtin_amdgcn_readlane((int)bb, __ffsll((unsigned long long)bm) - 1);
+                const uint32_t gx0 = b1 & 255u, gy0 = (b1 >> 8) & 255u, bw = ((b1 >> 16) & 255u) - gx0, cells = bw * ((b1 >> 24) - gy0);
+                for (uint32_t c = lane; c < cells; c += WAVE) atomicAdd(&bins.tbl[((gy0 + c / bw) << lf.grid_shift) | (gx0 + c % bw)], 1u);
+            }
+            const uint32_t nv = (uint32_t)__popcll(__ballot(vis));
+            if (lane == 0 && nv) atomicAdd(&bins.vis, nv);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < NB / BLOCK; ++k) {
+            const uint32_t b = (uint32_t)(k * BLOCK + tid), cnt = bins.tbl[b];
+            fbase[k] = cnt ? atomicAdd(lf.words + (size_t)(kL1FusedCursor0 + b) * kL1FusedStride, cnt) : 0u;
+        }
+        // V: over strided counters (a thousand workgroups on one counter would cost more than the rest of this kernel); level 2 sums them
+        if (tid == 0 && bins.vis)
+            __hip_atomic_fetch_add(lf.words + (size_t)((i / BLOCK) % kVisRegions) * kL1FusedStride, bins.vis, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+
     // ---- the SH block of the visible Gaussians: 48 contiguous floats each (192 B = three 64-byte lines); only lanes
     // that survived every cull need them, so SH traffic is 192 B per VISIBLE Gaussian.
     float rgb[3] = {0.0f, 0.0f, 0.0f};
@@ -289,7 +339,8 @@ __device__ __forceinline__ void preprocess_one(const SceneView& sv, const gs_uni
             } else {
                 sh_to_rgb(ShFromLds{reinterpret_cast<const float*>(blk)}, x, y, z, rgb);
             }
-            if (!av.vis) {  // (with the dense lists the entry below carries depth and box: the N-wide planes are not written at all)
+            if (!av.vis && R1 == 0) {  // (with the dense lists the entry below carries depth and box: the N-wide planes are not written at all;
+                                       // nor by the one-pass level 1: see below)
                 av.depth[oid] = depth;
                 av.aabb[oid] = make_ushort4((unsigned short)bx0, (unsigned short)by0, (unsigned short)bx1, (unsigned short)by1);
             }
@@ -301,7 +352,55 @@ __device__ __forceinline__ void preprocess_one(const SceneView& sv, const gs_uni
     // :128 / :176.  With the dense lists of visible Gaussians (av.vis) nothing downstream reads the N-wide planes tiles / depth /
     // aabb -- level 1 streams the lists, level 2 the candidate records -- so they are not written: a culled Gaussian writes
     // nothing at all (the stage taps rebuild the planes from the lists: launch_vis_to_planes)
-    if (valid && !av.vis) av.tiles[oid] = num_tiles;
+    // Nor does the one-pass level 1 (R1 != 0) write them: nothing of its frame reads them, and by scene id from a scene read in
+    // spatial order they are a 4-byte store per Gaussian and 12 per visible one, each to a line of its own (36 us of k_preprocess's
+    // 74 at 1 M Gaussians, profiles/r16_l1_one_pass_ab.txt).  It writes which Gaussians are visible instead, a bit each in the order
+    // read (8 bytes per wave); with the records that is all the taps need (launch_records_to_planes).
+    if (R1 == 0 && valid && !av.vis) av.tiles[oid] = num_tiles;
+    if constexpr (R1 != 0) {
+        const uint64_t m = __ballot(vis);
+        if (lane == 0 && valid) lf.vis_mask[i / WAVE] = m;
+    }
+
+    // ---- one-pass level 1, second half: the table now holds each touched bin's next free slot; the records are the ones
+    // k_l1_scatter_any_order writes.  Bin b (counted over the on-screen bins) owns [b cap, (b + 1) cap) of the candidate buffer; a
+    // slot beyond the region is not written -- the bin's cursor still ends at the true count, and level 2, which reads it, flags the
+    // overflow (the frame is re-run).  The order inside a bin differs from run to run: level 2 orders by (depth bits, id).
+    if constexpr (R1 != 0) {
+        constexpr int NB = 64 * R1;
+#pragma unroll
+        for (int k = 0; k < NB / BLOCK; ++k) bins.tbl[k * BLOCK + (int)threadIdx.x] = fbase[k];  // (an untouched bin: 0 over 0)
+        __syncthreads();
+        const BinGrid g{lf.tiles_x, lf.tiles_y, lf.bins_x, lf.bins_y, lf.bin_shift, lf.grid_shift};
+        auto emit = [&](uint32_t bin, uint32_t k, uint32_t gid, ushort4 box) {
+            const uint32_t pos = atomicAdd(&bins.tbl[bin], 1u);
+            if (pos < lf.cap) {
+                const uint32_t sb = (bin >> lf.grid_shift) * lf.bins_x + (bin & ((1u << lf.grid_shift) - 1u));
+                uint32_t* const rec = lf.cand + (size_t)kCandWords * ((size_t)sb * lf.cap + pos);  // three adjacent dwords: one 12-byte store
+                rec[0] = k;
+                rec[1] = gid;
+                rec[2] = bin_local_box16(g, bin, box);
+            }
+        };
+        const uint32_t x0 = bb & 255u, y0 = (bb >> 8) & 255u, x1 = (bb >> 16) & 255u, y1 = bb >> 24;
+        const ushort4 tb = make_ushort4((unsigned short)bx0, (unsigned short)by0, (unsigned short)bx1, (unsigned short)by1);
+        const uint32_t key = __float_as_uint(depth);
+        const bool big = (x1 - x0) * (y1 - y0) > kL1BigBox;
+        if (!big)
+            for (uint32_t y = y0; y < y1; ++y)
+                for (uint32_t x = x0; x < x1; ++x) emit((y << lf.grid_shift) | x, key, oid, tb);
+        for (uint64_t bm = __ballot(big); bm != 0; bm &= bm - 1) {  // one Gaussian at a time, one bin per lane
+            const int src = __ffsll((unsigned long long)bm) - 1;
+            const uint32_t b1 = (uint32_t)__builtin_amdgcn_readlane((int)bb, src);
+            const uint32_t gx0 = b1 & 255u, gy0 = (b1 >> 8) & 255u, bw = ((b1 >> 16) & 255u) - gx0, cells = bw * ((b1 >> 24) - gy0);
+            const uint32_t bkey = (uint32_t)__builtin_amdgcn_readlane((int)key, src), bgid = (uint32_t)__builtin_amdgcn_readlane((int)oid, src);
+            const uint32_t blo = (uint32_t)__builtin_amdgcn_readlane((int)((uint32_t)bx0 | ((uint32_t)by0 << 16)), src);
+            const uint32_t bhi = (uint32_t)__builtin_amdgcn_readlane((int)((uint32_t)bx1 | ((uint32_t)by1 << 16)), src);
+            const ushort4 bbox = make_ushort4((unsigned short)(blo & 0xFFFFu), (unsigned short)(blo >> 16), (unsigned short)(bhi & 0xFFFFu),
+                                              (unsigned short)(bhi >> 16));
+            for (uint32_t c = lane; c < cells; c += WAVE) emit(((gy0 + c / bw) << lf.grid_shift) | (gx0 + c % bw), bkey, bgid, bbox);
+        }
+    }
 
     // ---- the 64-byte-strided record of every visible Gaussian.  Wave-cooperative: the records pass through LDS and four
     // lanes write one record -- ONE 64-byte request per visible Gaussian (the last quarter: depth and radius, for the taps) instead of three
@@ -340,9 +439,14 @@ __device__ __forceinline__ void preprocess_one(const SceneView& sv, const gs_uni
     }
 }
 
-template <bool AA>
-__global__ __launch_bounds__(BLOCK) void k_preprocess(SceneView sv, PreUniforms pu, AttrView av) {
+template <bool AA, int R1>
+__global__ __launch_bounds__(BLOCK) void k_preprocess(SceneView sv, PreUniforms pu, AttrView av, L1Fused lf) {
     __shared__ float4 s_stage[BLOCK / WAVE][kPreWaveLds];
+    __shared__ PreBins<R1> s_bins;
+    if constexpr (R1 != 0) {  // (the barrier that orders this before the counting: preprocess_one, after the culls)
+        for (int b = threadIdx.x; b < 64 * R1; b += BLOCK) s_bins.tbl[b] = 0;
+        if (threadIdx.x == 0) s_bins.vis = 0;
+    }
     const gs_uniforms& u = pu.fp ? pu.fp->u : pu.u;  // uniform either way: scalar loads
     const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
     frame_stamp(pu.stamps, ST_PREPROCESS);
@@ -358,20 +462,61 @@ __global__ __launch_bounds__(BLOCK) void k_preprocess(SceneView sv, PreUniforms 
         pu.counters->q_head = 0;
         pu.counters->q_bins_done = 0;
     }
-    preprocess_one<AA>(sv, u, av, i, i < sv.n, s_stage[threadIdx.x / WAVE]);
+    preprocess_one<AA, R1>(sv, u, av, i, i < sv.n, s_stage[threadIdx.x / WAVE], lf, s_bins);
+}
+
+// Stage taps after a frame of the one-pass level 1 (k_preprocess wrote no planes): tiles_overlap, depth and the tile box of every
+// visible Gaussian from its record -- the depth as stored, the box by the operations k_preprocess takes it with (:160-165) from the
+// record's uv and radius -- and tiles_overlap = 0 for the others.  j: the Gaussian's place in the order the frame read the scene in.
+__global__ __launch_bounds__(BLOCK) void k_records_to_planes(const uint64_t* __restrict__ vis_mask, const uint32_t* __restrict__ perm,
+                                                             const AttrRecord* __restrict__ rec, uint32_t n, uint32_t width, uint32_t height,
+                                                             uint32_t* __restrict__ tiles, float* __restrict__ depth, ushort4* __restrict__ aabb) {
+    const uint32_t j = blockIdx.x * BLOCK + threadIdx.x;
+    if (j >= n) return;
+    const uint32_t oid = perm ? perm[j] : j;
+    uint32_t nt = 0;
+    if ((vis_mask[j / WAVE] >> (j % WAVE)) & 1ull) {
+        const AttrRecord r = rec[oid];
+        const int tile_w = (int)((width + kTile - 1) / kTile), tile_h = (int)((height + kTile - 1) / kTile);
+        const float uvx = r.uv_rg.x, uvy = r.uv_rg.y, radii = r.depth_radius.y;
+        const int bx0 = clampi(f2i_sat((uvx - radii) / kTile), 0, tile_w);
+        const int by0 = clampi(f2i_sat((uvy - radii) / kTile), 0, tile_h);
+        const int bx1 = clampi(f2i_sat((uvx + radii + kTile - 1) / kTile), 0, tile_w);
+        const int by1 = clampi(f2i_sat((uvy + radii + kTile - 1) / kTile), 0, tile_h);
+        nt = (uint32_t)(bx1 - bx0) * (uint32_t)(by1 - by0);
+        depth[oid] = r.depth_radius.x;
+        aabb[oid] = make_ushort4((unsigned short)bx0, (unsigned short)by0, (unsigned short)bx1, (unsigned short)by1);
+    }
+    tiles[oid] = nt;
+}
+void launch_records_to_planes(const uint64_t* vis_mask, const uint32_t* perm, const AttrView& av, uint32_t n, uint32_t width, uint32_t height,
+                              hipStream_t s) {
+    if (n == 0) return;
+    hipLaunchKernelGGL(k_records_to_planes, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, vis_mask, perm, av.rec, n, width, height, av.tiles,
+                       av.depth, av.aabb);
 }
 
 void launch_preprocess(const SceneView& sv, const gs_uniforms& u, const AttrView& av, Counters* counters,
-                       const FrameParams* fp, uint64_t* stamps, bool antialiased, hipStream_t s) {
+                       const FrameParams* fp, uint64_t* stamps, bool antialiased, const L1Fused& lf, hipStream_t s) {
     if (sv.n == 0) return;
     PreUniforms pu;
     pu.u = u;
     pu.counters = counters;
     pu.fp = fp;
     pu.stamps = stamps;
-    if (antialiased)
-        hipLaunchKernelGGL(k_preprocess<true>, dim3((sv.n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, sv, pu, av);
-    else
-        hipLaunchKernelGGL(k_preprocess<false>, dim3((sv.n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, sv, pu, av);
+    const dim3 grid((sv.n + BLOCK - 1) / BLOCK);
+    const int r1 = !lf.words ? 0 : (lf.grid_shift == 4 ? 4 : 16);  // the table's bins: 64 R1, as the level-1 kernels size theirs
+#define GS_PRE_CASE(A, R)                                                                       \
+    if (antialiased == A && r1 == R) {                                                          \
+        hipLaunchKernelGGL((k_preprocess<A, R>), grid, dim3(BLOCK), 0, s, sv, pu, av, lf);      \
+        return;                                                                                 \
+    }
+    GS_PRE_CASE(false, 0)
+    GS_PRE_CASE(false, 4)
+    GS_PRE_CASE(false, 16)
+    GS_PRE_CASE(true, 0)
+    GS_PRE_CASE(true, 4)
+    GS_PRE_CASE(true, 16)
+#undef GS_PRE_CASE
 }
 }  // namespace gs

@@ -37,7 +37,10 @@ struct FrameBuffers {
     DevBuf<gs::AttrRecord> rec;  // one 64-byte record per Gaussian: what the blend gathers
     DevBuf<uint4> vis;           // the frame's visible Gaussians as dense lists (gs::AttrView::vis): level 1's input on the bin-local path
     DevBuf<uint32_t> vis_count;  // the lists' counters, one per 128 bytes (the word behind each: the finished frame's count)
-    bool planes_stale = false;   // the last frame on this set streamed the dense lists: tiles / depth / aabb were not written (taps rebuild them)
+    // what the last frame on this set left of tiles / depth / aabb: written (0), or for the taps to rebuild -- from the dense lists it
+    // streamed (1), or, a frame of the one-pass level 1, from its visibility bits and records (2)
+    int planes_stale = 0;
+    DevBuf<uint64_t> vis_mask;   // the one-pass level 1's visibility bits (gs::L1Fused::vis_mask)
     uint32_t vis_region_slots = 0;
     // global depth order (only allocated when that path is taken)
     DevBuf<uint32_t> dkeys[2], dvals[2];
@@ -45,6 +48,7 @@ struct FrameBuffers {
     // two-level binning
     DevBuf<uint32_t> l1_hist, bin_count;  // [padded bins][level-1 blocks], [1024 counts + 1024 offsets]
     DevBuf<uint32_t> cand;                // [3 x cand_capacity] bin-major candidates: 12-byte records {depth bits, id, box} on the bin-local path, plain ids otherwise
+    DevBuf<uint32_t> l1_words;            // the one-pass level 1's counters (gs::L1Fused::words), zero between frames
     DevBuf<uint32_t> sorted;              // [capacity + 4] per-tile lists, bin-major
     DevBuf<uint32_t> ranges;              // [T][2]
     DevBuf<uint8_t> slabs;                // depth-slab descriptors (level 4; allocated on first use)
@@ -59,12 +63,12 @@ struct FrameBuffers {
     // (an aggregate: enqueue initialises the fields positionally, in the order they are declared and compared here)
     struct GraphKey {
         int level = -1, bin_shift = -1, hw_exp = 0, contract = 1;
-        bool antialiased = false, lockstep = false;
+        bool antialiased = false, lockstep = false, l1_fused = false;
         uint32_t width = 0, height = 0, capacity = 0, cand_capacity = 0;
         const void *tile_order = nullptr, *ranges = nullptr, *sh16 = nullptr;
         bool operator==(const GraphKey& o) const {
             return level == o.level && bin_shift == o.bin_shift && hw_exp == o.hw_exp && contract == o.contract &&
-                   antialiased == o.antialiased && lockstep == o.lockstep &&
+                   antialiased == o.antialiased && lockstep == o.lockstep && l1_fused == o.l1_fused &&
                    width == o.width && height == o.height && capacity == o.capacity && cand_capacity == o.cand_capacity &&
                    tile_order == o.tile_order && ranges == o.ranges && sh16 == o.sh16;
         }
@@ -92,6 +96,9 @@ struct FrameBuffers {
         if (dense_lists) ensure_dense_lists();  // only scenes of >= dense_min Gaussians ever use them (16 B x N)
         l1_hist.alloc(1025 * static_cast<size_t>(gs::bin_level1_columns(static_cast<uint32_t>(n))));  // + the row of visible counts
         bin_count.alloc(2048);  // counts, then offsets (gs_bin.h: kBinOffsets)
+        vis_mask.alloc((n + 63) / 64 + 1);
+        l1_words.alloc(gs::kL1FusedWords);
+        HIP_CHECK(hipMemset(l1_words.p, 0, l1_words.n * sizeof(uint32_t)));  // every one-pass frame's LAST kernel zeroes them again
         counters.alloc(1);
         stamps.alloc(gs::ST_COUNT);
         HIP_CHECK(hipMemset(stamps.p, 0, gs::ST_COUNT * sizeof(uint64_t)));
@@ -147,6 +154,8 @@ struct FrameSlot {
     int level = 0;  // the depth-order level this frame ran at (DepthPolicy::frame_level)
     int bin_shift = 3;
     bool lockstep = false;      // the blend's lockstep setting this frame ran with
+    bool l1_fused = false;      // k_preprocess filed the level-1 candidates itself (gs::L1Fused) ...
+    uint32_t l1_cap = 0;        // ... into bin regions of this many records
     uint32_t tune_round = 0;    // ... and the tuner's round it belongs to (samples of an earlier round are ignored)
     int tune_shape = 0;         // ... and which of the bank's tuners (one per frame shape) that was
 };
@@ -165,6 +174,10 @@ struct gs_renderer {
     int num_sets = 1;
     uint32_t capacity = 0;       // tile instances (D) the list buffers hold
     uint32_t cand_capacity = 0;  // level-1 candidates (E1) the candidate buffers hold
+    uint32_t default_cand_capacity = 0;  // ... and what they held at creation (L1FusedPolicy::grow_to's ceiling is a multiple of it)
+    // The one-pass level 1 (gs_kernels.h: L1Fused): when a frame takes it is L1FusedPolicy's rule; GS_L1_FUSED / gs_set_level1_fused set its mode
+    L1FusedPolicy l1_policy;
+    bool last_l1_fused = false;  // the most recently enqueued frame took it (gs_get_level1_fused)
     FrameBuffers* last_set = nullptr;  // buffers of the most recently enqueued frame (stage taps, gs_accumulate_contributions)
     uint32_t last_width = 0, last_height = 0;  // ... and that frame's size
 
@@ -204,6 +217,12 @@ struct gs_renderer {
     // trips and k_preprocess pays 2 us for the lists; 2 M and 3.5 M, profiles/r03_l1_dense_threshold.txt: -2.2 % / -0.5 %
     // one frame at a time, +0.5 % with three in flight).  The GPU tests set it to 0 for small scenes.
     uint64_t dense_min = 4u << 20;
+    // A scene that has its spatial copy (gs_scene: from 512 Ki Gaussians on) takes the lists below dense_min as well whenever it runs
+    // the three any-order level-1 kernels -- the fall-back of the one-pass level 1: read in spatial order, the N-wide planes are
+    // written by scene id, a store per Gaussian to a line of its own (B: 4 430 frames/s over the planes, 4 960 over the lists,
+    // profiles/r16_l1_one_pass_ab.txt).  An explicit GS_L1_DENSE_MIN is taken at its word.
+    bool dense_for_spatial = std::getenv("GS_L1_DENSE_MIN") == nullptr;
+    bool wants_dense_lists() const { return scene->n >= dense_min || (dense_for_spatial && scene->perm.p); }
     bool debug_levels = std::getenv("GS_DEBUG_LEVELS") != nullptr;
     bool level2_queue = !(std::getenv("GS_L2_QUEUE") && std::atoi(std::getenv("GS_L2_QUEUE")) == 0);
     // GS_DEBUG_STALLS=<ms>: a gs_render call that keeps the host longer than this is reported on stderr with the time each of
@@ -285,12 +304,13 @@ struct gs_renderer {
         if (const char* e = std::getenv("GS_INITIAL_CAND_CAPACITY")) want_cand = std::max<uint64_t>(256, std::strtoull(e, nullptr, 10));
         else if (std::getenv("GS_INITIAL_CAPACITY")) want_cand = std::min<uint64_t>(want_cand, want);  // (the tests' small start applies to both)
         cand_capacity = static_cast<uint32_t>(std::min<uint64_t>(want_cand, capacity));
-        sets[0].init(scene->n, capacity, cand_capacity, scene->n >= dense_min);
+        default_cand_capacity = cand_capacity;
+        sets[0].init(scene->n, capacity, cand_capacity, wants_dense_lists());
     }
 
     void set_num_sets(int k) {
         for (int i = 0; i < k; ++i)
-            if (!sets[i].ready) sets[i].init(scene->n, capacity, cand_capacity, scene->n >= dense_min);
+            if (!sets[i].ready) sets[i].init(scene->n, capacity, cand_capacity, wants_dense_lists());
         num_sets = k;
     }
 
@@ -366,6 +386,25 @@ struct gs_renderer {
                 HIP_CHECK(hipMemset(fb.slabs.p, 0, fb.slabs.n));  // no descriptor carries a launch's epoch yet
             }
         }
+        const bool fused_counters = n != 0 && u.width != 0 && u.height != 0;
+        // ---- the one-pass level 1: does this frame take it (L1FusedPolicy)?  Kept off only by bin regions that are too small, the
+        // candidate buffers grow once (which waits for the queued frames: the verdict is taken again after the wait)
+        auto l1_verdict = [&]() {
+            const BinGeometry g = bin_geometry(tx, ty);
+            const int at_level = policy.frame_level();
+            return l1_policy.decide(at_level < kGlobalLevel && g.bin_shift <= 3, n < dense_min, scene->perm.p != nullptr, u.width, u.height,
+                                    g.bin_shift, cand_capacity, g.bins_x * g.bins_y);
+        };
+        if (fused_counters) {
+            const BinGeometry g = bin_geometry(tx, ty);
+            if (l1_policy.grow_to(l1_verdict(), u.width, u.height, g.bin_shift, cand_capacity, g.bins_x * g.bins_y, default_cand_capacity) != 0) {
+                drain();
+                const BinGeometry g2 = bin_geometry(tx, ty);
+                const uint32_t grow = l1_policy.grow_to(l1_verdict(), u.width, u.height, g2.bin_shift, cand_capacity, g2.bins_x * g2.bins_y,
+                                                        default_cand_capacity);
+                if (grow > cand_capacity) set_cand_capacity(grow);
+            }
+        }
         // (after any drain above: retiring may re-run frames through enqueue, which would leave another set's buffers here)
         last_set = &fb;
         last_width = u.width;
@@ -387,14 +426,17 @@ struct gs_renderer {
         // list of visible Gaussians, which k_preprocess then writes beside the planes
         const bool l1_any_order = bin_local && geo.bin_shift <= 3;
         // (the lists exist only for scenes of >= dense_min Gaussians: FrameBuffers::init; the blend zeroes their counters)
-        const bool dense_list = l1_any_order && n != 0 && n >= dense_min && fb.vis.p && u.width != 0 && u.height != 0;
+        const bool l1_fused = fused_counters && l1_verdict() == L1FusedPolicy::kEngage;
+        const bool dense_list = l1_any_order && !l1_fused && n != 0 && wants_dense_lists() && fb.vis.p && u.width != 0 && u.height != 0;
         gs::AttrView av{fb.tiles.p, fb.depth.p, fb.aabb.p, fb.rec.p, dense_list ? fb.vis.p : nullptr, dense_list ? fb.vis_count.p : nullptr,
                         fb.vis_region_slots};
-        fb.planes_stale = dense_list;
+        const uint32_t l1_cap = L1FusedPolicy::region_cap(cand_capacity, geo.bins_x * geo.bins_y);
+        const gs::L1Fused lf{l1_fused ? fb.l1_words.p : nullptr, fb.cand.p, l1_cap, fb.vis_mask.p, tx, ty, geo.bins_x, geo.bins_y, geo.bin_shift, geo.grid_shift};
+        fb.planes_stale = dense_list ? 1 : (l1_fused ? 2 : 0);
+        last_l1_fused = l1_fused;
 
         // the first and the last kernel of the frame clear / publish the counters themselves; the blit nodes (and
         // their fences) are only needed when one of the two is not launched
-        const bool fused_counters = n != 0 && u.width != 0 && u.height != 0;
         if (!fused_counters) {
             HIP_CHECK(hipMemsetAsync(cnt, 0, sizeof(gs::Counters), stream));
             HIP_CHECK(hipMemsetAsync(fb.ranges.p, 0, 2 * nt * sizeof(uint32_t), stream));  // no Gaussians: every tile (0, 0)
@@ -402,7 +444,7 @@ struct gs_renderer {
         // the frame's launches; `fp` non-null = replayable form (per-frame values read from fb.params), no span events
         uint64_t* const stamps = fb.stamps.p;
         auto passes = [&](const gs::FrameParams* fp) {
-            gs::launch_preprocess(sv, u, av, cnt, fp, stamps, antialiased, stream);
+            gs::launch_preprocess(sv, u, av, cnt, fp, stamps, antialiased, lf, stream);
             lap(3);
             if (!bin_local && n != 0) {
                 // ---- global depth order of the visible Gaussians: 4 x 8-bit stable passes on bits(depth) ----
@@ -452,6 +494,8 @@ struct gs_renderer {
                 b.counters = cnt;
                 b.capacity = capacity;
                 b.cand_capacity = cand_capacity;
+                b.l1_fused_words = lf.words;
+                b.l1_fused_cap = l1_cap;
                 b.slabs = fb.slabs.p;
                 b.slab_capacity = fb.slabs.p ? gs::kSlabCapacity : 0u;
                 // level 4 as one launch over a queue of bins and slabs -- not in a captured frame (a replay repeats its arguments,
@@ -469,8 +513,11 @@ struct gs_renderer {
                 b.grid_shift = geo.grid_shift;
                 b.stamps = stamps;
                 // ---- level 1: which Gaussian touches which bin (count + scan, then the per-bin candidate lists) ----
-                gs::launch_bin_level1_count(b, stream);
-                gs::launch_bin_level1_scatter(b, l1_any_order, stream);
+                // (one pass: k_preprocess has filed the candidates; level 2 reads the bins' cursors)
+                if (!l1_fused) {
+                    gs::launch_bin_level1_count(b, stream);
+                    gs::launch_bin_level1_scatter(b, l1_any_order, stream);
+                }
                 lap(5);
                 // ---- level 2: order inside the bin (bin-local path), tile ranges, per-tile lists ----
                 gs::launch_bin_level2(b, lv, stream);
@@ -479,7 +526,7 @@ struct gs_renderer {
             // ---- blend ----
             gs::launch_blend(fb.ranges.p, fb.sorted.p, tile_order.p, av, u.width, u.height, d_rgba, d_bgra, cnt,
                              fused_counters ? sl.h_counters : nullptr, blend_exp_mode(), contract, fp, lockstep, stamps, stream);
-            gs::launch_frame_end(stamps, sl.h_stamps, fp, stream);
+            gs::launch_frame_end(stamps, sl.h_stamps, fp, lf.words, gs::kVisRegions + (1u << (2 * geo.grid_shift)), stream);
             lap(7);
         };
         depth_order = bin_local ? nullptr : fb.dvals[1].p;
@@ -489,7 +536,7 @@ struct gs_renderer {
             *sl.h_params = gs::FrameParams{u, d_rgba, d_bgra, sl.h_counters, sl.h_stamps};
             HIP_CHECK(hipMemcpyAsync(fb.params.p, sl.h_params, sizeof(gs::FrameParams), hipMemcpyHostToDevice, stream));
             const FrameBuffers::GraphKey key{lv, geo.bin_shift, blend_exp_mode(), contract ? 1 : 0,
-                                             antialiased, lockstep,
+                                             antialiased, lockstep, l1_fused,
                                              u.width, u.height, capacity, cand_capacity,
                                              tile_order.p, fb.ranges.p, sv.sh16};
             const int gi = lockstep ? 1 : 0;
@@ -521,6 +568,8 @@ struct gs_renderer {
         sl.level = lv;
         sl.bin_shift = geo.bin_shift;
         sl.lockstep = lockstep;
+        sl.l1_fused = l1_fused;
+        sl.l1_cap = l1_cap;
         sl.tune_round = tuner.round;
         sl.tune_shape = tune_shape;
         sl.u = u;
@@ -546,6 +595,7 @@ struct gs_renderer {
         }
         redo_chain = 0;
         policy.frame_retired(sl.level, sl.h_counters->max_bin, sl.bin_shift);
+        l1_policy.frame_retired(sl.u.width, sl.u.height, sl.bin_shift, sl.h_counters->max_bin, sl.h_counters->bin_entries, sl.h_counters->visible);
         last = frame_stats(sl);
         have_frame = true;
         const float v[7] = {last.ms_preprocess, last.ms_prefix_sum, last.ms_preprocess_sort, last.ms_sort,
@@ -575,6 +625,8 @@ struct gs_renderer {
             const gs::Counters& c = *q.h_counters;
             redo.push_back({q.u, q.rgba, q.bgra});
             ran.push_back({q.level, q.bin_shift, q.u.width, q.u.height, c.overflow, c.max_bin});
+            // the one-pass level 1: a bin's region ran over (its cursor ended beyond it) -- the frames re-run on the three kernels
+            if (q.l1_fused && (c.overflow & 1u) && c.max_bin > q.l1_cap) l1_policy.region_overflowed();
             if (c.overflow & 1u) {
                 // which of the two ran over: the level-1 candidates (E1: the frame's instance count then means nothing -- its
                 // bins were skipped) or the per-tile lists (D)
@@ -648,9 +700,10 @@ struct gs_renderer {
             // k_bin_build.  k_bin_build also produces the tile ranges: tile_boundary.comp's work has no kernel of
             // its own any more, so that span is 0 by construction.
             const bool global = sl.level >= kGlobalLevel;  // (only then is ST_ORDER this frame's)
-            st.ms_preprocess = span(gs::ST_PREPROCESS, global ? gs::ST_ORDER : gs::ST_L1_COUNT);
-            st.ms_prefix_sum = span(gs::ST_L1_COUNT, gs::ST_L1_SCATTER);
-            st.ms_preprocess_sort = span(gs::ST_L1_SCATTER, gs::ST_L2);
+            // (one-pass level 1: no level-1 kernel stamped -- the pass is part of k_preprocess, and its two spans are 0)
+            st.ms_preprocess = span(gs::ST_PREPROCESS, global ? gs::ST_ORDER : (sl.l1_fused ? gs::ST_L2 : gs::ST_L1_COUNT));
+            st.ms_prefix_sum = sl.l1_fused ? 0.0f : span(gs::ST_L1_COUNT, gs::ST_L1_SCATTER);
+            st.ms_preprocess_sort = sl.l1_fused ? 0.0f : span(gs::ST_L1_SCATTER, gs::ST_L2);
             st.ms_sort = (global ? span(gs::ST_ORDER, gs::ST_L1_COUNT) : 0.0f) + span(gs::ST_L2, gs::ST_BLEND);
             st.ms_tile_boundary = 0.0f;
             st.ms_render = span(gs::ST_BLEND, gs::ST_END);
@@ -707,6 +760,7 @@ int gs_renderer_create(gs_scene* scene, gs_renderer** out) {
         r->scene = scene;
         if (const char* e = std::getenv("GS_L1_DENSE_MIN")) r->dense_min = std::strtoull(e, nullptr, 10);  // (before init: sizes the buffer sets)
         r->init();
+        if (const char* e = std::getenv("GS_L1_FUSED")) r->l1_policy.mode = std::atoi(e) < 0 ? -1 : (std::atoi(e) != 0 ? 1 : 0);  // initial gs_set_level1_fused
         if (const char* e = std::getenv("GS_GRAPH")) r->graph_mode = std::atoi(e) != 0;  // initial gs_set_graph_mode
         if (const char* e = std::getenv("GS_EXP_MODE")) r->exp_mode = std::min(3, std::max(0, std::atoi(e)));  // initial gs_set_exp_mode
         if (const char* e = std::getenv("GS_BLEND_CONTRACTION")) r->contract = std::atoi(e) != 0;  // initial gs_set_blend_contraction
@@ -913,6 +967,24 @@ int gs_get_blend_lockstep(gs_renderer* r, int* settled) {
     return rc != 0 ? rc : now;
 }
 
+int gs_set_level1_fused(gs_renderer* r, int mode) {
+    return guarded([&] {
+        if (!r) throw Error(GS_ERR_INVALID, "null argument");
+        if (mode < -1 || mode > 1) throw Error(GS_ERR_INVALID, "level-1 fusion: -1 by rule, 0 off, 1 on");
+        r->drain();
+        r->l1_policy.mode = mode;
+    });
+}
+
+int gs_get_level1_fused(gs_renderer* r) {
+    int on = 0;
+    const int rc = guarded([&] {
+        if (!r) throw Error(GS_ERR_INVALID, "null argument");
+        on = r->last_l1_fused ? 1 : 0;  // (the most recently enqueued frame)
+    });
+    return rc != 0 ? rc : on;
+}
+
 int gs_set_graph_mode(gs_renderer* r, int enabled) {
     return guarded([&] {
         if (!r) throw Error(GS_ERR_INVALID, "renderer is null");
@@ -937,11 +1009,13 @@ int gs_debug_download(gs_renderer* r, int stage, void* dst, uint64_t bytes) {
         if (r->last_set->planes_stale && (stage == GS_STAGE_TILES || stage == GS_STAGE_DEPTH || stage == GS_STAGE_AABB)) {
             // the frame streamed the dense lists of visible Gaussians and wrote no per-Gaussian planes: rebuild them from the lists
             FrameBuffers& fb = *r->last_set;
-            gs::launch_vis_to_planes(gs::AttrView{fb.tiles.p, fb.depth.p, fb.aabb.p, fb.rec.p, fb.vis.p, fb.vis_count.p, fb.vis_region_slots},
-                                     static_cast<uint32_t>(n), fb.stream);
+            const gs::AttrView pv{fb.tiles.p, fb.depth.p, fb.aabb.p, fb.rec.p, fb.vis.p, fb.vis_count.p, fb.vis_region_slots};
+            if (fb.planes_stale == 1) gs::launch_vis_to_planes(pv, static_cast<uint32_t>(n), fb.stream);
+            // (... or took the one-pass level 1: from its visibility bits and the records)
+            else gs::launch_records_to_planes(fb.vis_mask.p, r->scene->perm.p, pv, static_cast<uint32_t>(n), r->last_width, r->last_height, fb.stream);
             HIP_CHECK(hipGetLastError());
             HIP_CHECK(hipStreamSynchronize(fb.stream));
-            fb.planes_stale = false;
+            fb.planes_stale = 0;
         }
         switch (stage) {
             case GS_STAGE_TILES: src = r->last_set->tiles.p; size = n * 4; break;

@@ -49,7 +49,7 @@ void gs_scene::drop_spatial_copy() {
 }
 // Spatial order: Morton code of the position (21 bits per axis over the scene's bounding box), ties by id (gs_host_math.h: spatial_order).
 void gs_scene::make_spatial_copy() {
-    uint64_t min_n = 4ull << 20;
+    uint64_t min_n = 1ull << 19;  // (4 Mi until the one-pass level 1, which needs this order: DESIGN.md section 10)
     if (const char* e = std::getenv("GS_SPATIAL_MIN")) min_n = std::strtoull(e, nullptr, 10);
     if (n == 0 || n < min_n) return;
     const size_t st = gs::blob_stride(n);

@@ -396,6 +396,15 @@ int gs_set_blend_lockstep(gs_renderer* r, int mode);
 /* The setting the next frame will run with (0 / 1; negative: error); *settled (nullable) = 1 once the measurement has decided
  * (or the mode is pinned). */
 int gs_get_blend_lockstep(gs_renderer* r, int* settled);
+/* The ONE-PASS level 1: k_preprocess files the level-1 candidate records itself -- one device atomic per (workgroup, bin its 256
+ * Gaussians touch) -- and the three level-1 kernels are not launched.  It changes no output (taps, images and counts are equal
+ * either way).  mode -1 (default): by rule -- bin-local frames with bins of at most 8 x 8 tiles, scenes below the dense-list
+ * threshold that have their spatial copy, a bin region (candidate capacity / bins) of at least 5/4 of the last frame's fullest bin,
+ * and no more than 8 bins per visible Gaussian; 0: never; 1: wherever the frame's structure allows.  A frame whose bin region runs
+ * over is re-run on the three kernels, which then stay for 32 frames.  GS_L1_FUSED=-1 / 0 / 1 sets the initial mode. */
+int gs_set_level1_fused(gs_renderer* r, int mode);
+/* 1: the most recently enqueued frame took the one-pass level 1; 0: it ran the three level-1 kernels (negative: error). */
+int gs_get_level1_fused(gs_renderer* r);
 /* Sums of the per-pass spans over all frames retired since the last reset (ms fields are sums,
  * counts are those of the last frame); *frames = number of frames summed.  Synchronizes. */
 int gs_get_timing_totals(gs_renderer* r, gs_frame_stats* sum, uint64_t* frames, int reset);

@@ -22,7 +22,8 @@ def short(name):
     name = re.sub(r"^void ", "", name)
     name = name.split("(")[0].replace("gs::", "")
     # k_preprocess<false> is the default (non-antialiased) instantiation: the kernel of the earlier runs, under its earlier name
-    return "k_preprocess" if name == "k_preprocess<false>" else name
+    # (... whatever the one-pass level 1 adds to it: <false, 0> the kernel alone, <false, 4> / <false, 16> with the level-1 pass inside)
+    return "k_preprocess" if re.fullmatch(r"k_preprocess<false(, \d+)?>", name) else name
 
 
 def bench_line(path):

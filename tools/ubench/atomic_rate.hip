@@ -19,6 +19,42 @@ __global__ __launch_bounds__(256) void k(uint32_t* c, uint32_t naddr, uint32_t s
     if (RET && acc == 0xFFFFFFFFu) *sink = acc;
 }
 
+// The sparse pattern (round 16): what a k_preprocess that files its own bin candidates would issue when it reads the scene in
+// Morton order -- every workgroup reserves in only the k bins its 256 Gaussians touch: ONE returning atomicAdd per (workgroup, bin),
+// lane j taking address (first + j) % naddr.  `first` moves slowly with the workgroup number, so neighbouring workgroups hit
+// overlapping address sets, as Morton neighbours do.  k == 0: the same kernel without any atomic (the launch floor to subtract).
+__global__ __launch_bounds__(256) void k_sparse(uint32_t* c, uint32_t naddr, uint32_t stride, uint32_t kper, uint32_t* sink) {
+    const uint32_t first = (uint32_t)(((uint64_t)blockIdx.x * naddr) / gridDim.x);
+    uint32_t base = 0;
+    if (threadIdx.x < kper) base = atomicAdd(c + (size_t)((first + threadIdx.x) % naddr) * stride, 1u + (threadIdx.x & 3u));
+    if (base == 0xFFFFFFFFu) *sink = base;
+}
+
+static void run_sparse(uint32_t* c, uint32_t* sink, hipEvent_t e0, hipEvent_t e1) {
+    const uint32_t blocks = 3906, naddr = 135, stride = 32;
+    const uint32_t ks[] = {0, 4, 8, 11, 16, 32, 64, 135};
+    float floor_us = 0.0f;
+    printf("sparse: %u WG, one returning atomicAdd per (WG, address), k of %u addresses 128 B apart per WG, neighbours overlap\n", blocks, naddr);
+    for (uint32_t kper : ks) {
+        float best = 1e9f;
+        for (int rep = 0; rep < 7; ++rep) {
+            hipEventRecord(e0);
+            hipLaunchKernelGGL(k_sparse, dim3(blocks), dim3(256), 0, 0, c, naddr, stride, kper, sink);
+            hipEventRecord(e1);
+            hipEventSynchronize(e1);
+            float ms;
+            hipEventElapsedTime(&ms, e0, e1);
+            if (ms < best) best = ms;
+        }
+        const float us = best * 1e3f;
+        if (kper == 0) floor_us = us;
+        const double n = (double)blocks * kper;
+        printf("  k = %3u  %8.0f atomics (%6.0f per address)  %7.1f us  (%6.1f us over the empty kernel", kper, n, n / naddr, us, us - floor_us);
+        if (kper) printf(", %5.1f ns per atomic and address", (us - floor_us) * 1e3 / (n / naddr));
+        printf(")\n");
+    }
+}
+
 int main() {
     uint32_t *c, *sink;
     hipMalloc(&c, 1 << 24);
@@ -54,5 +90,6 @@ int main() {
         const double n = (double)cs.blocks * 256 * cs.per;
         printf("%-78s %8.1f us  %6.2f ns/atomic  %7.1f ns per atomic and address\n", cs.name, best * 1e3, best * 1e6 / n, best * 1e6 / (n / cs.naddr));
     }
+    run_sparse(c, sink, e0, e1);
     return 0;
 }
