@@ -19,7 +19,8 @@ camera is the identity, so view depth is -z bit for bit and a scene's depths are
 returns a LimitScene: the records, the frame, the environment the renderer needs, and `expect` -- the quantities it pins, exact by
 construction.  The second half of the module re-measures those quantities from the oracle's stages (tests/test_limit_scenes.py
 asserts they are equal, with no GPU) and restates the level policy of gs_depth_policy.h for a fresh renderer, which is where the
-GPU test's predicted stats come from.
+GPU test's predicted stats come from.  The last part restates what the one-pass level 1 (gs_kernels.h: L1Fused) depends on: the
+default capacity of the candidate buffer, the region of it a bin owns, and which of these scenes run on that path.
 
 A plain module: numpy and tests/ only."""
 from dataclasses import dataclass, field
@@ -956,10 +957,21 @@ def predict(scene, forced=False, sort_path=0):
     Bins of 16 x 16 tiles or more (shift >= 4) are ordered by k_bin_build at every bin-local level: such a bin fits a
     bin-local level if and only if it holds <= 16384, at level 0 already, and one that does not has no level 4 to go to -- it
     is refined or goes straight to the global path."""
+    return _walk(scene, forced, sort_path)[0]
+
+
+def attempts(scene, forced=False, sort_path=0):
+    """[(bin shift, level)] of every attempt predict() passes through, the frame that finally retires (or fails) last."""
+    return _walk(scene, forced, sort_path)[1]
+
+
+def _walk(scene, forced, sort_path):
     tx, ty = tiles_across(scene.width), tiles_across(scene.height)
     shift = base_shift(tx, ty, scene.min_shift)
     level, retries, refined = (GLOBAL_LEVEL if sort_path == 1 else 0), 0, False
+    tried = []
     while True:
+        tried.append((shift, level))
         fullest = scene.expect["fullest_bin"][shift]
         one_size = shift >= ONE_SIZE_SHIFT
         if one_size:
@@ -968,7 +980,7 @@ def predict(scene, forced=False, sort_path=0):
             fits = level == GLOBAL_LEVEL or (fullest <= LEVEL_LIMITS[level] and not (level == SLAB_LEVEL and scene.slabs_fail))
         if fits:
             return dict(sort_level=level, sort_path=1 if level == GLOBAL_LEVEL else 2, retries=retries, bin_tiles=1 << shift,
-                        max_bin_entries=fullest, num_bin_entries=scene.expect["bin_entries"][shift])
+                        max_bin_entries=fullest, num_bin_entries=scene.expect["bin_entries"][shift]), tried
         wanted = level + 1
         while wanted < GLOBAL_LEVEL and fullest > LEVEL_LIMITS[wanted]:
             wanted += 1
@@ -978,6 +990,105 @@ def predict(scene, forced=False, sort_path=0):
             refined, shift, level = True, shift - 1, max(level, SLAB_LEVEL - 1)
         else:
             if forced and wanted >= GLOBAL_LEVEL:
-                return "bin too full" if one_size else "error"
+                return ("bin too full" if one_size else "error"), tried
             level = max(level, wanted)
         retries += 1
+
+
+# ================================================================================================ the one-pass level 1
+MAX_INSTANCES = (1 << 30) - 4096                    # gs_internal.h: kMaxInstances
+ONE_PASS_MAX_SHIFT = 3                              # gs_renderer.cpp: the path needs bins of <= 8 x 8 tiles (and a bin-local level)
+WIDE_RATIO = 8                                      # gs_depth_policy.h: L1FusedPolicy::kWideRatio
+
+
+def candidate_capacity(n, env=None):
+    """gs_renderer::init restated: the level-1 candidates the candidate buffer of a fresh renderer over a scene of n Gaussians
+    holds -- min(max(2^18, 2 n), max(2^20, 8 n)), capped at the instance maximum -- under the two test knobs of `env`."""
+    env = env or {}
+    want = max(1 << 20, 8 * n)
+    if "GS_INITIAL_CAPACITY" in env:
+        want = max(256, int(env["GS_INITIAL_CAPACITY"]))
+    capacity = min(want, MAX_INSTANCES)
+    cand = max(1 << 18, 2 * n)
+    if "GS_INITIAL_CAND_CAPACITY" in env:
+        cand = max(256, int(env["GS_INITIAL_CAND_CAPACITY"]))
+    elif "GS_INITIAL_CAPACITY" in env:
+        cand = min(cand, want)
+    return min(cand, capacity)
+
+
+def screen_bins(width, height, shift):
+    """The on-screen bins of a frame with bins of 2^shift tiles (gs_depth_policy.h: bin_geometry)."""
+    return (((tiles_across(width) - 1) >> shift) + 1) * (((tiles_across(height) - 1) >> shift) + 1)
+
+
+def region_cap(cand_capacity, bins):
+    """gs_depth_policy.h: L1FusedPolicy::region_cap -- the records of the candidate buffer every on-screen bin owns."""
+    return cand_capacity // bins if bins else 0
+
+
+def one_pass_final(want):
+    """Does the frame that finally retires take the one-pass level 1 when the switch forces it (gs_set_level1_fused(1), a scene
+    below the dense-list threshold)?  `want`: predict()'s result.  Bin-local, with bins of at most 8 x 8 tiles."""
+    return isinstance(want, dict) and want["sort_path"] == 2 and want["bin_tiles"] <= 1 << ONE_PASS_MAX_SHIFT
+
+
+# what tests/test_gpu_limits.py runs with one_pass=True, by builder (test_limit_scenes.py checks every one of them on the CPU)
+ONE_PASS_SLAB_COUNTS = (16385, 65534, 65535)
+ONE_PASS_L1_COUNTS = tuple((n, culled) for n in (255, 256, 257, 1025) for culled in (0, 300))
+ONE_PASS_REFUSAL = (1025, 4)                        # build_size: bins of 16 x 16 tiles -- the switch does not engage
+
+
+def one_pass_scenes():
+    """(scene, the fullest bin must FILL its region exactly) of every limit scene that runs on the one-pass level 1."""
+    for lim in LEVEL_LIMITS[:4]:
+        for d in (-1, 0, 1):
+            yield level2_size(lim + d), False
+    yield level2_size(16385, shift=3), False
+    for c in ONE_PASS_SLAB_COUNTS:
+        yield level2_size(c), False
+    yield level2_size(65536), True
+    for length in (64, 65, 66, 67):
+        for place in RUN_PLACES:
+            yield equal_run(length, place, slab=False), False
+            yield equal_run(length, place, slab=True), False
+    for k in (63, 64, 65, 66):
+        yield crowded_bucket(k), False
+    for kind in ("exact", "over", "most"):
+        yield slab_plan(kind), False
+    for rows, cols in BIG_BOXES:
+        yield big_box(rows, cols), False
+    for n, culled in ONE_PASS_L1_COUNTS:
+        yield level1_count(n, culled), False
+    yield build_size(*ONE_PASS_REFUSAL), False
+
+
+def wide_ratio(extra):
+    """The wide-splat exit of the one-pass level 1 (L1FusedPolicy: E1 > 8 V).  320 probes (big_box's technique, through _probe) on
+    a frame of 8 x 8 bins of 4 x 4 tiles, each of radius 120: a tile box 16 tiles wide, which is four bins, and -- centred on the
+    frame's top or bottom edge, which clips it -- 8 tiles high, which is two.  Every visible Gaussian touches exactly 2 x 4 bins:
+    E1 = 8 V.  extra: the last one has radius 88 around the middle of tiles [8, 20) instead, 12 x 12 tiles or 3 x 3 bins: E1 = 8 V + 1.
+    Every box edge that is not the frame's is 7 px or more clear of moving."""
+    w = h = 512
+    n = 320
+    i = np.arange(n, dtype=np.int64)
+    rec = _splats(_spread_bits(n), i % 32, i % 32, w, h)
+    for j in range(n):
+        a = 4 * (j % 5)                                          # tile columns [a, a + 16): bins a / 4 .. a / 4 + 3
+        _probe(rec[j:j + 1], 16.0 * a + 128.0, 0.0 if (j // 5) % 2 == 0 else float(h), 2.5 + 0.005 * j, 120.0, w, h)
+    if extra:
+        _probe(rec[n - 1:n], 224.0, 224.0, 2.5 + 0.005 * (n - 1), 88.0, w, h)   # the middle of tiles [8, 20), both ways
+    e1 = WIDE_RATIO * n + (1 if extra else 0)
+    per_bin = np.zeros((8, 8), np.int64)
+    boxes = {}
+    for j in range(n):
+        a, top = j % 5, (j // 5) % 2 == 0
+        box = (a, 0 if top else 6, a + 4, 2 if top else 8)
+        if extra and j == n - 1:
+            box = (2, 2, 5, 5)
+        boxes[j] = (box[2] - box[0], box[3] - box[1])
+        per_bin[box[1]:box[3], box[0]:box[2]] += 1
+    return LimitScene(f"wide_ratio/{'over' if extra else 'at'}", rec, w, h, {"GS_BIN_SHIFT": "2", "GS_SPATIAL_MIN": "0"},
+                      f"E1 = 8 V{' + 1' if extra else ''}",
+                      dict(n=n, visible=n, bin_entries={2: e1}, fullest_bin={2: int(per_bin.max())},
+                           probes={j: boxes[j] for j in (0, 7, 158, n - 1)}))

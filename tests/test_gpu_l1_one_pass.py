@@ -10,6 +10,7 @@ which is then what the test checks."""
 import numpy as np
 import pytest
 
+import limit_scenes as ls
 from helpers import compare_stages, oracle_frame
 
 pytestmark = pytest.mark.gpu
@@ -227,6 +228,93 @@ def test_region_edge(pkg, oracle, gpu, monkeypatch, _sort_path):
         assert st.retries == 1
         compare_stages(pkg, rend, u, ref)
         np.testing.assert_array_equal(img.view(np.uint32), ref["image"].view(np.uint32))
+
+
+def _exact_frame(pkg, rend, u, ref):
+    """One frame, equal to the oracle's: (whether it took the one-pass level 1, its stats)."""
+    img, _ = rend.render_host(u)
+    fused = rend.level1_fused()
+    st = rend.stats()
+    compare_stages(pkg, rend, u, ref)
+    np.testing.assert_array_equal(img.view(np.uint32), ref["image"].view(np.uint32))
+    return fused, st
+
+
+@pytest.mark.parametrize("extra", [False, True], ids=["E1_is_8V", "E1_is_8V_plus_1"])
+def test_wide_splat_exit(pkg, oracle, gpu, monkeypatch, _sort_path, extra):
+    """L1FusedPolicy's wide-splat exit, E1 > 8 V (limit_scenes.wide_ratio: every visible Gaussian in 4 x 2 bins, and one of them in
+    3 x 3).  By rule the first frame of either scene is a one-pass frame -- no frame has retired, the frame tells -- and what it
+    counted decides the second: at E1 = 8 V the path stays, at 8 V + 1 the three kernels run.  The switch overrides the ratio, and
+    the rule, asked again, leaves again.  E1 and V feed the rule, so both are asserted, whichever form of level 1 counted them."""
+    sc = ls.wide_ratio(extra)
+    for k, v in sc.env.items():
+        monkeypatch.setenv(k, v)
+    verts, u_ref, ref = oracle_frame(oracle, sc.records, sc.width, sc.height)
+    got = ls.measure(sc, ref)
+    for key, want in sc.expect.items():
+        assert got[key] == want, f"{sc.name} missed its edge ({sc.pins}): {key} is {got[key]}, not {want}"
+    e1, v = sc.expect["bin_entries"][2], sc.expect["visible"]
+    assert (e1 > ls.WIDE_RATIO * v) == extra and e1 - ls.WIDE_RATIO * v == (1 if extra else 0)
+    scene = pkg.Scene.from_records(sc.records, device=0)
+    rend = pkg.Renderer(scene)
+    u = pkg.camera_uniforms(pkg.make_camera(), sc.width, sc.height)
+    assert u.tobytes() == u_ref.tobytes()
+    auto = _sort_path != "1"   # (on the global path the one-pass level 1 never engages)
+    try:
+        for mode, want in [(None, auto), (None, auto and not extra), (1, auto), (1, auto), (-1, auto and not extra)]:
+            if mode is not None:
+                rend.set_level1_fused(mode)
+            fused, st = _exact_frame(pkg, rend, u, ref)
+            assert fused == want, f"{sc.name}: mode {mode}, one-pass {fused}"
+            assert (st.num_bin_entries, st.num_visible, st.max_bin_entries, st.retries) == (e1, v, sc.expect["fullest_bin"][2], 0)
+    finally:
+        rend.close()
+        scene.close()
+
+
+def _counts(pkg, rec, u):
+    """(fullest bin, E1, D) of the frame, from a renderer that runs the three kernels."""
+    scene = pkg.Scene.from_records(rec, device=0)
+    rend = pkg.Renderer(scene)
+    rend.set_level1_fused(0)
+    rend.render_host(u)
+    st = rend.stats()
+    assert st.retries == 0
+    rend.close()
+    scene.close()
+    return st.max_bin_entries, st.num_bin_entries, st.num_instances
+
+
+@pytest.mark.parametrize("edge", ["lists_hold_E1", "lists_hold_D_minus_1"])
+def test_list_buffer_overflow_on_a_one_pass_frame(pkg, oracle, gpu, monkeypatch, _sort_path, edge):
+    """A frame of one bin (64 x 64 px) whose splats cover several tiles each: D well above E1.  The per-tile lists start at the
+    least (E1: GS_INITIAL_CAPACITY caps the candidate buffer too, so the bin's region is then full to its last record) and the most
+    (D - 1) with which level 2 overflows them while the bin's region holds: exactly one re-run, no hold -- the re-run and the next
+    frame are one-pass frames -- and every frame equal to the oracle's."""
+    monkeypatch.setenv("GS_SPATIAL_MIN", "0")
+    rec = pkg.synth.synth_records(2000, seed=2000, kind="A")
+    w = h = 64
+    verts, u_ref, ref = oracle_frame(oracle, rec, w, h)
+    u = pkg.camera_uniforms(pkg.make_camera(), w, h)
+    fullest, e1, d = _counts(pkg, rec, u)
+    assert fullest == e1 >= 256 and d >= 2 * e1, f"one bin, D well above E1: fullest bin {fullest}, E1 {e1}, D {d}"
+    lists = e1 if edge == "lists_hold_E1" else d - 1
+    assert ls.region_cap(ls.candidate_capacity(len(rec), {"GS_INITIAL_CAPACITY": str(lists)}), ls.screen_bins(w, h, 3)) >= fullest
+    monkeypatch.setenv("GS_INITIAL_CAPACITY", str(lists))
+    scene = pkg.Scene.from_records(rec, device=0)
+    rend = pkg.Renderer(scene)
+    try:
+        for frame in range(2):
+            fused, st = _exact_frame(pkg, rend, u, ref)
+            assert (st.max_bin_entries, st.num_bin_entries, st.num_instances) == (fullest, e1, d)
+            if _sort_path == "1":   # the global path's lists overflow too; the one-pass level 1 never engages there
+                assert not fused and st.retries >= 1
+                continue
+            assert st.retries == 1, f"frame {frame}: {st.retries} re-runs"
+            assert fused, f"frame {frame}: the three kernels ran"
+    finally:
+        rend.close()
+        scene.close()
 
 
 def test_three_frames_in_flight_two_poses(pkg, oracle, gpu, monkeypatch, _sort_path):

@@ -8,10 +8,19 @@ Binning and blend: every capacity.  k_bin_build, the level-2 kernel of bins of 1
 the global path, in its five instantiations: its one capacity (16384 at every bin-local level), the sort rounds of 1024, equal
 depths across a wave's run of the list, a tile that takes all 16384, boxes clipped to the bin, a bin cut by the frame's edge, the
 streamed lists of the global path up to 70000, and the list buffer running over inside the kernel.  k_preprocess: every count
-of visible lanes of a wave at which its SH fetch, its run of slots in the dense lists or its record store changes shape, under every combination of SH storage, read order, dense lists and the
-antialiased mode, and the dense lists full to their last slot.  The global depth order: every shape of its grid.
+of visible lanes of a wave at which its SH fetch, its run of slots in the dense lists or its record store changes shape, under
+every combination of SH storage, read order, form of level 1 (planes, dense lists, one pass) and the antialiased mode, and the
+dense lists full to their last slot.  The global depth order: every shape of its grid.
+
+Which form of level 1 ran is part of every case: _assert_frame asserts level1_fused() of the frame that finally retired.  These
+scenes are read in scene-id order and have no spatial copy, so by rule they run the three level-1 kernels; the test_one_pass_*
+cases force the one-pass level 1 (k_preprocess files the bin candidates itself; level 2 reads the bins' cursors) onto the same
+level-2 and level-1 edges, and a region of the candidate buffer that is full to its last record.
 
 Not covered, and why:
+  * k_bin_build's one-pass branch (bin_candidates / bin_offset / bin_close_one_pass / one_pass_visible inside it): unreachable, the
+    one-pass level 1 needs bins of at most 8 x 8 tiles and k_bin_build orders bins of 16 x 16 and more, or the global path's
+    (test_one_pass_refused_by_bins_of_16x16_tiles: the switch does not engage there).
   * kMaxSlabs = 16 and the planner's `remaining > MAXC` exit: a bin of <= 65535 candidates cannot be cut into more than 11
     slabs of <= 12288 (tests/test_limit_scenes.py::test_no_bin_of_a_frame_needs_more_than_eleven_slabs).  The nearest
     reachable case, 11 slabs of which five are full, is test_slab_planning[most].
@@ -52,11 +61,14 @@ def _frame(pkg, oracle, monkeypatch, scene, extra_env=None):
     return gs, pkg.Renderer(gs), u, ref
 
 
-def _assert_frame(pkg, rend, u, ref, scene, want, label, grows=False):
+def _assert_frame(pkg, rend, u, ref, scene, want, label, fused, grows=False):
     """One frame: stats as predicted, every stage and the mode-2 image exact, the default blend within the guarded tolerance.
+    fused: what level1_fused() must say of the frame that finally retired -- k_preprocess filed the level-1 candidates itself.
     grows: the buffers start too small -- at least one re-run more than predicted, everything else as predicted."""
     img, _ = rend.render_host(u)
+    took = rend.level1_fused()
     st = rend.stats()
+    assert took == fused, f"{label}: the frame that retired {'took' if took else 'did not take'} the one-pass level 1"
     have = {k: getattr(st, k) for k in STAT_KEYS}
     print(f"{label}: {have}")
     if want is not None and grows:
@@ -75,14 +87,22 @@ def _assert_frame(pkg, rend, u, ref, scene, want, label, grows=False):
 BIN_TOO_FULL = "a bin holds more candidates than the bin-local sort can order"   # gs_renderer.cpp: DepthPolicy::kBinTooFull
 
 
-def _run(pkg, oracle, monkeypatch, scene, forced=False, extra_env=None, global_path=False, grows=False):
-    """global_path: gs_set_sort_path(1), the global depth order at once (level 5, no re-run, the scene's own bins)."""
+def _run(pkg, oracle, monkeypatch, scene, forced=False, extra_env=None, global_path=False, grows=False, one_pass=False):
+    """global_path: gs_set_sort_path(1), the global depth order at once (level 5, no re-run, the scene's own bins).
+    one_pass: gs_set_level1_fused(1) before the first frame (these scenes are read in scene-id order and have no spatial copy: by
+    rule they run the three level-1 kernels).  The frame that finally retires is then a one-pass frame exactly when it is
+    bin-local with bins of at most 8 x 8 tiles, and the re-runs are the predicted ones EXACTLY: a region that ran over would add
+    one, and a hold (tests/test_limit_scenes.py::test_one_pass_regions_hold_the_fullest_bin)."""
     gs, rend, u, ref = _frame(pkg, oracle, monkeypatch, scene, extra_env)
     try:
-        assert not (forced and global_path)
+        assert not (forced and global_path) and not (one_pass and (forced or global_path or grows))
         want = ls.predict(scene, forced, sort_path=1 if global_path else 0) if "fullest_bin" in scene.expect else None
+        assert not one_pass or isinstance(want, dict)
         rend.set_sort_path(1 if global_path else 2 if forced else 0)
-        label = f"{scene.name}{' forced' if forced else ' global' if global_path else ''}{' ' + str(extra_env) if extra_env else ''}"
+        if one_pass:
+            rend.set_level1_fused(1)
+        fused = one_pass and ls.one_pass_final(want)
+        label = f"{scene.name}{' forced' if forced else ' global' if global_path else ''}{' one-pass' if one_pass else ''}{' ' + str(extra_env) if extra_env else ''}"
         if want in ("error", "bin too full"):
             with pytest.raises(pkg.GsError) as e:
                 rend.render_host(u)
@@ -91,7 +111,7 @@ def _run(pkg, oracle, monkeypatch, scene, forced=False, extra_env=None, global_p
             if want == "bin too full":
                 assert BIN_TOO_FULL in str(e.value), f"{label}: the error of another failure: {e.value}"
             return None
-        return _assert_frame(pkg, rend, u, ref, scene, want, label, grows)
+        return _assert_frame(pkg, rend, u, ref, scene, want, label, fused, grows)
     finally:
         rend.close()
         gs.close()
@@ -267,15 +287,20 @@ def test_slab_planning(pkg, oracle, gpu, monkeypatch, kind, queue):
 
 
 # ------------------------------------------------------------------------------------------------ level 1
-def _level1(pkg, oracle, monkeypatch, scene, dense_min, sort_path):
+def _level1(pkg, oracle, monkeypatch, scene, dense_min, sort_path, one_pass=False):
+    """one_pass: as _run's -- the switch forces the one-pass level 1, which then is what ran (bin-local, bins of 8 x 8 tiles or less)."""
     gs, rend, u, ref = _frame(pkg, oracle, monkeypatch, scene, {"GS_L1_DENSE_MIN": dense_min})
     try:
         rend.set_sort_path(sort_path)
+        if one_pass:
+            rend.set_level1_fused(1)
         want = ls.predict(scene)
         assert want["retries"] == 0 and want["sort_level"] == 0   # these scenes are about level 1: no bin beyond 4096
         if sort_path == 1:
             want.update(sort_path=1, sort_level=ls.GLOBAL_LEVEL)
-        _assert_frame(pkg, rend, u, ref, scene, want, f"{scene.name} dense_min {dense_min} path {sort_path}")
+        fused = one_pass and ls.one_pass_final(want)
+        assert fused == (one_pass and sort_path == 0)
+        _assert_frame(pkg, rend, u, ref, scene, want, f"{scene.name} dense_min {dense_min} path {sort_path}{' one-pass' if one_pass else ''}", fused)
     finally:
         rend.close()
         gs.close()
@@ -307,6 +332,97 @@ def test_level1_bin_box_at_the_wave_emission_limit(pkg, oracle, gpu, monkeypatch
         _level1(pkg, oracle, monkeypatch, ls.big_box(rows, cols), dense_min, sort_path)
 
 
+# ------------------------------------------------------------------------------------------------ the same edges, one-pass level 1
+# Level 2 then takes a bin's count from its cursor and its offset from (on-screen index) x (region size), and produces V, E1, the
+# fullest bin and the overflow flag itself (gs_bin_l2.hip: bin_candidates, bin_offset, bin_close_one_pass, one_pass_visible) -- in
+# k_bin_fast<4 / 8 / 12 / 16>, k_bin_slabs + k_slab_work and k_bin_queue; k_preprocess counts and files the candidates.  Automatic
+# sort mode, the switch forced (_run: one_pass).  Everything _assert_frame checks, and that the frame that retired was a one-pass one.
+@pytest.mark.parametrize("delta", [-1, 0, 1])
+@pytest.mark.parametrize("level", [0, 1, 2, 3])
+def test_one_pass_level2_size_in_lds(pkg, oracle, gpu, monkeypatch, level, delta):
+    """test_level2_size_in_lds: the frame re-run one level up is a one-pass frame again (its cursors were zeroed by the frame
+    that overflowed), and max_bin_entries / num_bin_entries are bin_close_one_pass's."""
+    count = ls.LEVEL_LIMITS[level] + delta
+    st = _run(pkg, oracle, monkeypatch, ls.level2_size(count), one_pass=True)
+    assert st.sort_level == level + (delta > 0) and st.max_bin_entries == count and st.retries == (st.sort_level > 0)
+
+
+def test_one_pass_level2_16385_refines_the_bins_first(pkg, oracle, gpu, monkeypatch):
+    """The re-run has bins of half the edge: 16 regions of a sixteenth of the buffer where the first attempt had 4 of a quarter."""
+    st = _run(pkg, oracle, monkeypatch, ls.level2_size(16385, shift=3), one_pass=True)
+    assert (st.bin_tiles, st.sort_level, st.retries, st.max_bin_entries) == (4, 3, 1, 4097)
+
+
+@pytest.mark.parametrize("queue", ["1", "0"])
+@pytest.mark.parametrize("count", ls.ONE_PASS_SLAB_COUNTS)
+def test_one_pass_level2_size_in_slabs(pkg, oracle, gpu, monkeypatch, count, queue):
+    """Level 4 from its first candidate to its last: k_bin_queue reads every bin's cursor to rank the bins and again when it claims
+    one.  At 66 135 Gaussians k_preprocess's 256 strided counters of visible Gaussians wrap: num_visible is one_pass_visible's sum."""
+    st = _run(pkg, oracle, monkeypatch, ls.level2_size(count), extra_env={"GS_L2_QUEUE": queue}, one_pass=True)
+    assert (st.sort_path, st.sort_level, st.retries, st.max_bin_entries) == (2, 4, 1, count)
+
+
+@pytest.mark.parametrize("queue", ["1", "0"])
+def test_one_pass_level2_65536_fills_its_region(pkg, oracle, gpu, monkeypatch, queue):
+    """The region of the default candidate buffer holds exactly 65536 here, and it is the buffer's last: full to its last record it
+    does not count as overflowed (no hold, no re-run for its sake) -- but the bin is beyond the slabs' 16-bit slot, so the frame ends
+    on the global path with ONE re-run, and that frame is not a one-pass one."""
+    st = _run(pkg, oracle, monkeypatch, ls.level2_size(65536), extra_env={"GS_L2_QUEUE": queue}, one_pass=True)
+    assert (st.sort_path, st.sort_level, st.retries, st.max_bin_entries) == (1, 5, 1, 65536)
+
+
+@pytest.mark.parametrize("place", ls.RUN_PLACES)
+@pytest.mark.parametrize("length", [64, 65, 66, 67])
+def test_one_pass_equal_depth_run_in_a_fast_bin(pkg, oracle, gpu, monkeypatch, length, place):
+    """test_equal_depth_run_in_a_fast_bin with the bin's records in whatever order the workgroups' reservations fell."""
+    st = _run(pkg, oracle, monkeypatch, ls.equal_run(length, place, slab=False), one_pass=True)
+    assert (st.sort_path, st.sort_level, st.retries) == (2, 0, 0)
+
+
+@pytest.mark.parametrize("queue", ["1", "0"])
+@pytest.mark.parametrize("place", ls.RUN_PLACES)
+@pytest.mark.parametrize("length", [64, 65, 66, 67])
+def test_one_pass_equal_depth_run_in_a_slab(pkg, oracle, gpu, monkeypatch, length, place, queue):
+    """test_equal_depth_run_in_a_slab: candidates of equal depth arrive in an order that differs from run to run, and 64 and 65 of
+    them must still come out in id order; 66 and 67 end on the global path (two re-runs), which is not a one-pass frame."""
+    st = _run(pkg, oracle, monkeypatch, ls.equal_run(length, place, slab=True), extra_env={"GS_L2_QUEUE": queue}, one_pass=True)
+    assert (st.sort_path, st.sort_level, st.retries) == ((2, 4, 1) if length <= 65 else (1, 5, 2))
+
+
+@pytest.mark.parametrize("k", [63, 64, 65, 66])
+def test_one_pass_crowded_depth_bucket(pkg, oracle, gpu, monkeypatch, k):
+    st = _run(pkg, oracle, monkeypatch, ls.crowded_bucket(k), one_pass=True)
+    assert (st.sort_path, st.sort_level, st.retries) == (2, 0, 0)
+
+
+@pytest.mark.parametrize("queue", ["1", "0"])
+@pytest.mark.parametrize("kind", ["exact", "over", "most"])
+def test_one_pass_slab_planning(pkg, oracle, gpu, monkeypatch, kind, queue):
+    st = _run(pkg, oracle, monkeypatch, ls.slab_plan(kind), extra_env={"GS_L2_QUEUE": queue}, one_pass=True)
+    assert (st.sort_path, st.sort_level, st.retries) == (2, 4, 1)
+
+
+@pytest.mark.parametrize("rows,cols", ls.BIG_BOXES)
+def test_one_pass_bin_box_at_the_wave_emission_limit(pkg, oracle, gpu, monkeypatch, rows, cols):
+    """kL1BigBox = 12, which k_preprocess restates from k_l1_hist: a box of exactly 12 bins is emitted by its own lane, one of 13
+    or 14 by the whole wave -- in the kernel's counting half and in its filing half alike, or a bin's cursor and its records disagree."""
+    _level1(pkg, oracle, monkeypatch, ls.big_box(rows, cols), "1000000000", 0, one_pass=True)
+
+
+@pytest.mark.parametrize("n,culled", ls.ONE_PASS_L1_COUNTS)
+def test_one_pass_items_around_one_workgroup(pkg, oracle, gpu, monkeypatch, n, culled):
+    """k_preprocess's workgroup of 256: one short of it, one workgroup, one beyond, and four and a ragged fifth -- whose lanes
+    without a Gaussian still take part in the barriers of the counting and the filing half and reserve nothing."""
+    _level1(pkg, oracle, monkeypatch, ls.level1_count(n, culled), "1000000000", 0, one_pass=True)
+
+
+def test_one_pass_refused_by_bins_of_16x16_tiles(pkg, oracle, gpu, monkeypatch):
+    """The switch asks, the frame's structure refuses: k_bin_build's bins take their candidates in id order from the three kernels."""
+    st = _run(pkg, oracle, monkeypatch, ls.build_size(*ls.ONE_PASS_REFUSAL), one_pass=True)
+    assert (st.sort_path, st.sort_level, st.retries, st.max_bin_entries, st.bin_tiles) == (2, 0, 0, 1025, 16)
+    assert not ls.one_pass_final(ls.predict(ls.build_size(*ls.ONE_PASS_REFUSAL)))
+
+
 # ------------------------------------------------------------------------------------------------ blend chunks
 @pytest.mark.parametrize("lockstep", [0, 1])
 @pytest.mark.parametrize("k", ls.BLEND_LENGTHS)
@@ -317,7 +433,7 @@ def test_blend_list_lengths_around_the_chunks(pkg, oracle, gpu, monkeypatch, k, 
     gs, rend, u, ref = _frame(pkg, oracle, monkeypatch, scene)
     try:
         rend.set_blend_lockstep(lockstep)
-        st = _assert_frame(pkg, rend, u, ref, scene, None, f"{scene.name} lockstep {lockstep}")
+        st = _assert_frame(pkg, rend, u, ref, scene, None, f"{scene.name} lockstep {lockstep}", False)
         assert st.num_instances == scene.expect["instances"]
         ranges = rend.stage("ranges", u).astype(np.int64)
         tx = ls.tiles_across(scene.width)
@@ -333,7 +449,7 @@ def _guard_case(pkg, oracle, monkeypatch, scene):
     under test bit for bit against the reference where it was re-rendered with the reference's arithmetic."""
     gs, rend, u, ref = _frame(pkg, oracle, monkeypatch, scene)
     try:
-        _assert_frame(pkg, rend, u, ref, scene, None, scene.name)
+        _assert_frame(pkg, rend, u, ref, scene, None, scene.name, False)
         rend.set_exp_mode(3)
         rend.set_blend_contraction(False)
         img, _ = rend.render_host(u)
@@ -423,22 +539,32 @@ def _all_taps(rend, u):
     return out
 
 
+# The three forms of level 1, by name: (GS_L1_DENSE_MIN, gs_set_level1_fused on every renderer of the test; None: its default).
+# planes: k_l1_hist / k_l1_scan / k_l1_scatter_any_order over the N-wide planes -- switched off explicitly, because a spatially
+# ordered scene below dense_min takes the one-pass form by rule; dense_lists: the three kernels over the dense lists;
+# one_pass: k_preprocess files the candidates itself -- forced, because in index order the rule refuses for lack of a spatial copy.
+LEVEL1_FORMS = {"planes": ("1000000000", 0), "dense_lists": ("0", None), "one_pass": ("1000000000", 1)}
+
+
 @pytest.mark.parametrize("antialiased", [False, True], ids=["plain", "antialiased"])
-@pytest.mark.parametrize("dense_min", ["1000000000", "0"], ids=["planes", "dense_lists"])
+@pytest.mark.parametrize("level1", list(LEVEL1_FORMS))
 @pytest.mark.parametrize("order", ["index", "spatial"])
 @pytest.mark.parametrize("sh16", [False, True], ids=["fp32", "binary16"])
 @pytest.mark.parametrize("tail", ls.WAVE_TAILS)
-def test_preprocess_at_every_visible_lane_count(pkg, oracle, gpu, monkeypatch, tail, sh16, order, dense_min, antialiased):
+def test_preprocess_at_every_visible_lane_count(pkg, oracle, gpu, monkeypatch, tail, sh16, order, level1, antialiased):
     """k_preprocess's wave-cooperative steps -- the LDS-DMA fetch of the SH blocks by rank, the wave's run of slots in the dense
-    lists, the four-lanes-per-record store through the scene ids -- at every count and placement of visible lanes
-    (limit_scenes.wave_patterns), for each combination of SH storage, read order, level-1 input and the antialiased mode.  The
-    plain frame: every tap and the mode-2 image bit for bit against the oracle, the default blend within the guarded tolerance,
-    V and N, and the taps against float64.  The antialiased frame: test_gpu_antialiased.py's contract."""
+    lists or the one-pass level 1's count and filing of the bin candidates, the four-lanes-per-record store through the scene ids
+    -- at every count and placement of visible lanes (limit_scenes.wave_patterns), for each combination of SH storage, read order,
+    form of level 1 (LEVEL1_FORMS) and the antialiased mode.  The plain frame: every tap and the mode-2 image bit for bit against
+    the oracle, the default blend within the guarded tolerance, V and N, and the taps against float64.  The antialiased frame
+    (k_preprocess<true, 4> in the one-pass form): test_gpu_antialiased.py's contract.  Every frame ran the form the case is named for."""
     scene, verts, u_ref, ref, frame = _wave_reference(oracle, order, tail, sh16)
+    dense_min, switch = LEVEL1_FORMS[level1]
+    fused = level1 == "one_pass"
     monkeypatch.delenv("GS_SORT_PATH", raising=False)
     for k, v in {**scene.env, "GS_L1_DENSE_MIN": dense_min}.items():
         monkeypatch.setenv(k, v)
-    label = f"{scene.name} {'binary16' if sh16 else 'fp32'} dense_min {dense_min}"
+    label = f"{scene.name} {'binary16' if sh16 else 'fp32'} {level1}"
     u = pkg.camera_uniforms(pkg.make_camera(), scene.width, scene.height)
     assert u.tobytes() == u_ref.tobytes()
     gs = pkg.Scene.from_records(scene.records, device=0)
@@ -448,7 +574,10 @@ def test_preprocess_at_every_visible_lane_count(pkg, oracle, gpu, monkeypatch, t
             gs.quantize_sh()
         rend = pkg.Renderer(gs)
         made.append(rend)
-        _assert_frame(pkg, rend, u, ref, scene, None, label)
+        if switch is not None:
+            rend.set_level1_fused(switch)
+        _assert_frame(pkg, rend, u, ref, scene, None, label, fused)
+        assert rend.level1_fused() == fused, f"{label}: the default blend's frame"
         out = chk.outputs_from_hip(rend, u)
         rep = chk.assert_matches_float64(out, frame, label=f"{label} (HIP taps)")
         assert (rep["radius_explained"], rep["box_explained"], rep["visibility_explained"]) == (0, 0, 0)
@@ -458,6 +587,7 @@ def test_preprocess_at_every_visible_lane_count(pkg, oracle, gpu, monkeypatch, t
         plain = rend.stage("conic_opacity").reshape(-1, 4)[:, 3].copy()
         rend.set_antialiased(True)
         img_on, _ = rend.render_host(u)
+        assert rend.level1_fused() == fused, f"{label}: the antialiased frame"
         st = rend.stats()
         assert st.num_visible == scene.expect["visible"] and st.num_gaussians == scene.expect["n"]
         on = _all_taps(rend, u)
@@ -478,7 +608,10 @@ def test_preprocess_at_every_visible_lane_count(pkg, oracle, gpu, monkeypatch, t
             s2.quantize_sh()
         r2 = pkg.Renderer(s2)
         made.append(r2)
+        if switch is not None:
+            r2.set_level1_fused(switch)
         img2, _ = r2.render_host(u)
+        assert r2.level1_fused() == fused, f"{label}: the plain frame of S'"
         np.testing.assert_array_equal(img_on.view(np.uint32), img2.view(np.uint32))
         two = _all_taps(r2, u)
         for name in on:

@@ -234,7 +234,10 @@ def test_no_bin_of_a_frame_needs_more_than_eleven_slabs():
         assert len(ls.plan_slabs(h)) == 12 and h.sum() == 6 * 12289 > 65535
 
 
-@pytest.mark.parametrize("n,culled", [(1023, 0), (1024, 0), (1025, 0), (1023, 300), (1024, 300), (1025, 300)])
+L1_COUNTS = [(1023, 0), (1024, 0), (1025, 0), (1023, 300), (1024, 300), (1025, 300)]
+
+
+@pytest.mark.parametrize("n,culled", L1_COUNTS + [c for c in ls.ONE_PASS_L1_COUNTS if c not in L1_COUNTS])
 def test_level1_count(oracle, n, culled):
     sc = ls.level1_count(n, culled)
     got, _ = _check(oracle, sc)
@@ -445,8 +448,74 @@ def test_dense_lists_full(oracle):
     assert (p["sort_level"], p["retries"]) == (0, 0)
 
 
+# ------------------------------------------------------------------------------------------------ the one-pass level 1
+def test_candidate_capacity_restated():
+    """gs_renderer::init: min(max(2^18, 2 N), max(2^20, 8 N)), and what the two test knobs make of it; region_cap divides it by
+    the on-screen bins, rounding down."""
+    assert ls.candidate_capacity(1) == 1 << 18 and ls.candidate_capacity(131072) == 1 << 18 and ls.candidate_capacity(131073) == 262146
+    assert ls.candidate_capacity(66136) == 262144                        # level2_size(65536): 4 bins of 65536 records
+    assert ls.candidate_capacity(1 << 28) == 1 << 29 and ls.candidate_capacity(1 << 29) == ls.MAX_INSTANCES   # the instance maximum
+    assert ls.candidate_capacity(5000, {"GS_INITIAL_CAPACITY": "3000"}) == 3000       # the lists' knob caps the candidates too
+    assert ls.candidate_capacity(5000, {"GS_INITIAL_CAPACITY": "100"}) == 256
+    assert ls.candidate_capacity(5000, {"GS_INITIAL_CAND_CAPACITY": "70000"}) == 70000
+    assert ls.candidate_capacity(5000, {"GS_INITIAL_CAND_CAPACITY": "70000", "GS_INITIAL_CAPACITY": "3000"}) == 3000
+    assert ls.region_cap(262144, 4) == 65536 and ls.region_cap(262144, 48) == 5461 and ls.region_cap(100, 0) == 0
+    assert ls.screen_bins(128, 128, 2) == 4 and ls.screen_bins(1152, 128, 3) == 9 and ls.screen_bins(4112, 256, 4) == 17
+
+
+def test_one_pass_regions_hold_the_fullest_bin():
+    """Every scene test_gpu_limits.py runs on the one-pass level 1, at every bin edge the policy passes through on the way: the
+    region a bin owns holds the fullest bin (a region that ran over would add a re-run and a hold, and the case would no longer
+    test its own edge), and the candidate buffer holds E1.  level2_size(65536): the region holds EXACTLY the fullest bin."""
+    seen = 0
+    for sc, exact in ls.one_pass_scenes():
+        cand = ls.candidate_capacity(sc.expect["n"], sc.env)
+        tried = ls.attempts(sc)
+        assert len(tried) == ls.predict(sc)["retries"] + 1
+        for shift, level in tried:
+            cap = ls.region_cap(cand, ls.screen_bins(sc.width, sc.height, shift))
+            fullest = sc.expect["fullest_bin"][shift]
+            assert cap >= fullest, f"{sc.name}: a region of {cap} records for a bin of {fullest} with bins of 2^{shift} tiles"
+            assert not exact or cap == fullest, f"{sc.name}: a region of {cap} records is not full with {fullest}"
+            assert sc.expect["bin_entries"][shift] <= cand
+        seen += 1
+    assert seen == 12 + 1 + 3 + 1 + 32 + 4 + 3 + 5 + 8 + 1
+    # the last slot the slabs address is the last record of the region, and of the whole buffer
+    sc = ls.level2_size(65536)
+    assert ls.candidate_capacity(sc.expect["n"]) == 4 * 65536 and ls.one_pass_final(ls.predict(sc)) is False
+    assert ls.one_pass_final(ls.predict(ls.level2_size(65535))) and not ls.one_pass_final(ls.predict(ls.build_size(*ls.ONE_PASS_REFUSAL)))
+
+
+@pytest.mark.parametrize("tail", ls.WAVE_TAILS)
+@pytest.mark.parametrize("order", ["index", "spatial"])
+def test_one_pass_regions_of_the_wave_patterns(oracle, order, tail):
+    """The same for test_preprocess_at_every_visible_lane_count's scenes (9 x 1 bins of 8 x 8 tiles, level 0, no re-run)."""
+    sc = ls.wave_patterns(order, tail)
+    _, _, ref = oracle_frame(oracle, sc.records, sc.width, sc.height)
+    shift = ls.base_shift(ls.tiles_across(sc.width), ls.tiles_across(sc.height), sc.min_shift)
+    fullest = max(len(v) for v in ls.bin_members(ref, shift).values())
+    cap = ls.region_cap(ls.candidate_capacity(sc.expect["n"], sc.env), ls.screen_bins(sc.width, sc.height, shift))
+    assert shift == 3 and fullest <= ls.LEVEL_LIMITS[0] and cap >= fullest
+
+
+@pytest.mark.parametrize("extra", [False, True], ids=["at", "over"])
+def test_wide_ratio(oracle, extra):
+    """E1 = 8 V with every box 4 x 2 bins, and 8 V + 1 with one of 3 x 3: either side of L1FusedPolicy's wide-splat exit."""
+    sc = ls.wide_ratio(extra)
+    got, ref = _check(oracle, sc)
+    ids, x0, y0, x1, y1 = ls.bin_boxes(ref, 2)
+    shapes = sorted(set(zip((x1 - x0).tolist(), (y1 - y0).tolist())))
+    assert shapes == ([(3, 3), (4, 2)] if extra else [(4, 2)]) and len(ids) == got["visible"] == 320
+    e1 = got["bin_entries"][2]
+    assert e1 == 8 * got["visible"] + extra and (e1 > ls.WIDE_RATIO * got["visible"]) == extra
+    # the region: 5/4 of the fullest bin and more (L1FusedPolicy::cap_suffices), so only the ratio can keep the path off
+    cap = ls.region_cap(ls.candidate_capacity(sc.expect["n"], sc.env), ls.screen_bins(sc.width, sc.height, 2))
+    assert 4 * cap >= 5 * got["fullest_bin"][2] and ls.predict(sc)["retries"] == 0
+    assert len(np.unique(ref["attr"]["depth"][ids].view(np.uint32))) == len(ids)
+
+
 # ------------------------------------------------------------------------------------------------ the global path's grid
-RADIX_CASES = [(n, None) for n in ls.RADIX_SIZES] + [(ls.RADIX_SIZES[1], v) for v in ls.RADIX_SMALL_V]
+RADIX_CASES =[(n, None) for n in ls.RADIX_SIZES] + [(ls.RADIX_SIZES[1], v) for v in ls.RADIX_SMALL_V]
 
 
 @pytest.mark.parametrize("n,v", RADIX_CASES)
