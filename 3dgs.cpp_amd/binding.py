@@ -24,7 +24,7 @@ BLOB_PLANES = 59
 
 # the device code of libgs3d_hip.so: one translation unit per stage + the shared device headers
 KERNEL_SOURCES = ("gs_device.h", "gs_bin.h", "gs_scene.hip", "gs_preprocess.hip", "gs_radix.hip", "gs_bin_l1.hip", "gs_bin_l2.hip",
-                  "gs_blend.hip", "gs_contrib.hip", "gs_features.hip", "gs_kernels.h")
+                  "gs_blend.hip", "gs_contrib.hip", "gs_features.hip", "gs_lift.hip", "gs_kernels.h")
 
 
 def library_source_hash():
@@ -61,7 +61,7 @@ SYMBOLS = ["gs_last_error", "gs_device_count", "gs_read_ply", "gs_activate_recor
            "gs_deactivate_vertices", "gs_write_ply", "gs_scene_to_device_arrays", "gs_scene_download_records", "gs_scene_save_ply",
            "gs_scene_destroy", "gs_renderer_create", "gs_renderer_destroy", "gs_camera_uniforms",
            "gs_render", "gs_render_host", "gs_synchronize", "gs_set_timing", "gs_set_frames_in_flight", "gs_set_sort_path", "gs_set_exp_mode", "gs_set_graph_mode", "gs_set_blend_lockstep", "gs_get_blend_lockstep", "gs_set_level1_fused", "gs_get_level1_fused", "gs_set_blend_contraction", "gs_set_antialiased", "gs_get_antialiased", "gs_get_timing_totals",
-           "gs_get_frame_intervals", "gs_get_stats", "gs_poll_stats", "gs_debug_download", "gs_accumulate_contributions", "gs_blend_features", "gs_debug_expf_scan", "gs_debug_alpha_cut_scan", "gs_renderer_stream",
+           "gs_get_frame_intervals", "gs_get_stats", "gs_poll_stats", "gs_debug_download", "gs_accumulate_contributions", "gs_blend_features", "gs_lift_pixels", "gs_debug_expf_scan", "gs_debug_alpha_cut_scan", "gs_renderer_stream",
            "gs_dist_unique_id", "gs_dist_create", "gs_dist_rank", "gs_dist_world", "gs_dist_pose_count",
            "gs_dist_broadcast_scene", "gs_dist_broadcast_scene_ex", "gs_dist_verify", "gs_dist_destroy"]
 
@@ -185,6 +185,60 @@ class FeatureMaps(C.Structure):
 
 
 FEATURE_CHANNELS_MAX = 256  # GS_FEATURE_CHANNELS_MAX
+
+
+class PixelLift(C.Structure):
+    """gs_pixel_lift: the per-pixel channels, the mask and the two per-Gaussian sums of gs_lift_pixels (include/gs3d_hip.h)."""
+    _fields_ = [("values", C.c_void_p), ("channels", C.c_uint32), ("mask", C.c_void_p), ("out", C.c_void_p),
+                ("out_weight", C.c_void_p)]
+
+
+LIFT_CHANNELS_MAX = 256  # GS_LIFT_CHANNELS_MAX
+_FEATURE_MAPS_FN = None  # the torch.autograd.Function of Renderer.differentiable_feature_maps, defined when first asked for
+
+
+def _complete_callers_work(*tensors):
+    """gs_lift_pixels (and gs_blend_features under autograd) run on the renderer's own stream, which is non-blocking: nothing
+    orders it behind the stream the caller's tensors were produced on.  If any of `tensors` is a torch device tensor, wait on the
+    host for torch's CURRENT stream of that device: a fill, a copy, an optimizer step or a backward kernel still queued there has
+    then finished before the pass reads or adds to the tensor.  (The pass returns synchronised, so later work on torch's stream
+    is ordered behind it without more.)  Work queued on other streams is the caller's to order."""
+    import sys
+    torch = sys.modules.get("torch")
+    if torch is None:
+        return
+    for t in tensors:
+        if getattr(t, "is_cuda", False) is True:
+            torch.cuda.current_stream(t.device).synchronize()
+            return
+
+
+def _feature_maps_function():
+    """The autograd function behind Renderer.differentiable_feature_maps; torch is imported here, not with the module."""
+    global _FEATURE_MAPS_FN
+    if _FEATURE_MAPS_FN is None:
+        import torch
+
+        class FeatureMapsFunction(torch.autograd.Function):
+            """out = feature_maps(features) of the renderer's last frame; d/dfeatures only -- the frame is a constant."""
+
+            @staticmethod
+            def forward(ctx, renderer, features):
+                ctx.renderer, ctx.frame = renderer, renderer._frames
+                _complete_callers_work(features)  # (an optimizer step on the features may still be queued on torch's stream)
+                return renderer.feature_maps(features=features.detach().contiguous(), out=True)["out"]
+
+            @staticmethod
+            def backward(ctx, grad):
+                rend = ctx.renderer
+                if rend._frames != ctx.frame:
+                    raise RuntimeError(f"differentiable_feature_maps: the forward blended frame {ctx.frame} of this renderer, which has "
+                                       f"rendered frame {rend._frames} since; the gradient of another frame is not returned")
+                lifted = rend.lift_pixels(grad.contiguous().float(), out=True)["out"]
+                return None, lifted.to(torch.float32)
+
+        _FEATURE_MAPS_FN = FeatureMapsFunction
+    return _FEATURE_MAPS_FN
 
 
 def _tensor_exact(name, t, dtypes, shape, device, owner="Renderer.contributions"):
@@ -500,12 +554,14 @@ class Renderer:
         self.scene = scene
         self._h = C.c_void_p()
         self._frame_hw = None  # (height, width) of the last frame handed to render / render_host: what contributions() checks against
+        self._frames = 0       # frames handed to render / render_host: what a backward of differentiable_feature_maps checks against
         _check(lib().gs_renderer_create(scene._h, C.byref(self._h)))
 
     def render(self, uniforms, rgba_ptr=0, bgra_ptr=0):
         """Enqueue one frame into device buffers (raw pointers, e.g. tensor.data_ptr())."""
         _check(lib().gs_render(self._h, _p(uniforms), C.c_void_p(rgba_ptr), C.c_void_p(bgra_ptr)))
         self._frame_hw = (int(uniforms["height"][0]), int(uniforms["width"][0]))
+        self._frames += 1
 
     def contributions(self, weight=None, pixels=None, top_id=None, mask=None):
         """What every Gaussian contributed to the last frame (gs_accumulate_contributions), into torch tensors on the renderer's
@@ -569,6 +625,62 @@ class Renderer:
         _check(lib().gs_blend_features(self._h, C.byref(m)))
         return result
 
+    def lift_pixels(self, values, out=None, weight=None, mask=None):
+        """Per-pixel values of the last frame carried back onto its Gaussians (gs_lift_pixels), the transpose of feature_maps:
+        out (N, C) float64 += the sum over the counted pixels p that blend a Gaussian of w(p) * values[p], weight (N,) float64
+        += the sum of w itself, w = fl32(alpha T) as in contributions.  values float32 (H, W, C), or None for a weights-only
+        call; mask uint8 or bool (H, W): only pixels where it is not 0 are counted.  out and weight are each a tensor to ADD
+        into, True to have zeros allocated, or None to skip.  All are contiguous torch tensors on the renderer's device -- plain
+        device allocations, the adds are hardware float64 atomics.  N = the scene's Gaussians, (H, W) = the last frame,
+        C <= 256.  The order of the adds is unspecified: two calls agree to rounding, not bit for bit.  The arithmetic is the
+        reference's (exp mode 2) whatever mode the frame was blended in.  The pass runs on the renderer's own stream: the
+        wrapper first waits for torch's current stream, so that whatever was queued there to produce values, mask, out or weight
+        (the zeros of `True` included) is complete; producers on other streams are the caller's to order.  Returns
+        synchronised, with a dict of what was asked for (keys out, weight)."""
+        owner = "Renderer.lift_pixels"
+        n = int(self.scene.num_vertices)
+        dev = self.scene.device
+        asked = dict(out=out, weight=weight)
+        if self._frame_hw is None and any(v is True for v in asked.values()):
+            _check(lib().gs_lift_pixels(self._h, C.byref(PixelLift())))  # (refuses: there is no frame to size an input by)
+        h, w = self._frame_hw if self._frame_hw is not None else (None, None)
+        l = PixelLift()
+        channels = 0
+        if values is not None:
+            l.values = _tensor_exact("values", values, ("float32",), (h, w, None), dev, owner)
+            channels = int(values.shape[2])
+            if channels > LIFT_CHANNELS_MAX:
+                raise ValueError(f"values: {channels} channels, at most {LIFT_CHANNELS_MAX} are lifted in one call")
+            if out is None and channels > 0:  # (values of no channels: there is nothing to lift, a weights-only call)
+                raise ValueError("out: values are given but no output for them (pass a tensor or True)")
+        elif out is not None:
+            raise ValueError("out: an output for lifted values needs values")
+        l.channels = channels
+        if mask is not None:
+            l.mask = _tensor_exact("mask", mask, ("uint8", "bool"), (h, w), dev, owner)
+        shapes = dict(out=(n, channels), weight=(n,))
+        members = dict(out="out", weight="out_weight")
+        result = {}
+        for name, t in asked.items():
+            if t is None:
+                continue
+            if t is True:
+                import torch
+                t = torch.zeros(shapes[name], dtype=torch.float64, device=f"cuda:{int(dev)}")
+            setattr(l, members[name], _tensor_exact(name, t, ("float64",), shapes[name], dev, owner))
+            result[name] = t
+        _complete_callers_work(values, mask, *result.values())  # (the zeros allocated above among them: their fill is queued too)
+        _check(lib().gs_lift_pixels(self._h, C.byref(l)))
+        return result
+
+    def differentiable_feature_maps(self, features):
+        """feature_maps(features)["out"] as a torch.autograd.Function: features (N, C) float32 on the renderer's device -> the
+        (H, W, C) blended map of the last frame, differentiable with respect to `features` ONLY.  The frame -- positions,
+        opacities, covariances, the camera -- is a constant: the map is linear in features, and the backward is its transpose,
+        lift_pixels of the incoming gradient, rounded to float32.  A backward after this renderer has been handed another frame
+        raises RuntimeError instead of returning the gradient of a different frame."""
+        return _feature_maps_function().apply(self, features)
+
     def render_host(self, uniforms, want_rgba=True, want_bgra=False):
         h, w = int(uniforms["height"][0]), int(uniforms["width"][0])
         rgba = np.zeros((h, w, 4), np.float32) if want_rgba else None
@@ -576,6 +688,7 @@ class Renderer:
         _check(lib().gs_render_host(self._h, _p(uniforms), _p(rgba) if want_rgba else None,
                                     _p(bgra) if want_bgra else None))
         self._frame_hw = (h, w)
+        self._frames += 1
         return rgba, bgra
 
     def synchronize(self):

@@ -1,4 +1,4 @@
-// gs_kernels.h -- launch wrappers of the gfx950 kernels (gs_scene / gs_preprocess / gs_radix / gs_bin_l1 / gs_bin_l2 / gs_blend / gs_contrib / gs_features .hip).
+// gs_kernels.h -- launch wrappers of the gfx950 kernels (gs_scene / gs_preprocess / gs_radix / gs_bin_l1 / gs_bin_l2 / gs_blend / gs_contrib / gs_features / gs_lift .hip).
 // Host-side declarations only; everything takes raw device pointers + a stream.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -275,5 +275,15 @@ constexpr int kFeatureGroup = 16;
 void launch_features(const uint32_t* ranges, const uint32_t* sorted_gid, const uint32_t* tile_order, const AttrRecord* rec,
                      uint32_t width, uint32_t height, const float* features, uint32_t channels, float* out_features, float* out_alpha,
                      float* out_depth, float* out_median, hipStream_t s);
+
+// gs_lift_pixels (gs3d_hip.h; gs_lift.hip): the same second walk, transposed: per counted pixel (inside the image, mask null or
+// != 0) `channels` caller-supplied floats (values [height][width][channels]) are carried onto the Gaussians blended there with
+// k_contrib's w = fl32(alpha T): out[g][c] += (double)w values[p][c], out_weight[g] += (double)w, binary64 atomic adds.  Channels
+// go in groups of kLiftGroup, one launch per group on `s`, each walking the lists again; the first launch (or a channel-less one)
+// adds the weights.  mask, out, out_weight: nullable, device memory; with out null no channel is lifted.
+constexpr int kLiftGroup = 16, kLiftGroupSmall = 4;  // (a last group of at most 4 channels runs a kernel of 4)
+void launch_lift(const uint32_t* ranges, const uint32_t* sorted_gid, const uint32_t* tile_order, const AttrRecord* rec, uint32_t width,
+                 uint32_t height, const uint8_t* mask, const float* values, uint32_t channels, double* out, double* out_weight,
+                 hipStream_t s);
 
 }  // namespace gs

@@ -1131,6 +1131,29 @@ int gs_blend_features(gs_renderer* r, const gs_feature_maps* m) {
     });
 }
 
+int gs_lift_pixels(gs_renderer* r, const gs_pixel_lift* l) {
+    return guarded([&] {
+        if (!r || !l) throw Error(GS_ERR_INVALID, "null argument");
+        // (all by the members' values alone: nothing is dereferenced and no device is touched before they pass)
+        if (l->channels > GS_LIFT_CHANNELS_MAX) throw Error(GS_ERR_INVALID, "channels exceeds GS_LIFT_CHANNELS_MAX (256)");
+        if (l->channels > 0 && !l->values) throw Error(GS_ERR_INVALID, "channels > 0 needs values");
+        if (l->channels > 0 && !l->out) throw Error(GS_ERR_INVALID, "values given without out");
+        if (reinterpret_cast<uintptr_t>(l->values) % 4 != 0) throw Error(GS_ERR_INVALID, "values must be 4-byte aligned");
+        if (reinterpret_cast<uintptr_t>(l->out) % 8 != 0) throw Error(GS_ERR_INVALID, "out must be 8-byte aligned");
+        if (reinterpret_cast<uintptr_t>(l->out_weight) % 8 != 0) throw Error(GS_ERR_INVALID, "out_weight must be 8-byte aligned");
+        r->drain();  // queued frames retire; an overflowed one is re-run: the lists below are the last frame's, complete
+        if (!r->have_frame || !r->last_set) throw Error(GS_ERR_INVALID, "no frame rendered yet");
+        double* out = l->channels > 0 ? l->out : nullptr;  // channels == 0: that output is not touched
+        if (!out && !l->out_weight) return;
+        HIP_CHECK(hipSetDevice(r->scene->device));
+        const FrameBuffers& fb = *r->last_set;
+        gs::launch_lift(fb.ranges.p, fb.sorted.p, r->tile_order.p, fb.rec.p, r->last_width, r->last_height, l->mask, l->values,
+                        l->channels, out, l->out_weight, fb.stream);
+        HIP_CHECK(hipGetLastError());
+        fb.sync();
+    });
+}
+
 void* gs_renderer_stream(gs_renderer* r) { return r ? r->sets[0].stream : nullptr; }
 
 }  // extern "C"

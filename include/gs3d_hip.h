@@ -522,6 +522,62 @@ typedef struct {
     float* out_depth_median;    /* [height][width] */
 } gs_feature_maps;
 int gs_blend_features(gs_renderer* r, const gs_feature_maps* m);
+/* Per-pixel values of the LAST frame carried back onto its Gaussians: the transpose of gs_blend_features in its `features`
+ * argument, with the weights of gs_accumulate_contributions -- for lifting 2D maps into the scene without training (segmentation
+ * masks, multi-label votes, DINO / CLIP features, per-pixel error: out[g] / out_weight[g] accumulated over a camera set), for the
+ * gradient of gs_blend_features with respect to `features` (the frame's geometry is a constant), and for re-baking colours or
+ * per-Gaussian statistics from edited images.  No reference counterpart.  One more kernel (gs_lift.hip) walks the per-tile lists
+ * and attribute records the frame left in HBM; it reads ranges, lists and records of that frame and the caller's `values` and
+ * `mask`, and adds to the caller's two arrays and writes nothing the renderer owns: the next frame, the stage taps and captured
+ * graphs are unaffected.
+ *
+ * Per pixel the tile's list is walked exactly as gs_accumulate_contributions documents it (render.comp:61-89): `power > 0` skips
+ * an entry (:68), `alpha < 1/255` skips it (:78), `T (1 - alpha) < 1e-4` ends the walk (:83) -- ALWAYS with the reference's
+ * arithmetic: `power` with every product and sum rounded on its own, exp() = glibc's expf restated (exp mode 2), :78 decided on
+ * `power` against the record's alpha cut, whatever gs_set_exp_mode, gs_set_blend_contraction and gs_set_blend_lockstep say the
+ * frame ran with.  With gs_set_antialiased(1) the records carry opacity' and its cut, and the pass follows them.  Ids are SCENE
+ * ids, also for a scene that is read through its copy in spatial order: out[g] is the row of scene Gaussian g.
+ *
+ * A pixel is COUNTED if it lies inside the image and mask is NULL or not 0 there.  The mask gates what is recorded, never a
+ * pixel's T.  For a counted pixel p and an entry of Gaussian g that reaches :87 there, with that line's binary32 alpha and T (T
+ * before :88 updates it):
+ *     w              = fl32(alpha * T)                         the w of gs_accumulate_contributions
+ *     out[g][c]     += (double)w * (double)values[p][c]        for every channel c; the product of two binary32 values is exact
+ *     out_weight[g] += (double)w
+ * Both arrays are ADDED to (zero them once, call after each of many views).  Every add is a binary64 add; the ORDER of the adds
+ * is unspecified.  The sums are not integers, so -- unlike gs_accumulate_contributions -- two calls need not give the same bits.
+ * The result is within (n - 1) * 2^-53 * sum|terms| of the exact sum of the n terms a Gaussian receives (plus what the array
+ * held), and it is bit-exact whenever a Gaussian receives at most two terms into an element that held zero, because a binary64
+ * add is commutative.  A `values` row takes part only through the entries its own counted pixel blends: a NaN at an uncounted
+ * pixel, at a pixel outside every list, or at a pixel that skipped the entry reaches no output (a term is selected, never
+ * multiplied by zero); the values of an uncounted pixel are not read at all.
+ *
+ * Channels are processed in groups of 16 per launch, each launch walking the lists again; the first also adds the weights.  Per
+ * launch there is one device atomic per (blended entry, tile, channel), never one per pixel.  Cost: INTEGRATION.md, 3f.
+ *
+ * values [height][width][channels], channel innermost, floats, 4-byte aligned and nothing more; mask [height][width] bytes, any
+ * address; out [N][channels] row-major and out_weight [N], doubles, 8-byte aligned.  All are device pointers on the renderer's
+ * device.  out and out_weight must be ORDINARY device allocations (hipMalloc, a torch tensor): the adds are the hardware's
+ * global_atomic_add_f64, which fine-grained or host-coherent memory need not honour.  N = gs_scene_num_vertices, width and
+ * height those of the last frame, channels 0 .. GS_LIFT_CHANNELS_MAX.  The call synchronizes like gs_blend_features (queued frames
+ * retire, an overflowed frame is re-run), enqueues on the last frame's stream and returns when the arrays are written.
+ * That stream is the renderer's own and is NON-BLOCKING: the call waits for nothing the caller has queued elsewhere.  values, mask
+ * and the contents of out and out_weight -- the zeros they start from included -- must be COMPLETE when the call is made: the
+ * caller synchronises the stream that produces them first (hipStreamSynchronize, or an event this thread has waited on).  The
+ * Python wrapper does so for torch's current stream.
+ * GS_ERR_INVALID, checked before any device is touched: r or l NULL; channels > GS_LIFT_CHANNELS_MAX; channels > 0 with values
+ * NULL, or with out NULL while values is given (rejected rather than ignored); a misaligned pointer (judged by its value alone).
+ * GS_ERR_INVALID also when no frame has been rendered yet.  out and out_weight both NULL: success, nothing is launched.
+ * channels == 0 with out_weight given: only the weights are written; out, if given, is not touched. */
+#define GS_LIFT_CHANNELS_MAX 256
+typedef struct {
+    const float*   values;      /* [height][width][channels], channel innermost, device; NULL only with channels == 0 */
+    uint32_t       channels;    /* 0 .. GS_LIFT_CHANNELS_MAX */
+    const uint8_t* mask;        /* [height][width] bytes, nullable: only pixels where it is not 0 are counted */
+    double*        out;         /* [N][channels] row-major, ADDED to */
+    double*        out_weight;  /* [N], ADDED to: the sum of w itself */
+} gs_pixel_lift;
+int gs_lift_pixels(gs_renderer* r, const gs_pixel_lift* l);
 /* Test hook (tests/test_gpu_expf.py): evaluate the blend's exp() implementations ON THE DEVICE over the binary32 values with
  * bit patterns [first_bits, first_bits + count) (the negative floats run from 0x80000000 = -0 to 0xFF800000 = -inf).
  * block_sums[j] = sum over block j of 2^20 consecutive patterns of  bits(expf(x)) * ((bits(x) * 0x9E3779B1) | 1)  mod 2^64,
