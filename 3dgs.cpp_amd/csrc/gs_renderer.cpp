@@ -360,63 +360,95 @@ struct gs_renderer {
         return g;
     }
 
+    // What gs_render refuses because of the frame's size alone.  Depends on nothing but the size and min_bin_shift, which is fixed at
+    // creation: the entry points ask before they wait for a queued frame or allocate, and a refused call changes nothing.
+    void validate(const gs_uniforms& u) const {
+        const uint32_t tx = tiles_across(u.width), ty = tiles_across(u.height);
+        if (tx > 65535 || ty > 65535) throw Error(GS_ERR_INVALID, "resolution too large (tile box is 16-bit)");
+        (void)bin_geometry(tx, ty);
+    }
+
+    // The renderer has no last frame (any more): the taps and the three passes refuse until a frame that is enqueued from here on
+    // has retired.  `last`, what gs_get_stats reports, stays: the last frame that did retire.
+    void forget_last_frame() {
+        have_frame = false;
+        last_set = nullptr;
+        last_width = last_height = 0;
+        num_tiles = 0;
+        sorted_gid = depth_order = nullptr;
+    }
+    bool has_last_frame() const { return have_frame && last_set != nullptr; }
+
+    // ---- what a frame needs before it can be issued; asked before the wait of enqueue and again after it ----
+    // buffers of the frame's set that a frame of `nt` tiles at depth-order level `lv` needs and the set does not have
+    bool lacks_buffers(const FrameBuffers& fb, uint64_t nt, int lv) const {
+        return 2 * nt > fb.ranges.n || (lv >= kGlobalLevel && !fb.dkeys[0].p) || (lv == gs::kBinSlabLevel && !fb.slabs.p);
+    }
+    // the one-pass level 1: does a frame of this size take it now (L1FusedPolicy)?
+    L1FusedPolicy::Verdict l1_verdict(const gs_uniforms& u) const {
+        const BinGeometry g = bin_geometry(tiles_across(u.width), tiles_across(u.height));
+        return l1_policy.decide(policy.frame_level() < kGlobalLevel && g.bin_shift <= 3, scene->n < dense_min, scene->perm.p != nullptr,
+                                u.width, u.height, g.bin_shift, cand_capacity, g.bins_x * g.bins_y);
+    }
+    // ... kept off it only by bin regions that are too small, the candidate buffers grow once: to this many candidates (0: they stay)
+    uint32_t l1_growth(const gs_uniforms& u) const {
+        if (scene->n == 0 || u.width == 0 || u.height == 0) return 0;
+        const BinGeometry g = bin_geometry(tiles_across(u.width), tiles_across(u.height));
+        return l1_policy.grow_to(l1_verdict(u), u.width, u.height, g.bin_shift, cand_capacity, g.bins_x * g.bins_y, default_cand_capacity);
+    }
+
+    // Three parts, in this order.  (1) Refuse what cannot run: nothing has been touched.  (2) Wait, if this frame needs buffers that
+    // queued frames still use -- a failure of one of THOSE frames is thrown here, by rerun_queued, which has dropped them and the
+    // last frame with them; nothing of this frame exists yet.  (3) issue(): decide, allocate, launch.  The frame becomes "the last
+    // frame" only when every launch has been issued, and a failure in that part leaves the renderer without one (buffers of the last
+    // frame's set, or the tile table every set shares, may already be this frame's).
     void enqueue(const gs_uniforms& u, float* d_rgba, uint8_t* d_bgra) {
+        validate(u);
         HIP_CHECK(hipSetDevice(scene->device));
+        const uint32_t tx = tiles_across(u.width), ty = tiles_across(u.height);
+        // Every wait of this call.  New buffers, larger candidate buffers and a new tile table each wait for the queued frames that use
+        // the old ones.  Retiring them may re-run a frame at another depth-order level or bin size (retire_oldest) and allocates on
+        // the sets THEY run on: what this frame runs with, and which buffers its set lacks for that, is decided after the wait, when
+        // nothing is queued and nothing can change it any more -- a frame queued with the level of before the wait fails at once
+        // and, being judged as a failure of the new level, used to push the renderer onto the global path for slab_hold frames; and
+        // a set that was looked at before the wait may lack the buffers of the level the wait ended at
+        const bool new_grid = !(tx == order_tx && ty == order_ty && tile_order.p);
+        if (pending > 0 && (new_grid || lacks_buffers(sets[frames_enqueued % num_sets], static_cast<uint64_t>(tx) * ty, policy.frame_level()) ||
+                            l1_growth(u) != 0))
+            drain();
+        try {
+            issue(u, d_rgba, d_bgra);
+        } catch (...) {
+            forget_last_frame();
+            throw;
+        }
+    }
+
+    // Part (3) of enqueue.  Nothing that is queued needs to retire in here (ensure_tile_order's own drain finds nothing queued).
+    void issue(const gs_uniforms& u, float* d_rgba, uint8_t* d_bgra) {
         FrameSlot& sl = slots[frames_enqueued % kSlots];
         FrameBuffers& fb = sets[frames_enqueued % num_sets];
         hipStream_t stream = fb.stream;
         const uint32_t n = static_cast<uint32_t>(scene->n);
         const uint32_t tx = tiles_across(u.width), ty = tiles_across(u.height);
-        if (tx > 65535 || ty > 65535) throw Error(GS_ERR_INVALID, "resolution too large (tile box is 16-bit)");
         const uint64_t nt = static_cast<uint64_t>(tx) * ty;
-        auto lacks_buffers = [&](int at_level) {
-            return 2 * nt > fb.ranges.n || (at_level >= kGlobalLevel && !fb.dkeys[0].p) || (at_level == gs::kBinSlabLevel && !fb.slabs.p);
-        };
-        if (lacks_buffers(policy.frame_level())) {
-            // (re)allocation: wait for queued frames that still use the old buffers.  Retiring them may re-run a frame at another
-            // depth-order level or bin size (retire_oldest): what THIS frame runs with is decided after the wait, not before
-            // -- a frame queued with the level of before the wait fails at once and, being judged as a failure of the new
-            // level, used to push the renderer onto the global path for slab_hold frames
-            drain();
-            const int at_level = policy.frame_level();
+        const bool fused_counters = n != 0 && u.width != 0 && u.height != 0;
+        const int lv = policy.frame_level();
+        if (lacks_buffers(fb, nt, lv)) {
             fb.ranges.ensure(2 * nt);
-            if (at_level >= kGlobalLevel) fb.ensure_depth_order();
-            if (at_level == gs::kBinSlabLevel && !fb.slabs.p) {
+            if (lv >= kGlobalLevel) fb.ensure_depth_order();
+            if (lv == gs::kBinSlabLevel && !fb.slabs.p) {
                 fb.slabs.alloc(static_cast<size_t>(gs::kSlabCapacity) * gs::kSlabDescBytes);
                 HIP_CHECK(hipMemset(fb.slabs.p, 0, fb.slabs.n));  // no descriptor carries a launch's epoch yet
             }
         }
-        const bool fused_counters = n != 0 && u.width != 0 && u.height != 0;
-        // ---- the one-pass level 1: does this frame take it (L1FusedPolicy)?  Kept off only by bin regions that are too small, the
-        // candidate buffers grow once (which waits for the queued frames: the verdict is taken again after the wait)
-        auto l1_verdict = [&]() {
-            const BinGeometry g = bin_geometry(tx, ty);
-            const int at_level = policy.frame_level();
-            return l1_policy.decide(at_level < kGlobalLevel && g.bin_shift <= 3, n < dense_min, scene->perm.p != nullptr, u.width, u.height,
-                                    g.bin_shift, cand_capacity, g.bins_x * g.bins_y);
-        };
-        if (fused_counters) {
-            const BinGeometry g = bin_geometry(tx, ty);
-            if (l1_policy.grow_to(l1_verdict(), u.width, u.height, g.bin_shift, cand_capacity, g.bins_x * g.bins_y, default_cand_capacity) != 0) {
-                drain();
-                const BinGeometry g2 = bin_geometry(tx, ty);
-                const uint32_t grow = l1_policy.grow_to(l1_verdict(), u.width, u.height, g2.bin_shift, cand_capacity, g2.bins_x * g2.bins_y,
-                                                        default_cand_capacity);
-                if (grow > cand_capacity) set_cand_capacity(grow);
-            }
-        }
-        // (after any drain above: retiring may re-run frames through enqueue, which would leave another set's buffers here)
-        last_set = &fb;
-        last_width = u.width;
-        last_height = u.height;
+        if (const uint32_t grow = l1_growth(u); grow > cand_capacity) set_cand_capacity(grow);
+        ensure_tile_order(tx, ty);
         const int tune_shape = tuners.select(u.width, u.height);  // this frame shape's own tuner (a new shape measures afresh)
         const BlendTuner& tuner = tuners.current();
         const bool lockstep = tuner.current();
         const BinGeometry geo = bin_geometry(tx, ty);
-        const int lv = policy.frame_level();
         const bool bin_local = lv < kGlobalLevel;
-        num_tiles = nt;
-        ensure_tile_order(tx, ty);
         lap(2);
 
         gs::SceneView sv{scene->render_blob(), scene->cov3d.p, n, static_cast<uint32_t>(gs::blob_stride(n)),
@@ -426,14 +458,13 @@ struct gs_renderer {
         // list of visible Gaussians, which k_preprocess then writes beside the planes
         const bool l1_any_order = bin_local && geo.bin_shift <= 3;
         // (the lists exist only for scenes of >= dense_min Gaussians: FrameBuffers::init; the blend zeroes their counters)
-        const bool l1_fused = fused_counters && l1_verdict() == L1FusedPolicy::kEngage;
+        const bool l1_fused = fused_counters && l1_verdict(u) == L1FusedPolicy::kEngage;
         const bool dense_list = l1_any_order && !l1_fused && n != 0 && wants_dense_lists() && fb.vis.p && u.width != 0 && u.height != 0;
         gs::AttrView av{fb.tiles.p, fb.depth.p, fb.aabb.p, fb.rec.p, dense_list ? fb.vis.p : nullptr, dense_list ? fb.vis_count.p : nullptr,
                         fb.vis_region_slots};
         const uint32_t l1_cap = L1FusedPolicy::region_cap(cand_capacity, geo.bins_x * geo.bins_y);
         const gs::L1Fused lf{l1_fused ? fb.l1_words.p : nullptr, fb.cand.p, l1_cap, fb.vis_mask.p, tx, ty, geo.bins_x, geo.bins_y, geo.bin_shift, geo.grid_shift};
         fb.planes_stale = dense_list ? 1 : (l1_fused ? 2 : 0);
-        last_l1_fused = l1_fused;
 
         // the first and the last kernel of the frame clear / publish the counters themselves; the blit nodes (and
         // their fences) are only needed when one of the two is not launched
@@ -529,8 +560,6 @@ struct gs_renderer {
             gs::launch_frame_end(stamps, sl.h_stamps, fp, lf.words, gs::kVisRegions + (1u << (2 * geo.grid_shift)), stream);
             lap(7);
         };
-        depth_order = bin_local ? nullptr : fb.dvals[1].p;
-        sorted_gid = fb.sorted.p;
         const bool replay = graph_mode && fused_counters;
         if (replay) {
             *sl.h_params = gs::FrameParams{u, d_rgba, d_bgra, sl.h_counters, sl.h_stamps};
@@ -564,6 +593,15 @@ struct gs_renderer {
         if (!fused_counters) HIP_CHECK(hipMemcpyAsync(sl.h_counters, cnt, sizeof(gs::Counters), hipMemcpyDeviceToHost, stream));
         HIP_CHECK(hipEventRecord(sl.done, stream));
         HIP_CHECK(hipGetLastError());
+
+        // every launch has been issued: this is the last frame now
+        last_set = &fb;
+        last_width = u.width;
+        last_height = u.height;
+        num_tiles = nt;
+        last_l1_fused = l1_fused;
+        depth_order = bin_local ? nullptr : fb.dvals[1].p;
+        sorted_gid = fb.sorted.p;
 
         sl.level = lv;
         sl.bin_shift = geo.bin_shift;
@@ -635,10 +673,14 @@ struct gs_renderer {
             }
         }
         if (debug_levels) report_overflow();
-        // the queued frames are dropped from the ring first: whatever is thrown below, the renderer stays usable
+        // the queued frames are dropped from the ring first: whatever is thrown below, the renderer stays usable.  The last frame is
+        // one of them (the most recently enqueued one): its set holds the lists of a frame that overflowed or never finished, and
+        // the renderer has no last frame until the frames enqueued again below have retired -- or, if one of the errors below is
+        // thrown instead, until a later frame has
         frames_enqueued -= pending;
         pending = 0;
         prev_retired = false;
+        forget_last_frame();
         switch (policy.frames_overflowed(ran.data(), static_cast<int>(ran.size()))) {
             case DepthPolicy::kDepthsTooCrowded:
                 throw Error(GS_ERR_OVERFLOW, "a bin's depths are too crowded for the bin-local order (one depth bucket beyond a slab, or more than 65 equal depths in one): needs the global depth-order path");
@@ -786,6 +828,7 @@ int gs_render(gs_renderer* r, const gs_uniforms* u, float* d_rgba, uint8_t* d_bg
     return guarded([&] {
         if (!r || !u) throw Error(GS_ERR_INVALID, "null argument");
         if (u->width == 0 || u->height == 0) throw Error(GS_ERR_INVALID, "empty framebuffer");
+        r->validate(*u);  // (before any queued frame is waited for: a refused call changes nothing)
         r->lap(0);
         r->make_room();  // at most in_flight_limit frames queued; resolves pending overflows first
         r->lap(1);
@@ -800,6 +843,7 @@ int gs_render_host(gs_renderer* r, const gs_uniforms* u, float* h_rgba, uint8_t*
     return guarded([&] {
         if (!r || !u) throw Error(GS_ERR_INVALID, "null argument");
         if (u->width == 0 || u->height == 0) throw Error(GS_ERR_INVALID, "empty framebuffer");
+        r->validate(*u);  // (before anything is allocated or waited for: a refused call changes nothing)
         HIP_CHECK(hipSetDevice(r->scene->device));
         const size_t px = static_cast<size_t>(u->width) * u->height;
         DevBuf<float> d_rgba;
@@ -845,7 +889,7 @@ int gs_get_stats(gs_renderer* r, gs_frame_stats* out) {
         r->drain();
         r->latest_stats(out);
         // written by the blend itself, after it published the other counters: read from the device (everything has retired)
-        if (r->have_frame && r->last_set && r->last_set->counters.p) {
+        if (r->has_last_frame() && r->last_set->counters.p) {
             gs::Counters c{};
             HIP_CHECK(hipMemcpy(&c, r->last_set->counters.p, sizeof c, hipMemcpyDeviceToHost));
             out->blend_redo = c.blend_redo;
@@ -999,7 +1043,7 @@ int gs_debug_download(gs_renderer* r, int stage, void* dst, uint64_t bytes) {
     return guarded([&] {
         if (!r || !dst) throw Error(GS_ERR_INVALID, "null argument");
         r->drain();
-        if (!r->have_frame) throw Error(GS_ERR_INVALID, "no frame rendered yet");
+        if (!r->has_last_frame()) throw Error(GS_ERR_INVALID, "no frame rendered yet");
         if (stage == GS_STAGE_DEPTH_ORDER && !r->depth_order)
             throw Error(GS_ERR_INVALID, "the depth-order tap exists only on the global depth-order path (gs_set_sort_path(r, 1))");
         const uint64_t n = r->scene->n, v = r->last.num_visible;
@@ -1094,7 +1138,7 @@ int gs_accumulate_contributions(gs_renderer* r, const gs_contributions* c) {
         if (reinterpret_cast<uintptr_t>(c->pixels) % 4 != 0) throw Error(GS_ERR_INVALID, "pixels must be 4-byte aligned");
         if (reinterpret_cast<uintptr_t>(c->top_id) % 4 != 0) throw Error(GS_ERR_INVALID, "top_id must be 4-byte aligned");
         r->drain();  // queued frames retire; an overflowed one is re-run: the lists below are the last frame's, complete
-        if (!r->have_frame || !r->last_set) throw Error(GS_ERR_INVALID, "no frame rendered yet");
+        if (!r->has_last_frame()) throw Error(GS_ERR_INVALID, "no frame rendered yet");
         if (!c->weight && !c->pixels && !c->top_id) return;
         HIP_CHECK(hipSetDevice(r->scene->device));
         const FrameBuffers& fb = *r->last_set;
@@ -1119,7 +1163,7 @@ int gs_blend_features(gs_renderer* r, const gs_feature_maps* m) {
         for (const auto& q : ptrs)
             if (reinterpret_cast<uintptr_t>(q.p) % 4 != 0) throw Error(GS_ERR_INVALID, q.what);
         r->drain();  // queued frames retire; an overflowed one is re-run: the lists below are the last frame's, complete
-        if (!r->have_frame || !r->last_set) throw Error(GS_ERR_INVALID, "no frame rendered yet");
+        if (!r->has_last_frame()) throw Error(GS_ERR_INVALID, "no frame rendered yet");
         float* out_features = m->channels > 0 ? m->out_features : nullptr;  // channels == 0: that output is not touched
         if (!out_features && !m->out_alpha && !m->out_depth && !m->out_depth_median) return;
         HIP_CHECK(hipSetDevice(r->scene->device));
@@ -1142,7 +1186,7 @@ int gs_lift_pixels(gs_renderer* r, const gs_pixel_lift* l) {
         if (reinterpret_cast<uintptr_t>(l->out) % 8 != 0) throw Error(GS_ERR_INVALID, "out must be 8-byte aligned");
         if (reinterpret_cast<uintptr_t>(l->out_weight) % 8 != 0) throw Error(GS_ERR_INVALID, "out_weight must be 8-byte aligned");
         r->drain();  // queued frames retire; an overflowed one is re-run: the lists below are the last frame's, complete
-        if (!r->have_frame || !r->last_set) throw Error(GS_ERR_INVALID, "no frame rendered yet");
+        if (!r->has_last_frame()) throw Error(GS_ERR_INVALID, "no frame rendered yet");
         double* out = l->channels > 0 ? l->out : nullptr;  // channels == 0: that output is not touched
         if (!out && !l->out_weight) return;
         HIP_CHECK(hipSetDevice(r->scene->device));

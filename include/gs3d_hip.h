@@ -297,7 +297,24 @@ int gs_camera_uniforms(const gs_camera* cam, uint32_t width, uint32_t height, gs
  * Asynchronous: returns after enqueueing; gs_synchronize() or gs_get_stats() waits.
  * The instance count stays on the device (no mid-frame readback, cf. Renderer.cpp:391-399);
  * an overflow of the instance buffers is detected at the next gs_synchronize/gs_get_stats,
- * which grows them and re-runs the frame (Renderer.cpp:541-563). */
+ * which grows them and re-runs the frame (Renderer.cpp:541-563).
+ *
+ * "The last frame" -- what the stage taps, gs_accumulate_contributions, gs_blend_features and gs_lift_pixels answer from -- is the
+ * most recently enqueued frame, once it has retired.  What an error of gs_render / gs_render_host leaves of it:
+ *   * A REFUSED call changes nothing.  Refused (GS_ERR_INVALID, before any queued frame is waited for and before anything is
+ *     allocated): a null argument, an empty framebuffer, a tile box beyond 16 bits, a resolution beyond the tile binning.  The
+ *     last frame is still the last frame: every tap and every pass gives what it gave before the call, queued frames stay
+ *     queued, and the next frame -- one replayed from a captured graph too -- is what it would have been without the call.
+ *   * A call that FAILS WHILE RETIRING queued frames -- GS_ERR_OVERFLOW: a bin too full or depths too crowded for the forced
+ *     bin-local path (gs_set_sort_path(r, 2)), instance buffers that overflowed repeatedly, more than 2^30 tile instances or
+ *     level-1 candidates -- leaves the renderer WITHOUT a last frame.  Every queued frame was dropped: none of their targets is
+ *     valid, and the frame of the failing call, if any, was not enqueued.  The taps and the three passes return GS_ERR_INVALID
+ *     ("no frame rendered yet") until a frame rendered after the failure has retired; gs_get_stats keeps describing the last
+ *     frame that did retire (blend_redo / blend_resolved, which are read from the device, are 0 meanwhile).  The renderer
+ *     renders on: after gs_set_sort_path(r, 0) the same pose gives the right frame.  The same holds for gs_synchronize,
+ *     gs_get_stats and every other call that waits for queued frames and returns such an error.
+ *   * A device or allocation error (GS_ERR_DEVICE, GS_ERR_NOMEM) while the frame is being issued also leaves the renderer
+ *     without a last frame. */
 int gs_render(gs_renderer* r, const gs_uniforms* u, float* d_rgba, uint8_t* d_bgra);
 
 /* Convenience: gs_render into host buffers, synchronous. */
@@ -422,7 +439,9 @@ int gs_get_stats(gs_renderer* r, gs_frame_stats* out);
 int gs_poll_stats(gs_renderer* r, gs_frame_stats* out, uint64_t* frames_retired);
 /* Copy a stage buffer of the last frame to host memory; synchronizes.  The per-tile lists live bin-major in HBM;
  * GS_STAGE_SORTED_GID / _SORTED_TILE / _RANGES present them laid end to end in tile order, i.e. as the reference's
- * sorted payload, the tile half of its sorted keys and its tileBoundaryBuffer. */
+ * sorted payload, the tile half of its sorted keys and its tileBoundaryBuffer.  GS_ERR_INVALID ("no frame rendered yet") before
+ * the first frame and while the renderer has no last frame (gs_render: a call that failed while retiring queued frames); a
+ * refused gs_render changes no tap. */
 int gs_debug_download(gs_renderer* r, int stage, void* dst, uint64_t bytes);
 /* What every Gaussian contributed to the LAST frame: its weight, the pixels it was blended in, and per pixel the Gaussian that
  * dominates it -- for pruning by significance over a set of views, brush / lasso selection (mask) and click-to-pick (top_id).
@@ -458,7 +477,8 @@ int gs_debug_download(gs_renderer* r, int stage, void* dst, uint64_t bytes);
  * height those of the last frame.  The call synchronizes like gs_debug_download (queued frames retire, an overflowed frame is
  * re-run), enqueues on the last frame's stream and returns when the arrays are written.  GS_ERR_INVALID: r or c NULL (checked
  * before any device is touched), no frame rendered yet, a misaligned pointer (judged by its value alone).  All three outputs
- * NULL: nothing is launched. */
+ * NULL: nothing is launched.  "No frame rendered yet" is also the answer while the renderer has no last frame (gs_render: after
+ * a call that failed while retiring queued frames; nothing is written then); a refused gs_render changes nothing the pass gives. */
 typedef struct {
     const uint8_t* mask;
     uint64_t* weight;
@@ -510,7 +530,9 @@ int gs_accumulate_contributions(gs_renderer* r, const gs_contributions* c);
  * frames retire, an overflowed frame is re-run), enqueues on the last frame's stream and returns when the arrays are written.
  * GS_ERR_INVALID, checked before any device is touched: r or m NULL; channels > GS_FEATURE_CHANNELS_MAX; channels > 0 with
  * features NULL, or with out_features NULL while features is given (rejected rather than ignored); a misaligned pointer (judged
- * by its value alone).  GS_ERR_INVALID also when no frame has been rendered yet.  All four outputs NULL: success, nothing is
+ * by its value alone).  GS_ERR_INVALID also when no frame has been rendered yet, and while the renderer has no last frame
+ * (gs_render: after a call that failed while retiring queued frames; nothing is written then); a refused gs_render changes
+ * nothing the pass gives.  All four outputs NULL: success, nothing is
  * launched.  channels == 0 with out_features given: that output is not touched. */
 #define GS_FEATURE_CHANNELS_MAX 256
 typedef struct {
@@ -567,7 +589,9 @@ int gs_blend_features(gs_renderer* r, const gs_feature_maps* m);
  * Python wrapper does so for torch's current stream.
  * GS_ERR_INVALID, checked before any device is touched: r or l NULL; channels > GS_LIFT_CHANNELS_MAX; channels > 0 with values
  * NULL, or with out NULL while values is given (rejected rather than ignored); a misaligned pointer (judged by its value alone).
- * GS_ERR_INVALID also when no frame has been rendered yet.  out and out_weight both NULL: success, nothing is launched.
+ * GS_ERR_INVALID also when no frame has been rendered yet, and while the renderer has no last frame (gs_render: after a call
+ * that failed while retiring queued frames; nothing is added then); a refused gs_render changes nothing the pass gives, up to
+ * the order of its adds.  out and out_weight both NULL: success, nothing is launched.
  * channels == 0 with out_weight given: only the weights are written; out, if given, is not touched. */
 #define GS_LIFT_CHANNELS_MAX 256
 typedef struct {
