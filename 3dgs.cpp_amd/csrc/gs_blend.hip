@@ -4,7 +4,7 @@
 // binary32, one rounding per operation, in the order the reference shader writes it" (DESIGN.md section 3); fused
 // multiply-adds appear only where written explicitly.
 // Reference restated (paths relative to /root/reference/src/shaders): render.comp:30-99
-#include "gs_device.h"
+#include "gs_tile_walk.h"  // (and gs_device.h through it)
 
 namespace gs {
 
@@ -45,7 +45,8 @@ namespace gs {
 // the entry for that wave changes nothing.
 // ---------------------------------------------------------------------------------------
 
-// (min_q_rect, the minimum of an entry's quadratic over a pixel rectangle: gs_device.h -- k_contrib culls with it too)
+// (quadrant_keep -- that test with its slack -- and min_q_rect, the minimum of an entry's quadratic over a pixel rectangle:
+//  gs_tile_walk.h; the passes over the last frame's lists cull with them too)
 
 #if defined(GS_BLEND_STATS) || defined(GS_BLEND_CLOCK)
 // debug instrumentation (separate builds, never the shipped library).  GS_BLEND_STATS: the work counters (they live in the compiler's
@@ -425,25 +426,11 @@ __device__ __forceinline__ bool blend_walk(const uint2 range, const uint32_t* __
             const uint32_t i2 = i1 + WAVE;
             if (i2 < range.y) g_next = sorted_gid[i2];
         }
-        // classify entry `lane` of this chunk against the wave's quadrant.  cut = +inf: no power <= 0 is kept (never
-        // enters); -inf (NaN or infinite opacity: min(0.99, NaN) is 0.99 in the pipeline's definition): never culled
+        // classify entry `lane` of this chunk against the wave's quadrant (gs_tile_walk.h: quadrant_keep, with its slack).
+        // (the conic scaled by a power of two: the quadrant test and the staged record share the two products)
         const float cut = cur.bc.y;
-        // (the conic scaled by a power of two: exact, and |c / 2| = |c| / 2 bit for bit -- the quadrant test, its slack and the
-        //  staged record share the two products)
         const float h00 = 0.5f * cur.co.x, h11 = 0.5f * cur.co.z;
-        uint64_t bm = __builtin_amdgcn_ballot_w64(have) & __builtin_amdgcn_ballot_w64(cut <= 0.0f);
-        {   // (every lane: the wave pays for these instructions as soon as one lane needs them, and the AND of two scalar masks
-            //  needs no branch and no rebuilding from a VGPR; what a lane without an entry computes is never looked at)
-            const float mq = min_q_rect(h00, cur.co.y, h11, cur.bc.z, cur.bc.w, cur.uv.x, cur.uv.y, rx0, rx1, ry0, ry1);
-            // The rounding error of the shader's `power` (and of mq) is relative to the TERMS c00 dx^2, c11 dy^2,
-            // c01 dx dy, not to their sum: a thin diagonal splat far from its centre has terms ~1e5 cancelling to
-            // q ~ 5.  The slack therefore grows with the terms at the quadrant's corner farthest from the centre
-            // (16 roundings of 2^-24 each, generously).
-            const float ax = fmaxf(fabsf(cur.uv.x - rx0), fabsf(cur.uv.x - rx1));
-            const float ay = fmaxf(fabsf(cur.uv.y - ry0), fabsf(cur.uv.y - ry1));
-            const float mag = __builtin_fmaf(fabsf(h00) * ax, ax, __builtin_fmaf(fabsf(h11) * ay, ay, fabsf(cur.co.y) * ax * ay));
-            bm &= __builtin_amdgcn_ballot_w64(!(mq > __builtin_fmaf(mag, 9.6e-7f, -cut)));  // NaN -> keep
-        }
+        uint64_t bm = quadrant_keep(h00, cur.co.y, h11, cut, cur.bc.z, cur.bc.w, cur.uv.x, cur.uv.y, have, rx0, rx1, ry0, ry1);
         const bool keep = __builtin_amdgcn_inverse_ballot_w64(bm);  // (the scalar mask as the lanes' predicate, as it is)
         STAT_ADD(0, 1);
         STAT_ADD(6, __popcll(__ballot(have)));

@@ -216,33 +216,4 @@ __device__ __forceinline__ float alpha_cut_seeded(float o, const uint2* __restri
     return __uint_as_float(lo);
 }
 
-// ---------------------------------------------------------------------------------------
-// The quadrant test of the tile walks (gs_blend.hip: blend_walk; gs_contrib.hip: k_contrib).
-// min over the pixel rectangle [xa,xb] x [ya,yb] of q(d) = 0.5 (c00 dx^2 + c11 dy^2) + c01 dx dy,
-// d = uv - pixel.  q is convex with its minimum 0 at d = 0: inside the rectangle the answer is 0,
-// otherwise the minimum lies on an edge facing the centre, where q is a 1-D parabola.
-// h00 = c00 / 2, h11 = c11 / 2; r11 = -c01 rcp(c11), r00 = -c01 rcp(c00): the entry's own terms, carried in its record.
-__device__ __forceinline__ float min_q_rect(float h00, float c01, float h11, float r11, float r00, float u, float v, float xa,
-                                            float xb, float ya, float yb) {
-    const float dx_lo = u - xb, dx_hi = u - xa, dy_lo = v - yb, dy_hi = v - ya;
-    const bool in_x = !(dx_lo > 0.0f) && !(dx_hi < 0.0f), in_y = !(dy_lo > 0.0f) && !(dy_hi < 0.0f);  // NaN -> inside
-    // This is a bound, not part of the pipeline's arithmetic: FMAs are welcome (the caller's slack covers rounding).
-    // q(a, t) = h00 a^2 + t (h11 t + c01 a) with h = c / 2.  Only the edges that face the centre can hold the minimum
-    // (a segment from the centre to a point of a far edge crosses a near edge, where the convex q is smaller): at most
-    // one vertical and one horizontal edge; on an edge one coordinate is fixed and the other is the parabola's
-    // minimiser r * fixed, clamped to the edge.
-    const float a = dx_lo > 0.0f ? dx_lo : dx_hi;  // the vertical edge nearer to the centre: dx fixed, parabola in dy
-    const float t = fminf(fmaxf(r11 * a, dy_lo), dy_hi);
-    const float qv = __builtin_fmaf(t, __builtin_fmaf(h11, t, c01 * a), h00 * a * a);
-    const float b = dy_lo > 0.0f ? dy_lo : dy_hi;  // the horizontal edge nearer to the centre
-    const float s = fminf(fmaxf(r00 * b, dx_lo), dx_hi);
-    const float qh = __builtin_fmaf(s, __builtin_fmaf(h00, s, c01 * b), h11 * b * b);
-    // The cull `mq > lim` needs mq to be a LOWER bound of q over the quadrant, and evaluating the parabola at an inexact
-    // minimiser (r11, r00 are v_rcp_f32's, 1 ULP, evaluated once per Gaussian in k_preprocess instead of once per wave and entry
-    // here) OVER-estimates its minimum -- by a second-order amount: q(t* + dt) - q(t*) = h dt^2 with
-    // dt/t* ~ 2^-23, i.e. ~1e-14 relative, which the caller's slack (9.6e-7 x the quadratic's largest terms) absorbs
-    // many times over.  A coarser reciprocal or a smaller slack must revisit this.
-    return in_x ? (in_y ? 0.0f : qh) : (in_y ? qv : fminf(qv, qh));
-}
-
 }  // namespace gs

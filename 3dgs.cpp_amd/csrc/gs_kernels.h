@@ -43,7 +43,7 @@ struct AttrRecord {
     float4 conic_op;   // c00 c01 c11 opacity
     float4 uv_rg;      // u v r g
     // b, alpha cut (the most negative `power` at which render.comp:78 keeps the entry), and the two entry-only terms of the
-    // blend's quadrant test: r11 = -c01 rcp(c11), r00 = -c01 rcp(c00) (gs_blend.hip, min_q_rect), evaluated once per Gaussian
+    // blend's quadrant test: r11 = -c01 rcp(c11), r00 = -c01 rcp(c00) (gs_tile_walk.h, min_q_rect), evaluated once per Gaussian
     // here instead of once per (wave, entry) there
     float4 b_cut_r;
     float4 depth_radius;  // depth, radius, 0, 0: read by the stage taps only (k_preprocess writes a record as one full 64-byte line)

@@ -5,17 +5,16 @@
 // product and sum below is rounded on its own.  No kernel of the frame lives here and none is touched: the pass READS the per-tile
 // lists (ranges, sorted_gid), the attribute records the last frame left in HBM, the caller's mask and values, and ADDS to
 // caller-owned arrays only.
-// Reference restated: render.comp:61-89 (the shader gs_blend.hip restates).
-#include "gs_device.h"
+// Reference restated: render.comp:61-89 (the shader gs_blend.hip restates), in gs_tile_walk.h.
+#include "gs_tile_walk.h"
 
 namespace gs {
 
 // ---------------------------------------------------------------------------------------
-// The definition.  A pixel walks its tile's list as render.comp:61-89 does -- `power > 0` skips the entry (:68), `alpha < 1/255`
-// skips it (:78, decided on `power` against the record's alpha cut, as every blend mode decides it), `T (1 - alpha) < 1e-4` ends
-// the walk (:83) -- always with the REFERENCE's arithmetic, whatever mode the frame was blended in: `power` uncontracted,
-// exp = gs_expf_libm.  An entry of Gaussian g that reaches :87 at a COUNTED pixel p (inside the image, mask NULL or != 0 there) is
-// blended there with w = fl32(alpha T) (T as :87 reads it, before :88), k_contrib's w, and contributes
+// The definition.  A pixel walks its tile's list as render.comp:61-89 does, always with the REFERENCE's arithmetic, whatever mode
+// the frame was blended in (gs_tile_walk.h: walk_chunk).  An entry of Gaussian g that reaches :87 at a COUNTED pixel p (inside
+// the image, mask NULL or != 0 there) is blended there with w = fl32(alpha T) (T as :87 reads it, before :88), k_contrib's w, and
+// contributes
 //     out[g][c]     += (double)w * (double)values[p][c]      (the product of two binary32 values is exact in binary64)
 //     out_weight[g] += (double)w
 // Every add is a binary64 add and the order of the adds is unspecified: the sums are not integers, so two calls need not give the
@@ -24,12 +23,9 @@ namespace gs {
 // by zero: a NaN at an uncounted pixel (never read), at a pixel outside every list, or in a lane that skipped the entry reaches no
 // output.
 //
-// The shape is k_contrib's.  One workgroup per tile in tile_order, one pixel per lane, a wave per 8 x 8 quadrant -- the blend's
-// geometry, so the blend's exact quadrant test (gs_device.h: min_q_rect, the same slack) lets a wave skip the entries none of its
-// pixels keeps.  The list is taken in chunks of 64 entries STAGED ONCE PER WORKGROUP: waves 0, 1, 2 gather one 16-byte third of
-// the 64 records each (the 48 bytes the walk reads), wave 3 keeps the chunk's ids; the next chunk's records (and the ids of the
-// chunk after it) are loaded into registers while this one is walked.  A lane loads its own pixel's channels of the launch's
-// group ONCE, before the loop, and only if the pixel is counted (in the order lift_reduce wants them, which differs by lane).
+// The shape is the shared walk's (gs_tile_walk.h: tile per workgroup, quadrant per wave, chunks of 64 staged once per workgroup).
+// Beside the records, wave 3 keeps the chunk's ids.  A lane loads its own pixel's channels of the launch's group ONCE, before the
+// loop, and only if the pixel is counted (in the order lift_reduce wants them, which differs by lane).
 //
 // The wave's partial.  Per (entry, wave) that some counted lane blends -- nothing happens for an empty ballot, the common case --
 // every lane forms its terms t_c = (double)w (double)v[c], with w and v[c] SELECTED to 0 in a lane that does not blend the entry,
@@ -51,10 +47,8 @@ namespace gs {
 // s_cnt[entry] in one instruction at the top, before the channel-0 lane's store to it further down: a wave has one program
 // counter and the LDS takes a wave's instructions in order, so no lane can see the cleared count.
 //
-// Barriers.  Two per chunk (staged -> walk -> flush), taken by ALL FOUR waves of the tile: a wave whose counted pixels have all
-// broken (or that never had one) walks nothing more but stays -- it is a third of the loader and a quarter of the flush -- and
-// says so once in s_done; the workgroup leaves the loop together, at the chunk after which s_done reads 4 or at the list's end.
-// No wave ends early, so no barrier waits for a wave that has left (cf. gs_blend.hip's header), and no barrier follows the loop.
+// Barriers: the two per chunk of gs_tile_walk.h (staged -> walk -> flush), taken by all four waves; a wave that walks nothing more
+// stays as a third of the loader and a quarter of the flush.
 // What lies between the second barrier of chunk i and the first of chunk i + 1 is the flush of i and the staging of i + 1, by
 // different threads with no order between them, so they must not touch the same words:
 //   - the flush reads and clears s_acc, s_w, s_cnt, which the staging does not touch (the slots start zero, cleared before the
@@ -64,8 +58,7 @@ namespace gs {
 //     chunk's parity.  Buffer i & 1 is written again by the staging of i + 2, after barrier one of i + 1, i.e. after every
 //     thread has finished the flush of i;
 //   - the staging writes s_rec, which only the walk reads, between the two barriers of one chunk, as in k_contrib.
-// So the two barriers suffice and there is no third.  s_done is written only between the two barriers of a chunk and read only
-// after the second: the exit is uniform.  A tile without a counted pixel returns before it reads its range.
+// So the two barriers suffice and there is no third.  A tile without a counted pixel returns before it reads its range.
 //
 // Channel groups.  G = kLiftGroup = 16 channels per launch, one launch per group on the same stream, each walking the lists
 // again; the first launch (or the channel-less instantiation <0> when channels == 0) also adds out_weight.  The last group may
@@ -73,17 +66,17 @@ namespace gs {
 // FULL = false, which tests every row access against `gc`, the channels that exist: nothing past a pixel's row is read (a
 // channel that does not exist lifts 0 into a slot nobody flushes), nothing past a Gaussian's row is written.  The resource report
 // (-Rpass-analysis=kernel-resource-usage):
-//     k_lift<0, true>              47 VGPRs, 59 SGPRs, no spills, no scratch, occupancy 8 waves per SIMD,  4 872 bytes of LDS
-//     k_lift<4, true>, <4, false>  56 VGPRs, 62 / 64,  no spills, no scratch, occupancy 8,                 6 920 bytes of LDS
-//     k_lift<16, true>, <16, false>  95 VGPRs, 60 / 62, no spills, no scratch, occupancy 5,               13 064 bytes of LDS
-// The walk's own state is k_contrib's 47 registers, the group's values add G, and the binary64 working set of lift_reduce the
+//     k_lift<0, true>              45 VGPRs, 58 SGPRs, no spills, no scratch, occupancy 8 waves per SIMD,  4 872 bytes of LDS
+//     k_lift<4, true>, <4, false>  53 VGPRs, 60 / 62,  no spills, no scratch, occupancy 8,                 6 920 bytes of LDS
+//     k_lift<16, true>, <16, false>  92 VGPRs, 58 / 60, no spills, no scratch, occupancy 5,               13 064 bytes of LDS
+// The walk's own state is about 45 registers, the group's values add G, and the binary64 working set of lift_reduce the
 // rest: after step A eight doubles are live beside the terms being formed.  (The float-to-double conversions are pinned inside
 // the walk: hoisted, sixteen more registers would be held through it.)  Five waves per SIMD for the kernel of sixteen is the
 // price of reducing sixteen channels at once -- what runs between two barriers is dependent VALU arithmetic on registers, with the
-// sixteen channels' independent chains for the scheduler to interleave -- and it buys 1.42 ms for 16 channels at S(1e6),
+// sixteen channels' independent chains for the scheduler to interleave -- and it buys 1.33 ms for 16 channels at S(1e6),
 // 1920 x 1080 (tools/pixel_lift_rate.py) where the removed per-channel form, at 78 registers and six waves, took 4.88 ms
 // (historical, as above: a measurement of code that is no longer here).  G = 8 would
-// return to more waves and walk the lists twice as often; the walk alone (<0>) is 0.66 ms.  The LDS allows twelve workgroups
+// return to more waves and walk the lists twice as often; the walk alone (<0>) is 0.57 ms.  The LDS allows twelve workgroups
 // per CU, more than the registers do.
 // ---------------------------------------------------------------------------------------
 template <int CTRL>
@@ -161,24 +154,16 @@ __global__ __launch_bounds__(BLOCK) void k_lift(const uint2* __restrict__ ranges
                                                 const float* __restrict__ values, uint32_t channels, uint32_t c0, uint32_t gc,
                                                 double* __restrict__ out, double* __restrict__ out_weight) {
     static_assert(G == 0 || (WAVE % G == 0 && (WAVE * G) % BLOCK == 0), "an entry's G slots are flushed by lanes of one wave");
-    __shared__ float4 s_rec[3][WAVE];  // the chunk's {c00 c01 c11 o} {u v r g} {b cut r11 r00}, plane-major
+    __shared__ float4 s_rec[3][WAVE];  // the chunk's records (gs_tile_walk.h)
     __shared__ uint32_t s_gid[2][WAVE], s_cnt[WAVE];
     __shared__ double s_w[WAVE], s_acc[WAVE][G > 0 ? G : 1];
     __shared__ uint2 s_exptab[32];
     __shared__ uint32_t s_done;        // waves of the tile with no counted pixel left
 
-    const int tid = threadIdx.x, lane = tid & (WAVE - 1), w = tid / WAVE;
-    const uint32_t tile = tile_order[blockIdx.x];
-    const uint32_t tile_x = tile % tiles_x, tile_y = tile / tiles_x;
-    const uint32_t qx0 = tile_x * kTile + (w & 1) * 8, qy0 = tile_y * kTile + (w >> 1) * 8;
-    const uint32_t px = qx0 + (lane & 7), py = qy0 + (lane >> 3);
-    const bool inside = px < width && py < height;  // render.comp:36-39
-    const size_t p = (size_t)py * width + px;
-    const bool counted = inside && (mask == nullptr || mask[p] != 0);
-    if (tid < 32) {
-        const uint64_t v = kExpfTab[tid];
-        s_exptab[tid] = make_uint2((uint32_t)v, (uint32_t)(v >> 32));
-    }
+    const WalkPixel q = walk_pixel(tile_order, width, height, tiles_x);
+    const int tid = threadIdx.x, lane = q.lane, w = q.w;
+    const bool counted = q.inside && (mask == nullptr || mask[q.p] != 0);
+    walk_init_shared(s_exptab, &s_done);
     if (tid < WAVE) {
         s_cnt[tid] = 0;
         s_w[tid] = 0.0;
@@ -187,7 +172,6 @@ __global__ __launch_bounds__(BLOCK) void k_lift(const uint2* __restrict__ ranges
 #pragma unroll
         for (int j = 0; j < (WAVE * G) / BLOCK; ++j) (&s_acc[0][0])[j * BLOCK + tid] = 0.0;
     }
-    if (tid == 0) s_done = 0;
     if (__syncthreads_or(counted) == 0) return;  // (also publishes the table, the zeroed slots and s_done)
     float v[G > 0 ? G : 1];  // this pixel's channels of the group in lift_channel's order: read only where the pixel is counted
     uint32_t c_mine = 0;     // the channel of the group whose row sum this lane holds after lift_reduce
@@ -196,7 +180,7 @@ __global__ __launch_bounds__(BLOCK) void k_lift(const uint2* __restrict__ ranges
 #pragma unroll
         for (int j = 0; j < G; ++j) v[j] = 0.0f;
         if (counted) {
-            const float* __restrict__ row = values + p * channels + c0;
+            const float* __restrict__ row = values + q.p * channels + c0;
 #pragma unroll
             for (int j = 0; j < G; ++j) {
                 const uint32_t c = lift_channel<G>(j, lane);
@@ -204,88 +188,33 @@ __global__ __launch_bounds__(BLOCK) void k_lift(const uint2* __restrict__ ranges
             }
         }
     }
-    const float fx = (float)px, fy = (float)py;
-    const float rx0 = (float)qx0, ry0 = (float)qy0, rx1 = (float)qx0 + 7.0f, ry1 = (float)qy0 + 7.0f;
-    const uint2 range = ranges[tile];
-    uint64_t alive = __builtin_amdgcn_ballot_w64(counted);  // counted pixels that have not broken
-    if (alive == 0 && lane == 0) atomicAdd(&s_done, 1u);
+    uint64_t alive = walk_begin(counted, lane, &s_done);  // counted pixels that have not broken
     float T = 1.0f;
 
-    // software pipeline, as the blend's: ids two chunks ahead, this thread's third of a record one chunk ahead, both in registers
-    uint32_t g_nxt = 0, g_next = 0;
-    float4 r_nxt = make_float4(0, 0, 0, 0);
-    {
-        const uint32_t i0 = range.x + (uint32_t)lane;
-        if (i0 < range.y) {
-            g_nxt = sorted_gid[i0];
-            if (w < 3) r_nxt = reinterpret_cast<const float4*>(rec + g_nxt)[w];
-        }
-        const uint32_t i1 = i0 + WAVE;
-        if (i1 < range.y) g_next = sorted_gid[i1];
-    }
+    ListPipeline<false> pipe{sorted_gid, rec, ranges[q.tile], lane, w};
+    pipe.prime();
+    const uint2 range = pipe.range;
     int par = 0;  // the chunk's parity: which half of s_gid holds its ids
     for (uint32_t base = range.x; base < range.y; base += WAVE, par ^= 1) {
         const uint32_t n_here = range.y - base < (uint32_t)WAVE ? range.y - base : (uint32_t)WAVE;
-        if (w < 3) s_rec[w][lane] = r_nxt;
-        else s_gid[par][lane] = g_nxt;
-        {
-            const uint32_t i1 = base + WAVE + (uint32_t)lane;
-            g_nxt = g_next;
-            if (i1 < range.y && w < 3) r_nxt = reinterpret_cast<const float4*>(rec + g_nxt)[w];
-            const uint32_t i2 = i1 + WAVE;
-            if (i2 < range.y) g_next = sorted_gid[i2];
-        }
+        if (w < 3) s_rec[w][lane] = pipe.r_nxt;
+        else s_gid[par][lane] = pipe.g_nxt;
+        pipe.advance(base);
         __syncthreads();  // the chunk is staged, its slots are zero
-        if (alive != 0) {
-            // entry `lane` of the chunk against this wave's quadrant: the blend's test (gs_blend.hip, blend_walk), the same slack.
-            // An entry it drops is skipped by every pixel of the quadrant (power < cut there), so dropping it changes no bit.
-            const float4 co = s_rec[0][lane], uv = s_rec[1][lane], bc = s_rec[2][lane];
-            const float cut = bc.y;
-            const float h00 = 0.5f * co.x, h11 = 0.5f * co.z;
-            uint64_t bm = __builtin_amdgcn_ballot_w64((uint32_t)lane < n_here) & __builtin_amdgcn_ballot_w64(cut <= 0.0f);
-            {
-                const float mq = min_q_rect(h00, co.y, h11, bc.z, bc.w, uv.x, uv.y, rx0, rx1, ry0, ry1);
-                const float ax = fmaxf(fabsf(uv.x - rx0), fabsf(uv.x - rx1));
-                const float ay = fmaxf(fabsf(uv.y - ry0), fabsf(uv.y - ry1));
-                const float mag = __builtin_fmaf(fabsf(h00) * ax, ax, __builtin_fmaf(fabsf(h11) * ay, ay, fabsf(co.y) * ax * ay));
-                bm &= __builtin_amdgcn_ballot_w64(!(mq > __builtin_fmaf(mag, 9.6e-7f, -cut)));  // NaN -> keep
-            }
-            while (bm) {
-                const int k = __ffsll((unsigned long long)bm) - 1;
-                bm &= bm - 1;
-                const float4 e0 = s_rec[0][k], e1 = s_rec[1][k];
-                const float ecut = s_rec[2][k].y;
-                const float dx = e1.x - fx, dy = e1.y - fy;
-                // :66  -0.5 * (c00 dx dx + c11 dy dy) - c01 dx dy, every product and sum rounded (the scaling by -0.5 is exact)
-                const float cx = -0.5f * e0.x, cy = -e0.y, cz = -0.5f * e0.z;
-                const float s = cx * dx * dx + cz * dy * dy;
-                const float power = s + cy * dx * dy;
-                // :68 and :78 (a NaN power skips the entry; power >= cut  <=>  alpha >= 1/255 with the reference's exp)
-                const uint64_t m2 = alive & __builtin_amdgcn_ballot_w64(power <= 0.0f) & __builtin_amdgcn_ballot_w64(!(power < ecut));
-                if (m2 == 0) continue;
-                const float alpha = fminf(0.99f, e0.w * gs_expf_libm(power, s_exptab));  // :77
-                const float test_T = T * (1 - alpha);
-                const uint64_t mk = m2 & __builtin_amdgcn_ballot_w64(test_T < 0.0001f);  // :82-85 break
-                const uint64_t bl = m2 & ~mk;                                            // lanes that reach :87
-                if (bl != 0) {
-                    const bool upd = __builtin_amdgcn_inverse_ballot_w64(bl);
-                    const double wd = upd ? (double)(alpha * T) : 0.0;  // w = fl(alpha T), exactly; selected
-                    if (upd) T = test_T;                                // :88
-                    if (out_weight) {
-                        const double sum = wave_sum_f64(wd);
-                        if (lane == 0) atomicAdd(&s_w[k], sum);
-                    }
-                    if constexpr (G > 0) {
-                        const double sum = lift_reduce<G>(v, wd, upd);  // channel c_mine over this lane's row of 16
-                        if (G == 16 || (lane & 12) == 0) atomicAdd(&s_acc[k][c_mine], sum);  // (G = 4: a row's quads hold the same sums)
-                    }
-                    if (lane == 0) atomicAdd(&s_cnt[k], (uint32_t)__popcll(bl));
-                }
-                alive &= ~mk;
-                if (alive == 0) break;
-            }
-            if (alive == 0 && lane == 0) atomicAdd(&s_done, 1u);
-        }
+        walk_chunk(s_rec, s_exptab, &s_done, q, n_here, alive, T,
+                   [&](int k, uint64_t bl, bool upd, float alpha, float test_T, float& T) {
+                       const double wd = upd ? (double)(alpha * T) : 0.0;  // w = fl(alpha T), exactly; selected
+                       if (upd) T = test_T;                                // :88
+                       if (out_weight) {
+                           const double sum = wave_sum_f64(wd);
+                           if (lane == 0) atomicAdd(&s_w[k], sum);
+                       }
+                       if constexpr (G > 0) {
+                           const double sum = lift_reduce<G>(v, wd, upd);  // channel c_mine over this lane's row of 16
+                           if (G == 16 || (lane & 12) == 0) atomicAdd(&s_acc[k][c_mine], sum);  // (G = 4: a row's quads hold the same sums)
+                       }
+                       if (lane == 0) atomicAdd(&s_cnt[k], (uint32_t)__popcll(bl));
+                   });
         __syncthreads();  // the four waves' partials have met in the slots
         if constexpr (G > 0) {
 #pragma unroll
@@ -309,7 +238,7 @@ __global__ __launch_bounds__(BLOCK) void k_lift(const uint2* __restrict__ ranges
                 s_cnt[tid] = 0;
             }
         }
-        if (s_done == BLOCK / WAVE) break;  // (uniform: nobody writes s_done between this barrier and the next)
+        if (s_done == BLOCK / WAVE) break;  // (uniform: gs_tile_walk.h, Barriers)
     }
 }
 

@@ -415,7 +415,7 @@ __device__ __forceinline__ void preprocess_one(const SceneView& sv, const gs_uni
     if (vis) {
         stage[0 * kPrePlane + lane] = make_float4(c00, c01, c11, opacity);
         stage[1 * kPrePlane + lane] = make_float4(uvx, uvy, rgb[0], rgb[1]);
-        // the blend's entry-only terms (gs_blend.hip, min_q_rect: the minimiser of q along an edge is r * the fixed coordinate), with
+        // the blend's entry-only terms (gs_tile_walk.h, min_q_rect: the minimiser of q along an edge is r * the fixed coordinate), with
         // the very operations the blend used to spend on them per (wave, entry): v_rcp_f32, then the product with -c01
         const float r11 = -c01 * __builtin_amdgcn_rcpf(c11), r00 = -c01 * __builtin_amdgcn_rcpf(c00);
         stage[2 * kPrePlane + lane] = make_float4(rgb[2], acut, r11, r00);

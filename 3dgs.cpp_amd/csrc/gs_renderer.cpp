@@ -788,6 +788,22 @@ struct gs_renderer {
     void drain() {
         while (pending > 0) retire_oldest();
     }
+
+    // What the passes over the last frame's tile lists do after their own argument checks (gs_accumulate_contributions,
+    // gs_blend_features, gs_lift_pixels), in this order: queued frames retire (an overflowed one is re-run: the lists are the last
+    // frame's, complete); without a frame the call is refused; with nothing asked for it is done; otherwise launch(fb) enqueues
+    // the pass on the last frame's stream and the call waits for it.
+    template <class Launch>
+    void over_last_frame(bool nothing_asked, Launch&& launch) {
+        drain();
+        if (!has_last_frame()) throw Error(GS_ERR_INVALID, "no frame rendered yet");
+        if (nothing_asked) return;
+        HIP_CHECK(hipSetDevice(scene->device));
+        const FrameBuffers& fb = *last_set;
+        launch(fb);
+        HIP_CHECK(hipGetLastError());
+        fb.sync();
+    }
 };
 
 // ------------------------------------------------------------------------------------------
@@ -1137,15 +1153,10 @@ int gs_accumulate_contributions(gs_renderer* r, const gs_contributions* c) {
         if (reinterpret_cast<uintptr_t>(c->weight) % 8 != 0) throw Error(GS_ERR_INVALID, "weight must be 8-byte aligned");
         if (reinterpret_cast<uintptr_t>(c->pixels) % 4 != 0) throw Error(GS_ERR_INVALID, "pixels must be 4-byte aligned");
         if (reinterpret_cast<uintptr_t>(c->top_id) % 4 != 0) throw Error(GS_ERR_INVALID, "top_id must be 4-byte aligned");
-        r->drain();  // queued frames retire; an overflowed one is re-run: the lists below are the last frame's, complete
-        if (!r->has_last_frame()) throw Error(GS_ERR_INVALID, "no frame rendered yet");
-        if (!c->weight && !c->pixels && !c->top_id) return;
-        HIP_CHECK(hipSetDevice(r->scene->device));
-        const FrameBuffers& fb = *r->last_set;
-        gs::launch_contributions(fb.ranges.p, fb.sorted.p, r->tile_order.p, fb.rec.p, r->last_width, r->last_height, c->mask, c->weight,
-                                 c->pixels, c->top_id, fb.stream);
-        HIP_CHECK(hipGetLastError());
-        fb.sync();
+        r->over_last_frame(!c->weight && !c->pixels && !c->top_id, [&](const FrameBuffers& fb) {
+            gs::launch_contributions(fb.ranges.p, fb.sorted.p, r->tile_order.p, fb.rec.p, r->last_width, r->last_height, c->mask,
+                                     c->weight, c->pixels, c->top_id, fb.stream);
+        });
     });
 }
 
@@ -1162,16 +1173,11 @@ int gs_blend_features(gs_renderer* r, const gs_feature_maps* m) {
             {m->out_depth_median, "out_depth_median must be 4-byte aligned"}};
         for (const auto& q : ptrs)
             if (reinterpret_cast<uintptr_t>(q.p) % 4 != 0) throw Error(GS_ERR_INVALID, q.what);
-        r->drain();  // queued frames retire; an overflowed one is re-run: the lists below are the last frame's, complete
-        if (!r->has_last_frame()) throw Error(GS_ERR_INVALID, "no frame rendered yet");
         float* out_features = m->channels > 0 ? m->out_features : nullptr;  // channels == 0: that output is not touched
-        if (!out_features && !m->out_alpha && !m->out_depth && !m->out_depth_median) return;
-        HIP_CHECK(hipSetDevice(r->scene->device));
-        const FrameBuffers& fb = *r->last_set;
-        gs::launch_features(fb.ranges.p, fb.sorted.p, r->tile_order.p, fb.rec.p, r->last_width, r->last_height, m->features, m->channels,
-                            out_features, m->out_alpha, m->out_depth, m->out_depth_median, fb.stream);
-        HIP_CHECK(hipGetLastError());
-        fb.sync();
+        r->over_last_frame(!out_features && !m->out_alpha && !m->out_depth && !m->out_depth_median, [&](const FrameBuffers& fb) {
+            gs::launch_features(fb.ranges.p, fb.sorted.p, r->tile_order.p, fb.rec.p, r->last_width, r->last_height, m->features,
+                                m->channels, out_features, m->out_alpha, m->out_depth, m->out_depth_median, fb.stream);
+        });
     });
 }
 
@@ -1185,16 +1191,11 @@ int gs_lift_pixels(gs_renderer* r, const gs_pixel_lift* l) {
         if (reinterpret_cast<uintptr_t>(l->values) % 4 != 0) throw Error(GS_ERR_INVALID, "values must be 4-byte aligned");
         if (reinterpret_cast<uintptr_t>(l->out) % 8 != 0) throw Error(GS_ERR_INVALID, "out must be 8-byte aligned");
         if (reinterpret_cast<uintptr_t>(l->out_weight) % 8 != 0) throw Error(GS_ERR_INVALID, "out_weight must be 8-byte aligned");
-        r->drain();  // queued frames retire; an overflowed one is re-run: the lists below are the last frame's, complete
-        if (!r->has_last_frame()) throw Error(GS_ERR_INVALID, "no frame rendered yet");
         double* out = l->channels > 0 ? l->out : nullptr;  // channels == 0: that output is not touched
-        if (!out && !l->out_weight) return;
-        HIP_CHECK(hipSetDevice(r->scene->device));
-        const FrameBuffers& fb = *r->last_set;
-        gs::launch_lift(fb.ranges.p, fb.sorted.p, r->tile_order.p, fb.rec.p, r->last_width, r->last_height, l->mask, l->values,
-                        l->channels, out, l->out_weight, fb.stream);
-        HIP_CHECK(hipGetLastError());
-        fb.sync();
+        r->over_last_frame(!out && !l->out_weight, [&](const FrameBuffers& fb) {
+            gs::launch_lift(fb.ranges.p, fb.sorted.p, r->tile_order.p, fb.rec.p, r->last_width, r->last_height, l->mask, l->values,
+                            l->channels, out, l->out_weight, fb.stream);
+        });
     });
 }
 
