@@ -23,7 +23,7 @@ BLOB_PLANES = 59
 
 
 # the device code of libgs3d_hip.so: one translation unit per stage + the shared device headers
-KERNEL_SOURCES = ("gs_device.h", "gs_bin.h", "gs_scene.hip", "gs_preprocess.hip", "gs_radix.hip", "gs_bin_l1.hip", "gs_bin_l2.hip",
+KERNEL_SOURCES = ("gs_device.h", "gs_bin.h", "gs_tile_cull.h", "gs_scene.hip", "gs_preprocess.hip", "gs_radix.hip", "gs_bin_l1.hip", "gs_bin_l2.hip",
                   "gs_blend.hip", "gs_contrib.hip", "gs_features.hip", "gs_lift.hip", "gs_kernels.h")
 
 
@@ -49,7 +49,8 @@ def library_source_hash():
 STAGES = dict(tiles=(0, np.uint32), depth=(1, np.float32), radius=(2, np.float32), aabb=(3, np.uint16),
               conic_opacity=(4, np.float32), uv_rg=(5, np.float32), b=(6, np.float32),
               depth_order=(7, np.uint32), alpha_cut=(8, np.float32), sorted_tile=(11, np.uint32), sorted_gid=(12, np.uint32),
-              ranges=(13, np.uint32), lists_raw=(14, np.uint32), ranges_raw=(15, np.uint32))
+              ranges=(13, np.uint32), lists_raw=(14, np.uint32), ranges_raw=(15, np.uint32),
+              lists_culled=(16, np.uint32), ranges_culled=(17, np.uint32))
 
 # every symbol include/gs3d_hip.h declares
 SYMBOLS = ["gs_last_error", "gs_device_count", "gs_read_ply", "gs_activate_records", "gs_scene_load_ply", "gs_scene_from_records",
@@ -60,7 +61,7 @@ SYMBOLS = ["gs_last_error", "gs_device_count", "gs_read_ply", "gs_activate_recor
            "gs_scene_download_vertices", "gs_scene_download_cov3d",
            "gs_deactivate_vertices", "gs_write_ply", "gs_scene_to_device_arrays", "gs_scene_download_records", "gs_scene_save_ply",
            "gs_scene_destroy", "gs_renderer_create", "gs_renderer_destroy", "gs_camera_uniforms",
-           "gs_render", "gs_render_host", "gs_synchronize", "gs_set_timing", "gs_set_frames_in_flight", "gs_set_sort_path", "gs_set_exp_mode", "gs_set_graph_mode", "gs_set_blend_lockstep", "gs_get_blend_lockstep", "gs_set_level1_fused", "gs_get_level1_fused", "gs_set_blend_contraction", "gs_set_antialiased", "gs_get_antialiased", "gs_get_timing_totals",
+           "gs_render", "gs_render_host", "gs_synchronize", "gs_set_timing", "gs_set_frames_in_flight", "gs_set_sort_path", "gs_set_exp_mode", "gs_set_graph_mode", "gs_set_blend_lockstep", "gs_get_blend_lockstep", "gs_set_level1_fused", "gs_get_level1_fused", "gs_set_tile_cull", "gs_get_tile_cull", "gs_get_listed_instances", "gs_set_blend_contraction", "gs_set_antialiased", "gs_get_antialiased", "gs_get_timing_totals",
            "gs_get_frame_intervals", "gs_get_stats", "gs_poll_stats", "gs_debug_download", "gs_accumulate_contributions", "gs_blend_features", "gs_lift_pixels", "gs_debug_expf_scan", "gs_debug_alpha_cut_scan", "gs_renderer_stream",
            "gs_dist_unique_id", "gs_dist_create", "gs_dist_rank", "gs_dist_world", "gs_dist_pose_count",
            "gs_dist_broadcast_scene", "gs_dist_broadcast_scene_ex", "gs_dist_verify", "gs_dist_destroy"]
@@ -753,6 +754,24 @@ class Renderer:
             _check(now)
         return bool(now)
 
+    def set_tile_cull(self, on):
+        """The alpha-cut tile cull (gs_set_tile_cull; GS_TILE_CULL at creation, default on)."""
+        _check(lib().gs_set_tile_cull(self._h, C.c_int(1 if on else 0)))
+
+    def tile_cull(self):
+        """(the switch, whether the most recently enqueued frame's lists are culled) (gs_get_tile_cull)."""
+        culled = C.c_int(0)
+        now = lib().gs_get_tile_cull(self._h, C.byref(culled))
+        if now < 0:
+            _check(now)
+        return bool(now), bool(culled.value)
+
+    def listed_instances(self):
+        """Tile instances in the last frame's lists as the blend walked them (gs_get_listed_instances)."""
+        out = C.c_uint64(0)
+        _check(lib().gs_get_listed_instances(self._h, C.byref(out)))
+        return int(out.value)
+
     def set_sort_path(self, mode):
         """0 automatic, 1 global depth order, 2 bin-local (gs_set_sort_path)."""
         _check(lib().gs_set_sort_path(self._h, C.c_int(int(mode))))
@@ -790,7 +809,9 @@ class Renderer:
         n, v, d = st.num_gaussians, st.num_visible, min(st.num_instances, st.instance_capacity)
         count = {"tiles": n, "depth": n, "radius": n, "aabb": 4 * n, "conic_opacity": 4 * n, "uv_rg": 4 * n,
                  "b": n, "alpha_cut": n, "depth_order": v, "sorted_tile": d, "sorted_gid": d, "lists_raw": d}.get(name)
-        if name in ("ranges", "ranges_raw"):
+        if name == "lists_culled":
+            count = min(self.listed_instances(), st.instance_capacity)
+        if name in ("ranges", "ranges_raw", "ranges_culled"):
             w, h = int(uniforms["width"][0]), int(uniforms["height"][0])
             count = 2 * ((w + 15) // 16) * ((h + 15) // 16)
         out = np.zeros(max(int(count), 1), dt)

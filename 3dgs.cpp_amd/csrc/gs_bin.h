@@ -230,7 +230,7 @@ __device__ __forceinline__ uint32_t l1_block() {
 // What lands in the list is a 12-byte RECORD per candidate -- {depth bits, Gaussian id, tile box clipped to the bin} --
 // everything level 2 needs, so that k_bin_fast STREAMS its bin's candidates with one coalesced read instead of gathering
 // depth[id] (a 64-byte line per 4-byte value) and, after the sort, aabb[id] again (round 2: 2.3x the algorithmic bytes).
-constexpr int kCandWords = 3;  // {key, id, box16}
+constexpr int kCandWords = 3;  // {key, id, two box16: bin_box_pair}
 // a tile box clipped to a bin of S <= 8 tiles, bin-local, inclusive upper bounds, 4 bits each: x0 | y0 << 4 | x1 << 8 | y1 << 12
 __device__ __forceinline__ uint32_t bin_local_box16(const BinGrid& g, uint32_t bin, ushort4 box) {
     const int S = 1 << g.bin_shift;
@@ -238,6 +238,22 @@ __device__ __forceinline__ uint32_t bin_local_box16(const BinGrid& g, uint32_t b
     const int lx0 = max((int)box.x, ox) - ox, ly0 = max((int)box.y, oy) - oy;
     const int lx1 = min((int)box.z, ox + S) - ox - 1, ly1 = min((int)box.w, oy + S) - oy - 1;
     return (uint32_t)lx0 | ((uint32_t)ly0 << 4) | ((uint32_t)lx1 << 8) | ((uint32_t)ly1 << 12);
+}
+// A candidate record's third word: TWO such boxes.  Low half: the reference tile box clipped to the bin (what the reference's lists
+// hold: D, the overflow of the list capacity and the reference taps are made from it).  High half: the alpha-cut box (gs_tile_cull.h,
+// a subset of the reference box) clipped to the bin -- what the lists the blend walks are made from -- or kBoxNone where it misses
+// the bin.  A producer that has no tight box writes the reference box into both halves: the cull is then inert.
+// kBoxNone covers nothing under both readers: cover16 (x0 = x1 = 15: no column of a 4-wide bin) and cover_masks<1>(3, ...)
+// (rows 15 .. 15 of an 8-row bin); an ordinary box never has a coordinate beyond 7.
+constexpr uint32_t kBoxNone = 0xFFFFu;
+__device__ __forceinline__ uint32_t bin_box_pair(const BinGrid& g, uint32_t bin, ushort4 box, ushort4 tight) {
+    const int S = 1 << g.bin_shift;
+    const int ox = (int)(bin & ((1u << g.grid_shift) - 1u)) << g.bin_shift, oy = (int)(bin >> g.grid_shift) << g.bin_shift;
+    const bool hit = max((int)tight.x, ox) < min((int)tight.z, ox + S) && max((int)tight.y, oy) < min((int)tight.w, oy + S);
+    return bin_local_box16(g, bin, box) | ((hit ? bin_local_box16(g, bin, tight) : kBoxNone) << 16);
+}
+__device__ __forceinline__ uint32_t box16_tiles(uint32_t b) {  // tiles a (non-empty) bin-local box covers
+    return (((b >> 8) & 15u) - (b & 15u) + 1u) * (((b >> 12) & 15u) - ((b >> 4) & 15u) + 1u);
 }
 
 }  // namespace gs

@@ -313,7 +313,8 @@ __global__ __launch_bounds__(BLOCK) void k_l1_scatter_any_order(L1Args a) {
             uint32_t* const rec = a.cand + (size_t)kCandWords * pos;  // three adjacent dwords: one 12-byte store
             rec[0] = k;
             rec[1] = gid;
-            rec[2] = bin_local_box16(a.g, bin, box);
+            const uint32_t b16 = bin_local_box16(a.g, bin, box);
+            rec[2] = b16 | (b16 << 16);  // no alpha-cut box on this path: the reference box in both halves (gs_bin.h: bin_box_pair)
         }
     };
 #pragma unroll

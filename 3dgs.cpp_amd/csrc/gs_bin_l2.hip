@@ -49,6 +49,13 @@ struct BuildArgs {
     uint64_t* stamps;      // nullable: the frame's timeline (the level's first kernel stamps ST_L2)
     const uint32_t* l1_words;  // non-null: level 1 ran inside k_preprocess (gs_kernels.h: L1Fused), and l1_cap is a bin region's size
     uint32_t l1_cap;
+    // One pass: the frame's last kernel zeroes the cursors, so every bin workgroup leaves its bin's count and offset here, in the
+    // three-kernel form (bin_count's layout): a later run of level 2 over the same records -- the reference list taps of a culled
+    // frame (gs_renderer.cpp) -- reads them as k_l1_scan's.  Null otherwise.
+    uint32_t* bin_count_save;
+    // k_bin_fast: nonzero -- the lists are made from the records' REFERENCE boxes (the low half of the third word: gs_bin.h,
+    // bin_box_pair); zero -- from the alpha-cut boxes (the high half), while D and the capacity check still follow the reference's.
+    uint32_t reference_boxes;
 };
 
 // A bin's run of candidates in either form of level 1.  Three kernels: count and offset from k_l1_scan and the scatter's block 0.
@@ -473,7 +480,7 @@ __device__ __forceinline__ void bin_fast_body(const BuildArgs& a) {
     uint32_t* const t_cnt = smem + 2 * MAXC;                                                     // [64]
     uint32_t* const t_cur = t_cnt + 64;                                                          // [64]
     uint32_t (*const s_seg)[64] = reinterpret_cast<uint32_t(*)[64]>(t_cnt + 128);                // [16][64]
-    __shared__ uint32_t scratch[NW], scratch_hi[NW];
+    __shared__ uint32_t scratch[NW], scratch_hi[NW], scratch_sum[MODE == 0 ? NW : 1];
     __shared__ uint32_t s_seg0, s_flag;
     constexpr int kSlotBits = SLABS ? 16 : 14;  // a candidate's slot in the bin's record run: < MAXC <= 16384, or < 65536
     constexpr uint32_t kSlotMask = (1u << kSlotBits) - 1u;
@@ -508,6 +515,10 @@ __device__ __forceinline__ void bin_fast_body(const BuildArgs& a) {
             if (tid == 0) atomicOr(&a.counters->overflow, 2u);
             c_total = 0;
         }
+        if (a.bin_count_save && tid == 0) {  // (what this run went by: a bin it skipped is skipped again)
+            a.bin_count_save[bin] = c_total;
+            a.bin_count_save[kBinOffsets + bin] = off;
+        }
     };
     if constexpr (MODE == 0 || MODE == 1) bin_extent();
     if (tid == 0) s_flag = 0;
@@ -516,7 +527,7 @@ __device__ __forceinline__ void bin_fast_body(const BuildArgs& a) {
     // c: the candidates in LDS (the whole bin, or the current slab of it); rounds / wbase follow it
     uint32_t c = multi ? 0u : c_total;
     int rounds = (int)((c + THREADS - 1) / THREADS);  // block-uniform, <= ROUNDS
-    // this bin's run of 12-byte records {key, id, box16} as a raw buffer: 32-bit offsets (one address register per load instead
+    // this bin's run of 12-byte records {key, id, box pair} as a raw buffer: 32-bit offsets (one address register per load instead
     // of two) and the hardware's bounds check in place of branches (reads past the run return 0)
     typedef uint32_t u32x3 __attribute__((ext_vector_type(3)));
 #define recs uniform_rsrc(a.cand + (size_t)kCandWords * off, c_total * 12u)  /* rebuilt from scalars at every use: see uniform_rsrc */
@@ -615,25 +626,34 @@ __device__ __forceinline__ void bin_fast_body(const BuildArgs& a) {
         __syncthreads();
     };
     // smallest key and the span of the keys in LDS (block-uniform, scalar)
+    // MODE 0: the same two barriers also add up `ref_mine`, every thread's count of REFERENCE tile instances (the records' low
+    // boxes), into ref_inst: the bin's share of D, which place_lists advances the reference cursor by
+    uint32_t ref_mine = 0, ref_inst = 0;
     auto block_minmax = [&](uint32_t lo, uint32_t hi, uint32_t& kmin, uint32_t& span) {
+        uint32_t sum = ref_mine;
 #pragma unroll
         for (int d = 1; d < WAVE; d <<= 1) {
             lo = min(lo, (uint32_t)__shfl_xor((int)lo, d, WAVE));
             hi = max(hi, (uint32_t)__shfl_xor((int)hi, d, WAVE));
+            if constexpr (MODE == 0) sum += (uint32_t)__shfl_xor((int)sum, d, WAVE);
         }
         __syncthreads();  // scratch reuse; also: the LDS writes of the load are visible
         if (lane == 0) {
             scratch[w] = lo;
             scratch_hi[w] = hi;
+            if constexpr (MODE == 0) scratch_sum[w] = sum;
         }
         __syncthreads();
+        sum = 0;
 #pragma unroll
         for (int k = 0; k < NW; ++k) {
             lo = min(lo, scratch[k]);
             hi = max(hi, scratch_hi[k]);
+            if constexpr (MODE == 0) sum += scratch_sum[k];
         }
         kmin = (uint32_t)__builtin_amdgcn_readfirstlane((int)lo);
         span = (uint32_t)__builtin_amdgcn_readfirstlane((int)hi) - kmin;
+        if constexpr (MODE == 0) ref_inst = (uint32_t)__builtin_amdgcn_readfirstlane((int)sum);
     };
     auto key_range = [&](uint32_t& kmin, uint32_t& span) {
         uint32_t lo = 0xFFFFFFFFu, hi = 0u;
@@ -764,9 +784,17 @@ __device__ __forceinline__ void bin_fast_body(const BuildArgs& a) {
         uint32_t d_bin;
         const uint32_t excl = block_excl_scan<THREADS>(v, scratch, &d_bin);
         if (tid == 0) {
-            const uint32_t seg = d_bin ? atomicAdd(&a.counters->instances, d_bin) : 0u;
+            // Two cursors.  `listed`: where this bin's lists go -- the instances actually listed (fewer than the reference's where
+            // the alpha-cut boxes made them).  `instances`: the REFERENCE's count D, advanced by the reference boxes' instances, and the
+            // one the capacity is checked against: capacity growth, re-runs and the statistics do not depend on the cull.  Over the
+            // bins that have reserved, listed <= instances (every bin adds no more to the first than to the second -- in whatever
+            // order the two adds of different bins interleave, a bin's segment ends at most at the listed total of the frame, which
+            // is at most D): a frame that does not raise the overflow bit keeps every store inside the capacity.
+            const uint32_t d_ref = MODE == 0 ? ref_inst : d_bin;
+            const uint32_t seg = d_bin ? atomicAdd(&a.counters->listed, d_bin) : 0u;
+            const uint32_t ref_seg = d_ref ? atomicAdd(&a.counters->instances, d_ref) : 0u;
             s_seg0 = seg;
-            if ((uint64_t)seg + d_bin > a.capacity) atomicOr(&a.counters->overflow, 1u);
+            if ((uint64_t)ref_seg + d_ref > a.capacity) atomicOr(&a.counters->overflow, 1u);
         }
         __syncthreads();
         if (tid < 64) {
@@ -1013,6 +1041,10 @@ __device__ __forceinline__ void bin_fast_body(const BuildArgs& a) {
         asm volatile("" : "+v"(tid12));  // opaque: or the sixteen offsets are hoisted out of the attempt loop, kept, and spilled
         constexpr int HR = ROUNDS <= 8 ? ROUNDS : ROUNDS / 2;  // 4, 8, 6, 8
         const int h_end = multi ? 0 : ROUNDS;  // (a slab's members are in LDS already)
+        // MODE 0: which half of the record's box pair the lists are made from (block-uniform: a scalar shift); the slab modes' 16
+        // slot bits leave the payload the low half, the reference box: they do not cull
+        const uint32_t box_shift = (MODE == 0 && !a.reference_boxes) ? 16u : 0u;
+        ref_mine = 0;
 #pragma unroll
         for (int h = 0; h < h_end; h += HR) {
             uint32_t k[HR], b[HR];
@@ -1031,7 +1063,12 @@ __device__ __forceinline__ void bin_fast_body(const BuildArgs& a) {
                 const uint32_t e = (h + r) * THREADS + tid;
                 if (h + r < rounds && e < c) {
                     s_key[e] = k[r];
-                    s_pay[e] = e | (b[r] << kSlotBits);
+                    if constexpr (MODE == 0) {
+                        s_pay[e] = e | (((b[r] >> box_shift) & 0xFFFFu) << kSlotBits);
+                        ref_mine += box16_tiles(b[r]);
+                    } else {
+                        s_pay[e] = e | (b[r] << kSlotBits);
+                    }
                 }
             }
         }
@@ -1114,7 +1151,8 @@ __device__ __forceinline__ void bin_fast_body(const BuildArgs& a) {
                 const uint32_t pw = s_pay[e];
                 nk[r] = __builtin_amdgcn_raw_buffer_load_b32(recs, (pw & kSlotMask) * 12u, 0, 0);
                 ni[r] = s_id[e] + id_base;
-                nb[r] = pw >> kSlotBits;
+                // (MODE 0: the payload holds one half of the box pair; the record keeps both)
+                nb[r] = MODE == 0 ? __builtin_amdgcn_raw_buffer_load_b32(recs, (pw & kSlotMask) * 12u + 8u, 0, 0) : pw >> kSlotBits;
             }
         }
         __syncthreads();  // (workgroup-scope fence included) every record has been read before any is overwritten
@@ -1473,6 +1511,8 @@ void launch_bin_level2(const BinLaunch& b, int level, hipStream_t s) {
     a.stamps = b.stamps;
     a.l1_words = b.l1_fused_words;
     a.l1_cap = b.l1_fused_cap;
+    a.bin_count_save = b.l1_fused_words ? b.bin_count : nullptr;
+    a.reference_boxes = b.reference_boxes ? 1u : 0u;
     const uint32_t bins = b.bins_x * b.bins_y;  // on-screen bins: the kernels map the block index onto the padded grid
     const bool sort = level < kBinSortLevels;
     if (sort && b.bin_shift <= 3) {  // bins of 4 x 4 or 8 x 8 tiles: the all-in-LDS kernel, sized by the level

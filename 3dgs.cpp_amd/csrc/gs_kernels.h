@@ -104,6 +104,10 @@ struct Counters {
     uint32_t blend_redo;      // quadrants (8 x 8 px) abandoned and re-rendered whole with the reference's arithmetic
     // the work queue of k_bin_queue (level 4 in one launch): items handed out so far (bins first, then depth slabs); bins beyond a slab planned so far
     uint32_t q_head, q_bins_done;
+    // tile instances actually LISTED: the cursor the lists are placed by.  Equal to `instances` unless level 2 made the lists from the
+    // records' alpha-cut boxes (gs_bin.h: bin_box_pair), then at most that.  0 after a frame of k_bin_build (which has one cursor).
+    // (Cleared by k_preprocess and published by the blend with the rest of this block: no kernel of its own touches it.)
+    uint32_t listed;
 };
 // The frame's timeline, stamped by the kernels themselves (round 6).  Every pass's first kernel writes the constant-rate clock
 // (wall_clock64: s_memrealtime, hipDeviceAttributeWallClockRate kHz) at its start -- thread 0 of workgroup 0 -- and a one-wave kernel
@@ -218,6 +222,7 @@ struct BinLaunch {
     uint32_t cand_capacity;     // level-1 candidates the candidate buffer holds
     const uint32_t* l1_fused_words;  // non-null: level 1 ran inside k_preprocess (L1Fused) -- a bin's count is its cursor, its offset
     uint32_t l1_fused_cap;           // (on-screen index) x this; level 2 produces V, E1, the fullest bin and the overflow flag
+    bool reference_boxes;       // k_bin_fast: make the lists from the records' reference boxes (no alpha-cut cull; gs_bin_l2.hip: BuildArgs)
     void* slabs;                // [slab_capacity] 288-byte depth-slab descriptors (level 4)
     uint32_t slab_capacity;
     uint32_t slab_epoch;        // != 0: level 4 as ONE launch (k_bin_queue); a value no earlier launch on these descriptors carried

@@ -6,6 +6,7 @@
 // multiply-adds appear only where written explicitly.
 // Reference restated (paths relative to /root/reference/src/shaders): preprocess.comp:34-183
 #include "gs_bin.h"
+#include "gs_tile_cull.h"
 
 namespace gs {
 
@@ -372,23 +373,31 @@ __device__ __forceinline__ void preprocess_one(const SceneView& sv, const gs_uni
         for (int k = 0; k < NB / BLOCK; ++k) bins.tbl[k * BLOCK + (int)threadIdx.x] = fbase[k];  // (an untouched bin: 0 over 0)
         __syncthreads();
         const BinGrid g{lf.tiles_x, lf.tiles_y, lf.bins_x, lf.bins_y, lf.bin_shift, lf.grid_shift};
-        auto emit = [&](uint32_t bin, uint32_t k, uint32_t gid, ushort4 box) {
+        // The record's third word carries two boxes clipped to the bin (gs_bin.h: bin_box_pair): the reference box -- which alone
+        // decides the bins a Gaussian is filed in, E1, the fullest bin and D -- and the alpha-cut box inside it (gs_tile_cull.h),
+        // from which level 2 makes the lists the blend walks.  A few instructions per visible GAUSSIAN, none per instance.
+        auto emit = [&](uint32_t bin, uint32_t k, uint32_t gid, ushort4 box, ushort4 tight) {
             const uint32_t pos = atomicAdd(&bins.tbl[bin], 1u);
             if (pos < lf.cap) {
                 const uint32_t sb = (bin >> lf.grid_shift) * lf.bins_x + (bin & ((1u << lf.grid_shift) - 1u));
                 uint32_t* const rec = lf.cand + (size_t)kCandWords * ((size_t)sb * lf.cap + pos);  // three adjacent dwords: one 12-byte store
                 rec[0] = k;
                 rec[1] = gid;
-                rec[2] = bin_local_box16(g, bin, box);
+                rec[2] = bin_box_pair(g, bin, box, tight);
             }
         };
         const uint32_t x0 = bb & 255u, y0 = (bb >> 8) & 255u, x1 = (bb >> 16) & 255u, y1 = bb >> 24;
         const ushort4 tb = make_ushort4((unsigned short)bx0, (unsigned short)by0, (unsigned short)bx1, (unsigned short)by1);
+        ushort4 tt = make_ushort4(0, 0, 0, 0);
+        if (vis) {
+            const TileBox t = tile_cull_box(c00, c01, c11, uvx, uvy, acut, TileBox{bx0, by0, bx1, by1});
+            tt = make_ushort4((unsigned short)t.x0, (unsigned short)t.y0, (unsigned short)t.x1, (unsigned short)t.y1);
+        }
         const uint32_t key = __float_as_uint(depth);
         const bool big = (x1 - x0) * (y1 - y0) > kL1BigBox;
         if (!big)
             for (uint32_t y = y0; y < y1; ++y)
-                for (uint32_t x = x0; x < x1; ++x) emit((y << lf.grid_shift) | x, key, oid, tb);
+                for (uint32_t x = x0; x < x1; ++x) emit((y << lf.grid_shift) | x, key, oid, tb, tt);
         for (uint64_t bm = __ballot(big); bm != 0; bm &= bm - 1) {  // one Gaussian at a time, one bin per lane
             const int src = __ffsll((unsigned long long)bm) - 1;
             const uint32_t b1 = (uint32_t)__builtin_amdgcn_readlane((int)bb, src);
@@ -398,7 +407,11 @@ __device__ __forceinline__ void preprocess_one(const SceneView& sv, const gs_uni
             const uint32_t bhi = (uint32_t)__builtin_amdgcn_readlane((int)((uint32_t)bx1 | ((uint32_t)by1 << 16)), src);
             const ushort4 bbox = make_ushort4((unsigned short)(blo & 0xFFFFu), (unsigned short)(blo >> 16), (unsigned short)(bhi & 0xFFFFu),
                                               (unsigned short)(bhi >> 16));
-            for (uint32_t c = lane; c < cells; c += WAVE) emit(((gy0 + c / bw) << lf.grid_shift) | (gx0 + c % bw), bkey, bgid, bbox);
+            const uint32_t tlo = (uint32_t)__builtin_amdgcn_readlane((int)((uint32_t)tt.x | ((uint32_t)tt.y << 16)), src);
+            const uint32_t thi = (uint32_t)__builtin_amdgcn_readlane((int)((uint32_t)tt.z | ((uint32_t)tt.w << 16)), src);
+            const ushort4 tbox = make_ushort4((unsigned short)(tlo & 0xFFFFu), (unsigned short)(tlo >> 16), (unsigned short)(thi & 0xFFFFu),
+                                              (unsigned short)(thi >> 16));
+            for (uint32_t c = lane; c < cells; c += WAVE) emit(((gy0 + c / bw) << lf.grid_shift) | (gx0 + c % bw), bkey, bgid, bbox, tbox);
         }
     }
 
@@ -461,6 +474,7 @@ __global__ __launch_bounds__(BLOCK) void k_preprocess(SceneView sv, PreUniforms 
         pu.counters->blend_redo = 0;
         pu.counters->q_head = 0;
         pu.counters->q_bins_done = 0;
+        pu.counters->listed = 0;
     }
     preprocess_one<AA, R1>(sv, u, av, i, i < sv.n, s_stage[threadIdx.x / WAVE], lf, s_bins);
 }

@@ -63,12 +63,12 @@ struct FrameBuffers {
     // (an aggregate: enqueue initialises the fields positionally, in the order they are declared and compared here)
     struct GraphKey {
         int level = -1, bin_shift = -1, hw_exp = 0, contract = 1;
-        bool antialiased = false, lockstep = false, l1_fused = false;
+        bool antialiased = false, lockstep = false, l1_fused = false, tile_cull = false;
         uint32_t width = 0, height = 0, capacity = 0, cand_capacity = 0;
         const void *tile_order = nullptr, *ranges = nullptr, *sh16 = nullptr;
         bool operator==(const GraphKey& o) const {
             return level == o.level && bin_shift == o.bin_shift && hw_exp == o.hw_exp && contract == o.contract &&
-                   antialiased == o.antialiased && lockstep == o.lockstep && l1_fused == o.l1_fused &&
+                   antialiased == o.antialiased && lockstep == o.lockstep && l1_fused == o.l1_fused && tile_cull == o.tile_cull &&
                    width == o.width && height == o.height && capacity == o.capacity && cand_capacity == o.cand_capacity &&
                    tile_order == o.tile_order && ranges == o.ranges && sh16 == o.sh16;
         }
@@ -156,6 +156,7 @@ struct FrameSlot {
     bool lockstep = false;      // the blend's lockstep setting this frame ran with
     bool l1_fused = false;      // k_preprocess filed the level-1 candidates itself (gs::L1Fused) ...
     uint32_t l1_cap = 0;        // ... into bin regions of this many records
+    bool culled = false;        // level 2 made the lists from the records' alpha-cut boxes (gs_renderer::frame_is_culled)
     uint32_t tune_round = 0;    // ... and the tuner's round it belongs to (samples of an earlier round are ignored)
     int tune_shape = 0;         // ... and which of the bank's tuners (one per frame shape) that was
 };
@@ -178,6 +179,64 @@ struct gs_renderer {
     // The one-pass level 1 (gs_kernels.h: L1Fused): when a frame takes it is L1FusedPolicy's rule; GS_L1_FUSED / gs_set_level1_fused set its mode
     L1FusedPolicy l1_policy;
     bool last_l1_fused = false;  // the most recently enqueued frame took it (gs_get_level1_fused)
+    // The alpha-cut tile cull (gs_tile_cull.h; GS_TILE_CULL / gs_set_tile_cull, default on).  k_preprocess's one-pass level 1 puts a
+    // second, tighter box into every candidate record and k_bin_fast makes the lists the blend walks from it; D, the capacity check,
+    // the statistics and the reference list taps follow the reference box.  Only those frames are culled: the three-kernel level 1,
+    // the dense lists and the global path write the reference box twice, the slab levels read the reference half.
+    bool tile_cull = !(std::getenv("GS_TILE_CULL") && std::atoi(std::getenv("GS_TILE_CULL")) == 0);
+    bool frame_is_culled(bool l1_fused, int level) const { return tile_cull && l1_fused && level < gs::kBinSlabLevel; }
+    bool last_culled = false;    // the most recently enqueued frame's lists are culled ...
+    int last_level = 0;          // ... it ran at this depth-order level, on this bin grid (what the reference taps re-run level 2 with)
+    BinGeometry last_geo{};
+    uint64_t last_listed = 0;    // tile instances in the lists of the most recently retired frame (gs_get_listed_instances)
+    // The reference's lists of a culled last frame, for the taps that answer from them: level 2 once more over that frame's
+    // candidate records with BinLaunch::reference_boxes, into buffers and counters of the taps' own.  Nothing of the frame moves.
+    DevBuf<uint32_t> tap_ranges, tap_sorted;
+    DevBuf<gs::Counters> tap_counters;
+    uint64_t tap_frame = ~0ull;  // frames_enqueued when the buffers were filled
+    const FrameBuffers* tap_set = nullptr;
+    void reference_lists(const uint32_t** ranges, const uint32_t** lists) {
+        FrameBuffers& fb = *last_set;
+        if (!last_culled) {
+            *ranges = fb.ranges.p;
+            *lists = sorted_gid;
+            return;
+        }
+        if (tap_frame != frames_enqueued || tap_set != last_set) {
+            tap_frame = ~0ull;
+            tap_ranges.ensure(2 * num_tiles);
+            tap_sorted.ensure(static_cast<size_t>(capacity) + 4);
+            tap_counters.ensure(1);
+            HIP_CHECK(hipMemsetAsync(tap_counters.p, 0, sizeof(gs::Counters), fb.stream));
+            gs::BinLaunch b{};
+            b.n_bound = static_cast<uint32_t>(scene->n);
+            b.bin_count = fb.bin_count.p;  // the frame's bin workgroups left their counts and offsets there (BuildArgs::bin_count_save)
+            b.cand = fb.cand.p;
+            b.ranges = tap_ranges.p;
+            b.sorted_gid = tap_sorted.p;
+            b.counters = tap_counters.p;
+            b.capacity = capacity;
+            b.cand_capacity = cand_capacity;
+            b.reference_boxes = true;
+            b.tiles_x = tiles_across(last_width);
+            b.tiles_y = tiles_across(last_height);
+            b.bins_x = last_geo.bins_x;
+            b.bins_y = last_geo.bins_y;
+            b.bin_shift = last_geo.bin_shift;
+            b.grid_shift = last_geo.grid_shift;
+            gs::launch_bin_level2(b, last_level, fb.stream);
+            HIP_CHECK(hipGetLastError());
+            gs::Counters c{};
+            HIP_CHECK(hipMemcpyAsync(&c, tap_counters.p, sizeof c, hipMemcpyDeviceToHost, fb.stream));
+            HIP_CHECK(hipStreamSynchronize(fb.stream));
+            if (c.overflow != 0 || c.instances != last.num_instances)
+                throw Error(GS_ERR_DEVICE, "the reference lists of a culled frame do not add up to the frame's instance count");
+            tap_frame = frames_enqueued;
+            tap_set = last_set;
+        }
+        *ranges = tap_ranges.p;
+        *lists = tap_sorted.p;
+    }
     FrameBuffers* last_set = nullptr;  // buffers of the most recently enqueued frame (stage taps, gs_accumulate_contributions)
     uint32_t last_width = 0, last_height = 0;  // ... and that frame's size
 
@@ -376,6 +435,7 @@ struct gs_renderer {
         last_width = last_height = 0;
         num_tiles = 0;
         sorted_gid = depth_order = nullptr;
+        last_culled = false;
     }
     bool has_last_frame() const { return have_frame && last_set != nullptr; }
 
@@ -527,6 +587,7 @@ struct gs_renderer {
                 b.cand_capacity = cand_capacity;
                 b.l1_fused_words = lf.words;
                 b.l1_fused_cap = l1_cap;
+                b.reference_boxes = !tile_cull;
                 b.slabs = fb.slabs.p;
                 b.slab_capacity = fb.slabs.p ? gs::kSlabCapacity : 0u;
                 // level 4 as one launch over a queue of bins and slabs -- not in a captured frame (a replay repeats its arguments,
@@ -565,7 +626,7 @@ struct gs_renderer {
             *sl.h_params = gs::FrameParams{u, d_rgba, d_bgra, sl.h_counters, sl.h_stamps};
             HIP_CHECK(hipMemcpyAsync(fb.params.p, sl.h_params, sizeof(gs::FrameParams), hipMemcpyHostToDevice, stream));
             const FrameBuffers::GraphKey key{lv, geo.bin_shift, blend_exp_mode(), contract ? 1 : 0,
-                                             antialiased, lockstep, l1_fused,
+                                             antialiased, lockstep, l1_fused, tile_cull,
                                              u.width, u.height, capacity, cand_capacity,
                                              tile_order.p, fb.ranges.p, sv.sh16};
             const int gi = lockstep ? 1 : 0;
@@ -600,6 +661,9 @@ struct gs_renderer {
         last_height = u.height;
         num_tiles = nt;
         last_l1_fused = l1_fused;
+        last_culled = frame_is_culled(l1_fused, lv);
+        last_level = lv;
+        last_geo = geo;
         depth_order = bin_local ? nullptr : fb.dvals[1].p;
         sorted_gid = fb.sorted.p;
 
@@ -608,6 +672,7 @@ struct gs_renderer {
         sl.lockstep = lockstep;
         sl.l1_fused = l1_fused;
         sl.l1_cap = l1_cap;
+        sl.culled = frame_is_culled(l1_fused, lv);
         sl.tune_round = tuner.round;
         sl.tune_shape = tune_shape;
         sl.u = u;
@@ -635,6 +700,7 @@ struct gs_renderer {
         policy.frame_retired(sl.level, sl.h_counters->max_bin, sl.bin_shift);
         l1_policy.frame_retired(sl.u.width, sl.u.height, sl.bin_shift, sl.h_counters->max_bin, sl.h_counters->bin_entries, sl.h_counters->visible);
         last = frame_stats(sl);
+        last_listed = sl.culled ? sl.h_counters->listed : sl.h_counters->instances;
         have_frame = true;
         const float v[7] = {last.ms_preprocess, last.ms_prefix_sum, last.ms_preprocess_sort, last.ms_sort,
                             last.ms_tile_boundary, last.ms_render, last.ms_total};
@@ -1045,6 +1111,33 @@ int gs_get_level1_fused(gs_renderer* r) {
     return rc != 0 ? rc : on;
 }
 
+int gs_set_tile_cull(gs_renderer* r, int enabled) {
+    return guarded([&] {
+        if (!r) throw Error(GS_ERR_INVALID, "null argument");
+        r->drain();
+        r->tile_cull = enabled != 0;
+    });
+}
+
+int gs_get_tile_cull(gs_renderer* r, int* last_frame_culled) {
+    int on = 0;
+    const int rc = guarded([&] {
+        if (!r) throw Error(GS_ERR_INVALID, "null argument");
+        on = r->tile_cull ? 1 : 0;
+        if (last_frame_culled) *last_frame_culled = r->last_set != nullptr && r->last_culled ? 1 : 0;  // (the most recently enqueued frame)
+    });
+    return rc != 0 ? rc : on;
+}
+
+int gs_get_listed_instances(gs_renderer* r, uint64_t* out) {
+    return guarded([&] {
+        if (!r || !out) throw Error(GS_ERR_INVALID, "null argument");
+        r->drain();
+        if (!r->has_last_frame()) throw Error(GS_ERR_INVALID, "no frame rendered yet");
+        *out = r->last_listed;
+    });
+}
+
 int gs_set_graph_mode(gs_renderer* r, int enabled) {
     return guarded([&] {
         if (!r) throw Error(GS_ERR_INVALID, "renderer is null");
@@ -1063,7 +1156,7 @@ int gs_debug_download(gs_renderer* r, int stage, void* dst, uint64_t bytes) {
         if (stage == GS_STAGE_DEPTH_ORDER && !r->depth_order)
             throw Error(GS_ERR_INVALID, "the depth-order tap exists only on the global depth-order path (gs_set_sort_path(r, 1))");
         const uint64_t n = r->scene->n, v = r->last.num_visible;
-        const uint64_t d = std::min<uint64_t>(r->last.num_instances, r->capacity);
+        const uint64_t d = std::min<uint64_t>(r->last.num_instances, r->capacity), d_ref = d;
         const void* src = nullptr;
         uint64_t size = 0;
         if (r->last_set->planes_stale && (stage == GS_STAGE_TILES || stage == GS_STAGE_DEPTH || stage == GS_STAGE_AABB)) {
@@ -1106,12 +1199,22 @@ int gs_debug_download(gs_renderer* r, int stage, void* dst, uint64_t bytes) {
             case GS_STAGE_SORTED_TILE:
             case GS_STAGE_SORTED_GID:
             case GS_STAGE_RANGES:
+            case GS_STAGE_LISTS_CULLED:
+            case GS_STAGE_RANGES_CULLED:
                 {   // The per-tile lists are stored bin-major (the tiles of a bin consecutive, the bins wherever their
                     // workgroup's atomic add put them); `ranges` holds each tile's (start, end) in that buffer.  The
                     // reference's buffers are the same lists laid end to end in tile order: the taps present them so.
+                    // (The _CULLED pair: the frame's own lists, as the blend walked them; the others: the reference's lists,
+                    // made once more from the reference boxes where the frame's are culled.)
+                    const bool own = stage == GS_STAGE_LISTS_CULLED || stage == GS_STAGE_RANGES_CULLED;
+                    const uint32_t *ranges_src = r->last_set->ranges.p, *lists_src = r->sorted_gid;
+                    if (!own) r->reference_lists(&ranges_src, &lists_src);
+                    const uint64_t d = own ? std::min<uint64_t>(r->last_listed, r->capacity) : d_ref;
+                    if (stage == GS_STAGE_RANGES_CULLED) stage = GS_STAGE_RANGES;
+                    if (stage == GS_STAGE_LISTS_CULLED) stage = GS_STAGE_SORTED_GID;
                     const uint64_t nt = r->num_tiles;
                     std::vector<uint32_t> rg(2 * nt);
-                    if (nt) HIP_CHECK(hipMemcpy(rg.data(), r->last_set->ranges.p, rg.size() * 4, hipMemcpyDeviceToHost));
+                    if (nt) HIP_CHECK(hipMemcpy(rg.data(), ranges_src, rg.size() * 4, hipMemcpyDeviceToHost));
                     if (stage == GS_STAGE_RANGES) {
                         if (bytes < nt * 8) throw Error(GS_ERR_INVALID, "destination too small for stage buffer");
                         uint32_t* out = static_cast<uint32_t*>(dst);
@@ -1128,7 +1231,7 @@ int gs_debug_download(gs_renderer* r, int stage, void* dst, uint64_t bytes) {
                     std::vector<uint32_t> lists;
                     if (stage == GS_STAGE_SORTED_GID) {
                         lists.resize(r->capacity);
-                        HIP_CHECK(hipMemcpy(lists.data(), r->sorted_gid, lists.size() * 4, hipMemcpyDeviceToHost));
+                        HIP_CHECK(hipMemcpy(lists.data(), lists_src, lists.size() * 4, hipMemcpyDeviceToHost));
                     }
                     uint32_t* out = static_cast<uint32_t*>(dst);
                     uint64_t pos = 0;
@@ -1137,8 +1240,15 @@ int gs_debug_download(gs_renderer* r, int stage, void* dst, uint64_t bytes) {
                             out[pos++] = stage == GS_STAGE_SORTED_GID ? lists[i] : static_cast<uint32_t>(t);
                     return;
                 }
-            case GS_STAGE_LISTS_RAW: src = r->sorted_gid; size = d * 4; break;
-            case GS_STAGE_RANGES_RAW: src = r->last_set->ranges.p; size = r->num_tiles * 8; break;
+            case GS_STAGE_LISTS_RAW:
+            case GS_STAGE_RANGES_RAW:
+                {
+                    const uint32_t *ranges_src = nullptr, *lists_src = nullptr;
+                    r->reference_lists(&ranges_src, &lists_src);
+                    if (stage == GS_STAGE_LISTS_RAW) src = lists_src, size = d * 4;
+                    else src = ranges_src, size = r->num_tiles * 8;
+                    break;
+                }
             default: throw Error(GS_ERR_INVALID, "unknown stage");
         }
         if (bytes < size) throw Error(GS_ERR_INVALID, "destination too small for stage buffer");

@@ -99,7 +99,10 @@ enum gs_stage {
     GS_STAGE_SORTED_GID = 12,    /* uint32[D]  == sorted payload of the reference             */
     GS_STAGE_RANGES = 13,        /* uint32[2T] == tileBoundaryBuffer                          */
     GS_STAGE_LISTS_RAW = 14,     /* uint32[D]  the per-tile lists exactly as they lie in HBM (bin-major)            */
-    GS_STAGE_RANGES_RAW = 15     /* uint32[2T] each tile's (start, end) in GS_STAGE_LISTS_RAW; (0, 0) when empty    */
+    GS_STAGE_RANGES_RAW = 15,    /* uint32[2T] each tile's (start, end) in GS_STAGE_LISTS_RAW; (0, 0) when empty    */
+    /* the lists as the blend walked them (gs_set_tile_cull): tile order, like 12 / 13; equal to those unless the frame is culled */
+    GS_STAGE_LISTS_CULLED = 16,  /* uint32[L]  L = gs_get_listed_instances                     */
+    GS_STAGE_RANGES_CULLED = 17  /* uint32[2T] each tile's (start, end) in GS_STAGE_LISTS_CULLED; (0, 0) when empty */
 };
 
 const char* gs_last_error(void);
@@ -422,6 +425,22 @@ int gs_get_blend_lockstep(gs_renderer* r, int* settled);
 int gs_set_level1_fused(gs_renderer* r, int mode);
 /* 1: the most recently enqueued frame took the one-pass level 1; 0: it ran the three level-1 kernels (negative: error). */
 int gs_get_level1_fused(gs_renderer* r);
+/* The ALPHA-CUT TILE CULL (default on; GS_TILE_CULL=0 / 1 sets the initial value).  render.comp:78 skips an entry whose alpha is
+ * below 1/255, i.e. whose `power` is below the Gaussian's alpha cut: a Gaussian reaches no further than the ellipse power = cut,
+ * which is usually well inside the 3-sigma tile box of preprocess.comp:160-165.  On the frames of the one-pass level 1 that
+ * k_bin_fast orders (depth-order levels 0 .. 3) the per-tile lists the blend walks are made from the tiles that ellipse's bounding
+ * rectangle touches (csrc/gs_tile_cull.h, with the slack that makes the rule conservative against the shader's rounded power):
+ * every entry left out is one the shader skips at every pixel of the tile, so images, contributions, feature maps and lifts are
+ * what they are without the cull.  What describes the REFERENCE's lists does not move either: gs_frame_stats (num_instances is
+ * the reference's D; capacity growth and retries follow it) and the taps GS_STAGE_SORTED_TILE / _SORTED_GID / _RANGES /
+ * _LISTS_RAW / _RANGES_RAW, which on a culled frame are answered by running level 2 once more over the frame's candidate
+ * records with the reference boxes, into buffers of the taps' own.  GS_STAGE_LISTS_CULLED / _RANGES_CULLED show the lists as
+ * walked.  Frames of the three-kernel level 1, of the dense lists, of the slab level and of the global path are not culled. */
+int gs_set_tile_cull(gs_renderer* r, int enabled);
+/* 1 / 0: the switch (negative: error).  *last_frame_culled (nullable): 1 if the most recently enqueued frame's lists are culled. */
+int gs_get_tile_cull(gs_renderer* r, int* last_frame_culled);
+/* Tile instances in the lists of the last frame as the blend walked them: num_instances unless the frame is culled.  Synchronizes. */
+int gs_get_listed_instances(gs_renderer* r, uint64_t* out);
 /* Sums of the per-pass spans over all frames retired since the last reset (ms fields are sums,
  * counts are those of the last frame); *frames = number of frames summed.  Synchronizes. */
 int gs_get_timing_totals(gs_renderer* r, gs_frame_stats* sum, uint64_t* frames, int reset);

@@ -56,11 +56,25 @@ def main():
             L.gs_debug_blend_stats(out, 1)
         st = rend.stats()
         v = [int(x) for x in out]
+        # walked_pairs is defined over the REFERENCE's lists.  On a frame whose lists are culled (gs_set_tile_cull) the instrumented
+        # loop walks the shorter lists and would count fewer of them: that figure, and contributing_pairs beside it, come from one
+        # more frame with the cull off; everything else is this implementation's work on the lists it walks.
+        listed = None
+        if hasattr(L, "gs_set_tile_cull") and rend.tile_cull()[1]:
+            listed = rend.listed_instances()
+            rend.set_tile_cull(False)
+            rend.render_host(u, want_rgba=True)
+            L.gs_debug_blend_stats(out, 1)
+            v_ref = [int(x) for x in out]
+            assert v_ref[8] == v[8], "the cull changed the contributing pairs"
+            v[7] = v_ref[7]
         result[workload_key(n, w, h, kind)] = {
             "gaussians": int(st.num_gaussians), "visible": int(st.num_visible), "instances": int(st.num_instances),
             "walked_pairs": v[7], "contributing_pairs": v[8], "wave_pairs": v[2], "wave_pairs_reaching_exp": v[4],
             "lanes_alive_in_wave_pairs": v[3], "lanes_in_exp": v[5], "wave_chunks": v[0], "entries_staged": v[6],
             "flop_per_walked_pair": 22}
+        if listed is not None:
+            result[workload_key(n, w, h, kind)]["instances_listed"] = int(listed)
         print(name, json.dumps(result[workload_key(n, w, h, kind)]), flush=True)
         rend.close()
         scene.close()
