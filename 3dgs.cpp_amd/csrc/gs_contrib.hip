@@ -110,13 +110,11 @@ __global__ __launch_bounds__(BLOCK) void k_contrib(const uint2* __restrict__ ran
     if (top_id && q.inside) top_id[q.p] = counted ? best_id : kContribNone;
 }
 
-void launch_contributions(const uint32_t* ranges, const uint32_t* sorted_gid, const uint32_t* tile_order, const AttrRecord* rec,
-                          uint32_t width, uint32_t height, const uint8_t* mask, uint64_t* weight, uint32_t* pixels, uint32_t* top_id,
-                          hipStream_t s) {
-    if (width == 0 || height == 0) return;
-    const uint32_t tx = (width + kTile - 1) / kTile, ty = (height + kTile - 1) / kTile;
-    hipLaunchKernelGGL(k_contrib, dim3(tx * ty), dim3(BLOCK), 0, s, reinterpret_cast<const uint2*>(ranges), sorted_gid, tile_order, rec,
-                       width, height, tx, mask, reinterpret_cast<unsigned long long*>(weight), pixels, top_id);
+void launch_contributions(const TileLists& t, const uint8_t* mask, uint64_t* weight, uint32_t* pixels, uint32_t* top_id, hipStream_t s) {
+    if (t.width == 0 || t.height == 0) return;
+    const uint32_t tx = (t.width + kTile - 1) / kTile, ty = (t.height + kTile - 1) / kTile;
+    hipLaunchKernelGGL(k_contrib, dim3(tx * ty), dim3(BLOCK), 0, s, reinterpret_cast<const uint2*>(t.ranges), t.sorted_gid, t.tile_order,
+                       t.rec, t.width, t.height, tx, mask, reinterpret_cast<unsigned long long*>(weight), pixels, top_id);
 }
 
 }  // namespace gs

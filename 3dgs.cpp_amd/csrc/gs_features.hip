@@ -124,13 +124,14 @@ __global__ __launch_bounds__(BLOCK) void k_features(const uint2* __restrict__ ra
     if (out_median) out_median[p] = M;
 }
 
-void launch_features(const uint32_t* ranges, const uint32_t* sorted_gid, const uint32_t* tile_order, const AttrRecord* rec,
-                     uint32_t width, uint32_t height, const float* features, uint32_t channels, float* out_features, float* out_alpha,
+void launch_features(const TileLists& t, const float* features, uint32_t channels, float* out_features, float* out_alpha,
                      float* out_depth, float* out_median, hipStream_t s) {
+    const uint32_t *sorted_gid = t.sorted_gid, *tile_order = t.tile_order, width = t.width, height = t.height;
+    const AttrRecord* rec = t.rec;
     if (width == 0 || height == 0) return;
     constexpr int G = kFeatureGroup;
     const uint32_t tx = (width + kTile - 1) / kTile, ty = (height + kTile - 1) / kTile;
-    const uint2* rg = reinterpret_cast<const uint2*>(ranges);
+    const uint2* rg = reinterpret_cast<const uint2*>(t.ranges);
     if (!out_features) channels = 0;
     if (channels == 0) {
         if (out_alpha || out_depth || out_median)

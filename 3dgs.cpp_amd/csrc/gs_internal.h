@@ -5,7 +5,8 @@
 //   gs_capi.cpp      error plumbing, device selection, the entry points that own no object
 //   gs_scene_host.cpp  gs_scene: load-time passes, upload, download, SH quantisation
 //   gs_ply.cpp       PLY ingest (header parse, mmap, streamed upload)
-//   gs_renderer.cpp  per-frame buffer sets, the ring of frames in flight, graph capture, the render entry points
+//   gs_renderer.cpp  per-frame buffer sets (FrameBuffers), what a frame is decided to run with (FramePlan), the ring of frames in
+//                    flight (FrameSlot), the frame the taps and passes answer from (LastFrame), graph capture, the render entry points
 //     gs_depth_policy.h  which depth-order level and bin grid a frame runs with (host-only, tested on the CPU; constants: gs_levels.h)
 //     gs_blend_tuner.h   which of the blend's two schedules it runs (host-only, tested on the CPU)
 //   gs_dist.cpp      multi-GPU: RCCL scene broadcast + pose sharding

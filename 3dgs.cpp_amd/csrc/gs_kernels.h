@@ -265,21 +265,27 @@ void launch_blend(const uint32_t* ranges, const uint32_t* sorted_gid, const uint
                   uint64_t* stamps /* nullable: [ST_BLEND] = the kernel's start */,
                   hipStream_t s);
 
+// A finished frame's per-tile lists, as the three passes below walk them: the first six arguments of each of their kernels.
+struct TileLists {
+    const uint32_t* ranges;      // [T][2]
+    const uint32_t* sorted_gid;  // the lists, bin-major
+    const uint32_t* tile_order;  // tile_order[b] = the tile workgroup b walks
+    const AttrRecord* rec;       // [N]
+    uint32_t width, height;
+};
+
 // gs_accumulate_contributions (gs3d_hip.h; gs_contrib.hip): a second walk of a finished frame's per-tile lists with the reference's
 // arithmetic.  Reads ranges / sorted_gid / rec of that frame, writes the caller's arrays only: weight[g] += sum of q, pixels[g] +=
 // blended pixels (integer atomics), top_id[pixel] = the dominant id.  mask, weight, pixels, top_id: nullable, device memory.
-void launch_contributions(const uint32_t* ranges, const uint32_t* sorted_gid, const uint32_t* tile_order, const AttrRecord* rec,
-                          uint32_t width, uint32_t height, const uint8_t* mask, uint64_t* weight, uint32_t* pixels, uint32_t* top_id,
-                          hipStream_t s);
+void launch_contributions(const TileLists& t, const uint8_t* mask, uint64_t* weight, uint32_t* pixels, uint32_t* top_id, hipStream_t s);
 
 // gs_blend_features (gs3d_hip.h; gs_features.hip): the same second walk, per pixel: `channels` caller-supplied per-Gaussian floats
 // blended as the colour is (features [N][channels] -> out_features [height][width][channels]), alpha = 1 - T, expected and median
 // depth.  Channels go in groups of kFeatureGroup, one launch per group on `s`, each walking the lists again; the first launch (or a
 // channel-less one) writes alpha and the depths.  Every output is nullable; with out_features null no channel is blended.
 constexpr int kFeatureGroup = 16;
-void launch_features(const uint32_t* ranges, const uint32_t* sorted_gid, const uint32_t* tile_order, const AttrRecord* rec,
-                     uint32_t width, uint32_t height, const float* features, uint32_t channels, float* out_features, float* out_alpha,
-                     float* out_depth, float* out_median, hipStream_t s);
+void launch_features(const TileLists& t, const float* features, uint32_t channels, float* out_features, float* out_alpha, float* out_depth,
+                     float* out_median, hipStream_t s);
 
 // gs_lift_pixels (gs3d_hip.h; gs_lift.hip): the same second walk, transposed: per counted pixel (inside the image, mask null or
 // != 0) `channels` caller-supplied floats (values [height][width][channels]) are carried onto the Gaussians blended there with
@@ -287,8 +293,7 @@ void launch_features(const uint32_t* ranges, const uint32_t* sorted_gid, const u
 // go in groups of kLiftGroup, one launch per group on `s`, each walking the lists again; the first launch (or a channel-less one)
 // adds the weights.  mask, out, out_weight: nullable, device memory; with out null no channel is lifted.
 constexpr int kLiftGroup = 16, kLiftGroupSmall = 4;  // (a last group of at most 4 channels runs a kernel of 4)
-void launch_lift(const uint32_t* ranges, const uint32_t* sorted_gid, const uint32_t* tile_order, const AttrRecord* rec, uint32_t width,
-                 uint32_t height, const uint8_t* mask, const float* values, uint32_t channels, double* out, double* out_weight,
+void launch_lift(const TileLists& t, const uint8_t* mask, const float* values, uint32_t channels, double* out, double* out_weight,
                  hipStream_t s);
 
 }  // namespace gs

@@ -242,13 +242,14 @@ __global__ __launch_bounds__(BLOCK) void k_lift(const uint2* __restrict__ ranges
     }
 }
 
-void launch_lift(const uint32_t* ranges, const uint32_t* sorted_gid, const uint32_t* tile_order, const AttrRecord* rec, uint32_t width,
-                 uint32_t height, const uint8_t* mask, const float* values, uint32_t channels, double* out, double* out_weight,
+void launch_lift(const TileLists& t, const uint8_t* mask, const float* values, uint32_t channels, double* out, double* out_weight,
                  hipStream_t s) {
+    const uint32_t *sorted_gid = t.sorted_gid, *tile_order = t.tile_order, width = t.width, height = t.height;
+    const AttrRecord* rec = t.rec;
     if (width == 0 || height == 0) return;
     constexpr int G = kLiftGroup;
     const uint32_t tx = (width + kTile - 1) / kTile, ty = (height + kTile - 1) / kTile;
-    const uint2* rg = reinterpret_cast<const uint2*>(ranges);
+    const uint2* rg = reinterpret_cast<const uint2*>(t.ranges);
     if (!out) channels = 0;
     if (channels == 0) {
         if (out_weight)

@@ -14,6 +14,7 @@
 #include <cstring>
 #include <limits>
 #include <memory>
+#include <utility>
 #include <vector>
 
 #include "gs_blend_tuner.h"
@@ -60,7 +61,6 @@ struct FrameBuffers {
     // ... one per setting of the blend's lockstep: the tuner flips it several times per measurement, and re-capturing the frame on every
     // flip would make the measurement weigh the capture (round-5 advisor finding)
     hipGraphExec_t graph_execs[2] = {nullptr, nullptr};
-    // (an aggregate: enqueue initialises the fields positionally, in the order they are declared and compared here)
     struct GraphKey {
         int level = -1, bin_shift = -1, hw_exp = 0, contract = 1;
         bool antialiased = false, lockstep = false, l1_fused = false, tile_cull = false;
@@ -142,6 +142,26 @@ struct FrameBuffers {
     }
 };
 
+// What a frame runs with: everything gs_renderer::plan_frame decides before the frame's first launch.  Decided once and stored once
+// -- in the frame's slot of the ring, and, when the frame is the last one, in LastFrame; the graph key is made from it.
+struct FramePlan {
+    uint32_t width = 0, height = 0, tx = 0, ty = 0;  // the frame's size and its grid of tiles ...
+    uint64_t num_tiles = 0;     // ... tx * ty of them
+    int level = 0;              // the depth-order level the frame runs at (DepthPolicy::frame_level) ...
+    BinGeometry geo{};          // ... on this bin grid
+    bool l1_fused = false;      // k_preprocess files the level-1 candidates itself (gs::L1Fused) ...
+    uint32_t l1_cap = 0;        // ... into bin regions of this many records
+    bool dense_list = false;    // level 1 streams the dense lists of visible Gaussians, which k_preprocess writes beside the planes
+    bool culled = false;        // level 2 makes the lists from the records' alpha-cut boxes (gs_renderer::tile_cull)
+    bool lockstep = false;      // the blend's lockstep setting ...
+    uint32_t tune_round = 0;    // ... and the tuner's round it belongs to (samples of an earlier round are ignored)
+    int tune_shape = 0;         // ... and which of the bank's tuners (one per frame shape) that was
+    bool stamped = false;       // the frame has Gaussians and pixels (one without launches nothing that stamps or publishes the counters)
+    bool bin_local() const { return level < DepthPolicy::kGlobalLevel; }
+    // the level-1 kernels that take their items in any order (bin-local path, bins of <= 8 x 8 tiles)
+    bool l1_any_order() const { return bin_local() && geo.bin_shift <= 3; }
+};
+
 struct FrameSlot {
     gs_uniforms u{};
     float* rgba = nullptr;
@@ -150,15 +170,16 @@ struct FrameSlot {
     gs::Counters* h_counters = nullptr;  // pinned
     uint64_t* h_stamps = nullptr;        // pinned [ST_COUNT]: the frame's timeline, written by its kernels and copied here by k_frame_end
     gs::FrameParams* h_params = nullptr;  // pinned staging of the frame's parameter block (graph replay)
-    bool timed = false;
-    int level = 0;  // the depth-order level this frame ran at (DepthPolicy::frame_level)
-    int bin_shift = 3;
-    bool lockstep = false;      // the blend's lockstep setting this frame ran with
-    bool l1_fused = false;      // k_preprocess filed the level-1 candidates itself (gs::L1Fused) ...
-    uint32_t l1_cap = 0;        // ... into bin regions of this many records
-    bool culled = false;        // level 2 made the lists from the records' alpha-cut boxes (gs_renderer::frame_is_culled)
-    uint32_t tune_round = 0;    // ... and the tuner's round it belongs to (samples of an earlier round are ignored)
-    int tune_shape = 0;         // ... and which of the bank's tuners (one per frame shape) that was
+    FramePlan plan;                      // what the frame ran with
+};
+
+// The frame the taps and the three passes answer from: the most recently enqueued one.  One value, replaced whole when a frame has
+// been issued and emptied when the renderer loses its last frame (gs_renderer::forget_last_frame): nothing in it outlives its frame.
+struct LastFrame {
+    FrameBuffers* set = nullptr;  // the frame's buffers; null: there is no last frame
+    FramePlan plan;
+    uint64_t listed = 0;          // tile instances in the lists of the frame that retired last (once nothing is queued: this frame's)
+    bool tap_lists = false;       // the renderer's tap buffers hold THIS frame's reference lists (gs_renderer::reference_lists)
 };
 
 struct gs_renderer {
@@ -178,67 +199,14 @@ struct gs_renderer {
     uint32_t default_cand_capacity = 0;  // ... and what they held at creation (L1FusedPolicy::grow_to's ceiling is a multiple of it)
     // The one-pass level 1 (gs_kernels.h: L1Fused): when a frame takes it is L1FusedPolicy's rule; GS_L1_FUSED / gs_set_level1_fused set its mode
     L1FusedPolicy l1_policy;
-    bool last_l1_fused = false;  // the most recently enqueued frame took it (gs_get_level1_fused)
+    // gs_get_level1_fused's answer.  It does not drain, and it still describes a frame that failed or was dropped after it was enqueued,
+    bool enqueued_l1_fused = false;  // so this one fact about the most recently enqueued frame is kept outside LastFrame
     // The alpha-cut tile cull (gs_tile_cull.h; GS_TILE_CULL / gs_set_tile_cull, default on).  k_preprocess's one-pass level 1 puts a
     // second, tighter box into every candidate record and k_bin_fast makes the lists the blend walks from it; D, the capacity check,
     // the statistics and the reference list taps follow the reference box.  Only those frames are culled: the three-kernel level 1,
     // the dense lists and the global path write the reference box twice, the slab levels read the reference half.
-    bool tile_cull = !(std::getenv("GS_TILE_CULL") && std::atoi(std::getenv("GS_TILE_CULL")) == 0);
-    bool frame_is_culled(bool l1_fused, int level) const { return tile_cull && l1_fused && level < gs::kBinSlabLevel; }
-    bool last_culled = false;    // the most recently enqueued frame's lists are culled ...
-    int last_level = 0;          // ... it ran at this depth-order level, on this bin grid (what the reference taps re-run level 2 with)
-    BinGeometry last_geo{};
-    uint64_t last_listed = 0;    // tile instances in the lists of the most recently retired frame (gs_get_listed_instances)
-    // The reference's lists of a culled last frame, for the taps that answer from them: level 2 once more over that frame's
-    // candidate records with BinLaunch::reference_boxes, into buffers and counters of the taps' own.  Nothing of the frame moves.
-    DevBuf<uint32_t> tap_ranges, tap_sorted;
-    DevBuf<gs::Counters> tap_counters;
-    uint64_t tap_frame = ~0ull;  // frames_enqueued when the buffers were filled
-    const FrameBuffers* tap_set = nullptr;
-    void reference_lists(const uint32_t** ranges, const uint32_t** lists) {
-        FrameBuffers& fb = *last_set;
-        if (!last_culled) {
-            *ranges = fb.ranges.p;
-            *lists = sorted_gid;
-            return;
-        }
-        if (tap_frame != frames_enqueued || tap_set != last_set) {
-            tap_frame = ~0ull;
-            tap_ranges.ensure(2 * num_tiles);
-            tap_sorted.ensure(static_cast<size_t>(capacity) + 4);
-            tap_counters.ensure(1);
-            HIP_CHECK(hipMemsetAsync(tap_counters.p, 0, sizeof(gs::Counters), fb.stream));
-            gs::BinLaunch b{};
-            b.n_bound = static_cast<uint32_t>(scene->n);
-            b.bin_count = fb.bin_count.p;  // the frame's bin workgroups left their counts and offsets there (BuildArgs::bin_count_save)
-            b.cand = fb.cand.p;
-            b.ranges = tap_ranges.p;
-            b.sorted_gid = tap_sorted.p;
-            b.counters = tap_counters.p;
-            b.capacity = capacity;
-            b.cand_capacity = cand_capacity;
-            b.reference_boxes = true;
-            b.tiles_x = tiles_across(last_width);
-            b.tiles_y = tiles_across(last_height);
-            b.bins_x = last_geo.bins_x;
-            b.bins_y = last_geo.bins_y;
-            b.bin_shift = last_geo.bin_shift;
-            b.grid_shift = last_geo.grid_shift;
-            gs::launch_bin_level2(b, last_level, fb.stream);
-            HIP_CHECK(hipGetLastError());
-            gs::Counters c{};
-            HIP_CHECK(hipMemcpyAsync(&c, tap_counters.p, sizeof c, hipMemcpyDeviceToHost, fb.stream));
-            HIP_CHECK(hipStreamSynchronize(fb.stream));
-            if (c.overflow != 0 || c.instances != last.num_instances)
-                throw Error(GS_ERR_DEVICE, "the reference lists of a culled frame do not add up to the frame's instance count");
-            tap_frame = frames_enqueued;
-            tap_set = last_set;
-        }
-        *ranges = tap_ranges.p;
-        *lists = tap_sorted.p;
-    }
-    FrameBuffers* last_set = nullptr;  // buffers of the most recently enqueued frame (stage taps, gs_accumulate_contributions)
-    uint32_t last_width = 0, last_height = 0;  // ... and that frame's size
+    bool tile_cull = true;
+    LastFrame last_frame;
 
     // frames in flight: a ring of descriptors, all enqueued on `stream` (so device buffers are
     // reused in stream order); the host only waits when the ring is full or on gs_synchronize.
@@ -280,14 +248,41 @@ struct gs_renderer {
     // the three any-order level-1 kernels -- the fall-back of the one-pass level 1: read in spatial order, the N-wide planes are
     // written by scene id, a store per Gaussian to a line of its own (B: 4 430 frames/s over the planes, 4 960 over the lists,
     // profiles/r16_l1_one_pass_ab.txt).  An explicit GS_L1_DENSE_MIN is taken at its word.
-    bool dense_for_spatial = std::getenv("GS_L1_DENSE_MIN") == nullptr;
+    bool dense_for_spatial = true;
     bool wants_dense_lists() const { return scene->n >= dense_min || (dense_for_spatial && scene->perm.p); }
-    bool debug_levels = std::getenv("GS_DEBUG_LEVELS") != nullptr;
-    bool level2_queue = !(std::getenv("GS_L2_QUEUE") && std::atoi(std::getenv("GS_L2_QUEUE")) == 0);
+    bool debug_levels = false, debug_occupancy = false;  // GS_DEBUG_LEVELS, GS_DEBUG_OCCUPANCY
+    bool level2_queue = true;                            // GS_L2_QUEUE=0: level 4 as the two launches of round 4
+    // test knobs (0: not given): start small so that the overflow / grow / re-run machinery is exercised by small scenes
+    uint64_t initial_capacity = 0, initial_cand_capacity = 0;  // GS_INITIAL_CAPACITY, GS_INITIAL_CAND_CAPACITY
     // GS_DEBUG_STALLS=<ms>: a gs_render call that keeps the host longer than this is reported on stderr with the time each of
     // its parts took (wait for a free frame slot; the launches of each pass; the closing event records) -- how the runtime's
     // own hiccups (profiles/r05_stall_*.txt) are told from the renderer's
-    double stall_ms = std::getenv("GS_DEBUG_STALLS") ? std::atof(std::getenv("GS_DEBUG_STALLS")) : 0.0;
+    double stall_ms = 0.0;
+
+    // Every GS_* variable the renderer reads: once, at creation, before the first buffer set is sized (dense_min sizes it).  Each is
+    // the initial value of the setter named beside it, or a debug / test knob that has no setter.
+    void read_environment() {
+        auto text = [](const char* name) { return std::getenv(name); };
+        auto num = [&](const char* name, int unset) { return text(name) ? std::atoi(text(name)) : unset; };
+        auto size = [&](const char* name) { return text(name) ? std::max<uint64_t>(256, std::strtoull(text(name), nullptr, 10)) : 0; };
+        auto tri = [](int v) { return v < 0 ? -1 : (v != 0 ? 1 : 0); };
+        tile_cull = num("GS_TILE_CULL", 1) != 0;                                     // gs_set_tile_cull
+        dense_for_spatial = !text("GS_L1_DENSE_MIN");                                // (an explicit value is taken at its word)
+        if (!dense_for_spatial) dense_min = std::strtoull(text("GS_L1_DENSE_MIN"), nullptr, 10);
+        debug_levels = text("GS_DEBUG_LEVELS") != nullptr, debug_occupancy = text("GS_DEBUG_OCCUPANCY") != nullptr;
+        level2_queue = num("GS_L2_QUEUE", 1) != 0;
+        if (text("GS_DEBUG_STALLS")) stall_ms = std::atof(text("GS_DEBUG_STALLS"));
+        if (text("GS_BLEND_LOCKSTEP")) tuners.pin(tri(num("GS_BLEND_LOCKSTEP", 0)));  // gs_set_blend_lockstep
+        initial_capacity = size("GS_INITIAL_CAPACITY"), initial_cand_capacity = size("GS_INITIAL_CAND_CAPACITY");
+        l1_policy.mode = tri(num("GS_L1_FUSED", l1_policy.mode));                    // gs_set_level1_fused
+        graph_mode = num("GS_GRAPH", 0) != 0;                                        // gs_set_graph_mode
+        exp_mode = std::min(3, std::max(0, num("GS_EXP_MODE", exp_mode)));           // gs_set_exp_mode
+        contract = num("GS_BLEND_CONTRACTION", 0) != 0;                              // gs_set_blend_contraction
+        antialiased = num("GS_ANTIALIASED", 0) != 0;                                 // gs_set_antialiased
+        policy.min_bin_shift = std::min(5, std::max(2, num("GS_BIN_SHIFT", policy.min_bin_shift)));  // default bin edge
+        policy.sort_mode = num("GS_SORT_PATH", 0);                                   // gs_set_sort_path, for hosts that cannot call it (the viewer)
+        if (policy.sort_mode < 0 || policy.sort_mode > 2) throw Error(GS_ERR_INVALID, "GS_SORT_PATH must be 0 (auto), 1 (global) or 2 (bin-local)");
+    }
     static constexpr int kLaps = 10;
     std::chrono::steady_clock::time_point laps[kLaps];
     void lap(int k) {
@@ -301,8 +296,7 @@ struct gs_renderer {
                              "level2 %.3f, blend %.3f, closing events %.3f\n", (unsigned long long)(frames_enqueued - 1), ms(0, 9), ms(0, 1), ms(1, 2), ms(2, 3),
                      ms(3, 4), ms(4, 5), ms(5, 6), ms(6, 7), ms(7, 9));
     }
-    bool have_frame = false;
-    uint32_t retries = 0;        // lifetime count of re-run frames (statistics only)
+    uint32_t retries = 0;       // lifetime count of re-run frames (statistics only)
     uint32_t redo_chain = 0;     // consecutive re-runs since a frame last retired cleanly: the runaway guard
     double total_ms[7] = {0, 0, 0, 0, 0, 0, 0};
     uint64_t total_frames = 0;
@@ -312,10 +306,6 @@ struct gs_renderer {
     std::vector<float> intervals;
     bool prev_retired = false;  // the frame before the one being retired completed normally (its events are valid)
     uint64_t latest_done = 0;   // index of the retired frame whose blend ended last (at most sets - 1 frames back)
-
-    uint32_t* sorted_gid = nullptr;  // result buffers of the last enqueued frame
-    uint32_t* depth_order = nullptr;
-    uint64_t num_tiles = 0;
 
     ~gs_renderer() {
         for (auto& sl : slots) {
@@ -338,14 +328,13 @@ struct gs_renderer {
     }
 
     void init() {
-        if (const char* e = std::getenv("GS_BLEND_LOCKSTEP")) tuners.pin(std::atoi(e) < 0 ? -1 : (std::atoi(e) != 0 ? 1 : 0));
         HIP_CHECK(hipSetDevice(scene->device));
         {   // the clock the kernels stamp the frame's timeline with (wall_clock64): constant rate, in kHz
             int khz = 0;
             if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, scene->device) == hipSuccess && khz > 0) tick_ms = 1.0 / khz;
         }
         HIP_CHECK(gs::bin_prepare_device());
-        if (std::getenv("GS_DEBUG_OCCUPANCY")) gs::bin_debug_occupancy();
+        if (debug_occupancy) gs::bin_debug_occupancy();
         for (auto& sl : slots) {
             HIP_CHECK(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
             HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&sl.h_stamps), gs::ST_COUNT * sizeof(uint64_t), hipHostMallocDefault));
@@ -354,14 +343,12 @@ struct gs_renderer {
             *sl.h_counters = gs::Counters{};
             HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&sl.h_params), sizeof(gs::FrameParams), hipHostMallocDefault));
         }
-        uint64_t want = std::max<uint64_t>(1u << 20, 8 * static_cast<uint64_t>(scene->n));
-        // test knob: start small so that the overflow / grow / re-run machinery is exercised by small scenes
-        if (const char* e = std::getenv("GS_INITIAL_CAPACITY")) want = std::max<uint64_t>(256, std::strtoull(e, nullptr, 10));
+        const uint64_t want = initial_capacity ? initial_capacity : std::max<uint64_t>(1u << 20, 8 * static_cast<uint64_t>(scene->n));
         capacity = static_cast<uint32_t>(std::min<uint64_t>(want, kMaxInstances));
         // candidates: E1 <= D always; ~1.5 per visible Gaussian with bins of 8 x 8 tiles, ~2 with 4 x 4 (config B 0.74 M, E 4.6 M, T 5.3 M)
         uint64_t want_cand = std::max<uint64_t>(1u << 18, 2 * static_cast<uint64_t>(scene->n));
-        if (const char* e = std::getenv("GS_INITIAL_CAND_CAPACITY")) want_cand = std::max<uint64_t>(256, std::strtoull(e, nullptr, 10));
-        else if (std::getenv("GS_INITIAL_CAPACITY")) want_cand = std::min<uint64_t>(want_cand, want);  // (the tests' small start applies to both)
+        if (initial_cand_capacity) want_cand = initial_cand_capacity;
+        else if (initial_capacity) want_cand = std::min<uint64_t>(want_cand, want);  // (the tests' small start applies to both)
         cand_capacity = static_cast<uint32_t>(std::min<uint64_t>(want_cand, capacity));
         default_cand_capacity = cand_capacity;
         sets[0].init(scene->n, capacity, cand_capacity, wants_dense_lists());
@@ -429,15 +416,9 @@ struct gs_renderer {
 
     // The renderer has no last frame (any more): the taps and the three passes refuse until a frame that is enqueued from here on
     // has retired.  `last`, what gs_get_stats reports, stays: the last frame that did retire.
-    void forget_last_frame() {
-        have_frame = false;
-        last_set = nullptr;
-        last_width = last_height = 0;
-        num_tiles = 0;
-        sorted_gid = depth_order = nullptr;
-        last_culled = false;
-    }
-    bool has_last_frame() const { return have_frame && last_set != nullptr; }
+    void forget_last_frame() { last_frame = LastFrame{}; }
+    // (... and has retired: nothing is queued, and a frame that leaves the queue without retiring takes the last frame with it)
+    bool has_last_frame() const { return last_frame.set != nullptr && pending == 0; }
 
     // ---- what a frame needs before it can be issued; asked before the wait of enqueue and again after it ----
     // buffers of the frame's set that a frame of `nt` tiles at depth-order level `lv` needs and the set does not have
@@ -484,60 +465,92 @@ struct gs_renderer {
         }
     }
 
+    // What the frame runs with, decided once.  The set and the renderer are made ready for it on the way, in the order these steps
+    // have always had: the set's missing buffers, the one growth of the candidate buffers, the tile table, this shape's tuner -- the
+    // decisions behind them (the one-pass level 1, its region capacity) see the candidate buffers as the frame will find them.
+    FramePlan plan_frame(const gs_uniforms& u, FrameBuffers& fb) {
+        FramePlan p;
+        p.width = u.width, p.height = u.height;
+        p.tx = tiles_across(u.width), p.ty = tiles_across(u.height), p.num_tiles = static_cast<uint64_t>(p.tx) * p.ty;
+        p.stamped = scene->n != 0 && u.width != 0 && u.height != 0;
+        p.level = policy.frame_level();
+        if (lacks_buffers(fb, p.num_tiles, p.level)) {
+            fb.ranges.ensure(2 * p.num_tiles);
+            if (p.level >= kGlobalLevel) fb.ensure_depth_order();
+            if (p.level == gs::kBinSlabLevel && !fb.slabs.p) {
+                fb.slabs.alloc(static_cast<size_t>(gs::kSlabCapacity) * gs::kSlabDescBytes);
+                HIP_CHECK(hipMemset(fb.slabs.p, 0, fb.slabs.n));  // no descriptor carries a launch's epoch yet
+            }
+        }
+        if (const uint32_t grow = l1_growth(u); grow > cand_capacity) set_cand_capacity(grow);
+        ensure_tile_order(p.tx, p.ty);
+        p.tune_shape = tuners.select(u.width, u.height);  // this frame shape's own tuner (a new shape measures afresh)
+        const BlendTuner& tuner = tuners.current();
+        p.lockstep = tuner.current(), p.tune_round = tuner.round;
+        p.geo = bin_geometry(p.tx, p.ty);
+        p.l1_fused = p.stamped && l1_verdict(u) == L1FusedPolicy::kEngage;
+        // the any-order level-1 kernels stream the dense list of visible Gaussians, which k_preprocess then writes beside the planes
+        // (the lists exist only for scenes of >= dense_min Gaussians: FrameBuffers::init; the blend zeroes their counters)
+        p.dense_list = p.l1_any_order() && !p.l1_fused && p.stamped && wants_dense_lists() && fb.vis.p;
+        p.l1_cap = L1FusedPolicy::region_cap(cand_capacity, p.geo.bins_x * p.geo.bins_y);
+        p.culled = tile_cull && p.l1_fused && p.level < gs::kBinSlabLevel;  // (the only frames that are: see tile_cull)
+        return p;
+    }
+
+    // What a frame's own level 2 and the rebuild of its reference lists (reference_lists) hand gs::BinLaunch alike: the grid, the
+    // capacities, the candidates with the counts and offsets of their bins, and the frame's own lists as the output.
+    gs::BinLaunch bin_launch(const FrameBuffers& fb, const FramePlan& p) const {
+        gs::BinLaunch b{};
+        b.n_bound = static_cast<uint32_t>(scene->n);
+        b.bin_count = fb.bin_count.p, b.cand = fb.cand.p;
+        b.ranges = fb.ranges.p, b.sorted_gid = fb.sorted.p, b.counters = fb.counters.p;
+        b.capacity = capacity, b.cand_capacity = cand_capacity;
+        b.tiles_x = p.tx, b.tiles_y = p.ty;
+        b.bins_x = p.geo.bins_x, b.bins_y = p.geo.bins_y;
+        b.bin_shift = p.geo.bin_shift, b.grid_shift = p.geo.grid_shift;
+        return b;
+    }
+
+    // What a captured frame was captured for: the plan and the renderer's settings its launches carry as arguments.
+    FrameBuffers::GraphKey graph_key(const FrameBuffers& fb, const FramePlan& p, const void* sh16) const {
+        FrameBuffers::GraphKey k;
+        k.level = p.level, k.bin_shift = p.geo.bin_shift, k.hw_exp = blend_exp_mode(), k.contract = contract ? 1 : 0;
+        k.antialiased = antialiased, k.lockstep = p.lockstep, k.l1_fused = p.l1_fused, k.tile_cull = tile_cull;
+        k.width = p.width, k.height = p.height, k.capacity = capacity, k.cand_capacity = cand_capacity;
+        k.tile_order = tile_order.p, k.ranges = fb.ranges.p, k.sh16 = sh16;
+        return k;
+    }
+
     // Part (3) of enqueue.  Nothing that is queued needs to retire in here (ensure_tile_order's own drain finds nothing queued).
     void issue(const gs_uniforms& u, float* d_rgba, uint8_t* d_bgra) {
         FrameSlot& sl = slots[frames_enqueued % kSlots];
         FrameBuffers& fb = sets[frames_enqueued % num_sets];
         hipStream_t stream = fb.stream;
         const uint32_t n = static_cast<uint32_t>(scene->n);
-        const uint32_t tx = tiles_across(u.width), ty = tiles_across(u.height);
-        const uint64_t nt = static_cast<uint64_t>(tx) * ty;
-        const bool fused_counters = n != 0 && u.width != 0 && u.height != 0;
-        const int lv = policy.frame_level();
-        if (lacks_buffers(fb, nt, lv)) {
-            fb.ranges.ensure(2 * nt);
-            if (lv >= kGlobalLevel) fb.ensure_depth_order();
-            if (lv == gs::kBinSlabLevel && !fb.slabs.p) {
-                fb.slabs.alloc(static_cast<size_t>(gs::kSlabCapacity) * gs::kSlabDescBytes);
-                HIP_CHECK(hipMemset(fb.slabs.p, 0, fb.slabs.n));  // no descriptor carries a launch's epoch yet
-            }
-        }
-        if (const uint32_t grow = l1_growth(u); grow > cand_capacity) set_cand_capacity(grow);
-        ensure_tile_order(tx, ty);
-        const int tune_shape = tuners.select(u.width, u.height);  // this frame shape's own tuner (a new shape measures afresh)
-        const BlendTuner& tuner = tuners.current();
-        const bool lockstep = tuner.current();
-        const BinGeometry geo = bin_geometry(tx, ty);
-        const bool bin_local = lv < kGlobalLevel;
+        const FramePlan plan = plan_frame(u, fb);
         lap(2);
 
         gs::SceneView sv{scene->render_blob(), scene->cov3d.p, n, static_cast<uint32_t>(gs::blob_stride(n)),
                           scene->sh_half ? scene->sh16.p : nullptr, scene->acut.p, scene->perm.p};
         gs::Counters* cnt = fb.counters.p;
-        // the level-1 kernels that take their items in any order (bin-local path, bins of <= 8 x 8 tiles) stream the dense
-        // list of visible Gaussians, which k_preprocess then writes beside the planes
-        const bool l1_any_order = bin_local && geo.bin_shift <= 3;
-        // (the lists exist only for scenes of >= dense_min Gaussians: FrameBuffers::init; the blend zeroes their counters)
-        const bool l1_fused = fused_counters && l1_verdict(u) == L1FusedPolicy::kEngage;
-        const bool dense_list = l1_any_order && !l1_fused && n != 0 && wants_dense_lists() && fb.vis.p && u.width != 0 && u.height != 0;
-        gs::AttrView av{fb.tiles.p, fb.depth.p, fb.aabb.p, fb.rec.p, dense_list ? fb.vis.p : nullptr, dense_list ? fb.vis_count.p : nullptr,
+        gs::AttrView av{fb.tiles.p, fb.depth.p, fb.aabb.p, fb.rec.p, plan.dense_list ? fb.vis.p : nullptr, plan.dense_list ? fb.vis_count.p : nullptr,
                         fb.vis_region_slots};
-        const uint32_t l1_cap = L1FusedPolicy::region_cap(cand_capacity, geo.bins_x * geo.bins_y);
-        const gs::L1Fused lf{l1_fused ? fb.l1_words.p : nullptr, fb.cand.p, l1_cap, fb.vis_mask.p, tx, ty, geo.bins_x, geo.bins_y, geo.bin_shift, geo.grid_shift};
-        fb.planes_stale = dense_list ? 1 : (l1_fused ? 2 : 0);
+        const gs::L1Fused lf{plan.l1_fused ? fb.l1_words.p : nullptr, fb.cand.p, plan.l1_cap, fb.vis_mask.p, plan.tx, plan.ty,
+                             plan.geo.bins_x, plan.geo.bins_y, plan.geo.bin_shift, plan.geo.grid_shift};
+        fb.planes_stale = plan.dense_list ? 1 : (plan.l1_fused ? 2 : 0);
 
         // the first and the last kernel of the frame clear / publish the counters themselves; the blit nodes (and
         // their fences) are only needed when one of the two is not launched
-        if (!fused_counters) {
+        if (!plan.stamped) {
             HIP_CHECK(hipMemsetAsync(cnt, 0, sizeof(gs::Counters), stream));
-            HIP_CHECK(hipMemsetAsync(fb.ranges.p, 0, 2 * nt * sizeof(uint32_t), stream));  // no Gaussians: every tile (0, 0)
+            HIP_CHECK(hipMemsetAsync(fb.ranges.p, 0, 2 * plan.num_tiles * sizeof(uint32_t), stream));  // no Gaussians: every tile (0, 0)
         }
         // the frame's launches; `fp` non-null = replayable form (per-frame values read from fb.params), no span events
         uint64_t* const stamps = fb.stamps.p;
         auto passes = [&](const gs::FrameParams* fp) {
             gs::launch_preprocess(sv, u, av, cnt, fp, stamps, antialiased, lf, stream);
             lap(3);
-            if (!bin_local && n != 0) {
+            if (!plan.bin_local() && n != 0) {
                 // ---- global depth order of the visible Gaussians: 4 x 8-bit stable passes on bits(depth) ----
                 const int blocks = std::max(1, std::min<int>(gs::kSortMaxBlocks, (n + gs::kSortTileKeys - 1) / gs::kSortTileKeys));
                 const uint32_t* kin = reinterpret_cast<const uint32_t*>(fb.depth.p);
@@ -567,10 +580,9 @@ struct gs_renderer {
             }
             lap(4);
             if (n != 0) {
-                gs::BinLaunch b{};
-                b.order = bin_local ? nullptr : fb.dvals[1].p;
-                b.n_items = bin_local ? nullptr : &cnt->visible;
-                b.n_bound = n;
+                gs::BinLaunch b = bin_launch(fb, plan);
+                b.order = plan.bin_local() ? nullptr : fb.dvals[1].p;
+                b.n_items = plan.bin_local() ? nullptr : &cnt->visible;
                 b.tiles = fb.tiles.p;
                 b.aabb = fb.aabb.p;
                 b.depth = fb.depth.p;
@@ -578,58 +590,42 @@ struct gs_renderer {
                 b.vis_count = av.vis_count;
                 b.vis_region_slots = av.vis_region_slots;
                 b.hist = fb.l1_hist.p;
-                b.bin_count = fb.bin_count.p;
-                b.cand = fb.cand.p;
-                b.ranges = fb.ranges.p;
-                b.sorted_gid = fb.sorted.p;
-                b.counters = cnt;
-                b.capacity = capacity;
-                b.cand_capacity = cand_capacity;
                 b.l1_fused_words = lf.words;
-                b.l1_fused_cap = l1_cap;
+                b.l1_fused_cap = plan.l1_cap;
                 b.reference_boxes = !tile_cull;
                 b.slabs = fb.slabs.p;
                 b.slab_capacity = fb.slabs.p ? gs::kSlabCapacity : 0u;
                 // level 4 as one launch over a queue of bins and slabs -- not in a captured frame (a replay repeats its arguments,
                 // and a descriptor is ready when it holds THIS launch's epoch); GS_L2_QUEUE=0: the two launches of round 4
                 b.slab_epoch = 0;
-                if (level2_queue && !fp && lv == gs::kBinSlabLevel) {
+                if (level2_queue && !fp && plan.level == gs::kBinSlabLevel) {
                     if (++fb.slab_epoch == 0) ++fb.slab_epoch;
                     b.slab_epoch = fb.slab_epoch;
                 }
-                b.tiles_x = tx;
-                b.tiles_y = ty;
-                b.bins_x = geo.bins_x;
-                b.bins_y = geo.bins_y;
-                b.bin_shift = geo.bin_shift;
-                b.grid_shift = geo.grid_shift;
                 b.stamps = stamps;
                 // ---- level 1: which Gaussian touches which bin (count + scan, then the per-bin candidate lists) ----
                 // (one pass: k_preprocess has filed the candidates; level 2 reads the bins' cursors)
-                if (!l1_fused) {
+                if (!plan.l1_fused) {
                     gs::launch_bin_level1_count(b, stream);
-                    gs::launch_bin_level1_scatter(b, l1_any_order, stream);
+                    gs::launch_bin_level1_scatter(b, plan.l1_any_order(), stream);
                 }
                 lap(5);
                 // ---- level 2: order inside the bin (bin-local path), tile ranges, per-tile lists ----
-                gs::launch_bin_level2(b, lv, stream);
+                gs::launch_bin_level2(b, plan.level, stream);
             }
             lap(6);
             // ---- blend ----
             gs::launch_blend(fb.ranges.p, fb.sorted.p, tile_order.p, av, u.width, u.height, d_rgba, d_bgra, cnt,
-                             fused_counters ? sl.h_counters : nullptr, blend_exp_mode(), contract, fp, lockstep, stamps, stream);
-            gs::launch_frame_end(stamps, sl.h_stamps, fp, lf.words, gs::kVisRegions + (1u << (2 * geo.grid_shift)), stream);
+                             plan.stamped ? sl.h_counters : nullptr, blend_exp_mode(), contract, fp, plan.lockstep, stamps, stream);
+            gs::launch_frame_end(stamps, sl.h_stamps, fp, lf.words, gs::kVisRegions + (1u << (2 * plan.geo.grid_shift)), stream);
             lap(7);
         };
-        const bool replay = graph_mode && fused_counters;
+        const bool replay = graph_mode && plan.stamped;
         if (replay) {
             *sl.h_params = gs::FrameParams{u, d_rgba, d_bgra, sl.h_counters, sl.h_stamps};
             HIP_CHECK(hipMemcpyAsync(fb.params.p, sl.h_params, sizeof(gs::FrameParams), hipMemcpyHostToDevice, stream));
-            const FrameBuffers::GraphKey key{lv, geo.bin_shift, blend_exp_mode(), contract ? 1 : 0,
-                                             antialiased, lockstep, l1_fused, tile_cull,
-                                             u.width, u.height, capacity, cand_capacity,
-                                             tile_order.p, fb.ranges.p, sv.sh16};
-            const int gi = lockstep ? 1 : 0;
+            const FrameBuffers::GraphKey key = graph_key(fb, plan, sv.sh16);
+            const int gi = plan.lockstep ? 1 : 0;
             if (!fb.graph_execs[gi] || !(key == fb.graph_keys[gi])) {  // first frame of this configuration: capture its launches
                 fb.drop_graph(gi);
                 hipGraph_t graph = nullptr;
@@ -651,34 +647,16 @@ struct gs_renderer {
         } else {
             passes(nullptr);
         }
-        if (!fused_counters) HIP_CHECK(hipMemcpyAsync(sl.h_counters, cnt, sizeof(gs::Counters), hipMemcpyDeviceToHost, stream));
+        if (!plan.stamped) HIP_CHECK(hipMemcpyAsync(sl.h_counters, cnt, sizeof(gs::Counters), hipMemcpyDeviceToHost, stream));
         HIP_CHECK(hipEventRecord(sl.done, stream));
         HIP_CHECK(hipGetLastError());
 
         // every launch has been issued: this is the last frame now
-        last_set = &fb;
-        last_width = u.width;
-        last_height = u.height;
-        num_tiles = nt;
-        last_l1_fused = l1_fused;
-        last_culled = frame_is_culled(l1_fused, lv);
-        last_level = lv;
-        last_geo = geo;
-        depth_order = bin_local ? nullptr : fb.dvals[1].p;
-        sorted_gid = fb.sorted.p;
+        last_frame = LastFrame{&fb, plan};
+        enqueued_l1_fused = plan.l1_fused;
 
-        sl.level = lv;
-        sl.bin_shift = geo.bin_shift;
-        sl.lockstep = lockstep;
-        sl.l1_fused = l1_fused;
-        sl.l1_cap = l1_cap;
-        sl.culled = frame_is_culled(l1_fused, lv);
-        sl.tune_round = tuner.round;
-        sl.tune_shape = tune_shape;
-        sl.u = u;
-        sl.rgba = d_rgba;
-        sl.bgra = d_bgra;
-        sl.timed = fused_counters;  // (a frame without Gaussians or pixels launches nothing that stamps)
+        sl.plan = plan;
+        sl.u = u, sl.rgba = d_rgba, sl.bgra = d_bgra;
         ++frames_enqueued;
         ++pending;
         lap(9);
@@ -697,11 +675,10 @@ struct gs_renderer {
             return;
         }
         redo_chain = 0;
-        policy.frame_retired(sl.level, sl.h_counters->max_bin, sl.bin_shift);
-        l1_policy.frame_retired(sl.u.width, sl.u.height, sl.bin_shift, sl.h_counters->max_bin, sl.h_counters->bin_entries, sl.h_counters->visible);
+        policy.frame_retired(sl.plan.level, sl.h_counters->max_bin, sl.plan.geo.bin_shift);
+        l1_policy.frame_retired(sl.u.width, sl.u.height, sl.plan.geo.bin_shift, sl.h_counters->max_bin, sl.h_counters->bin_entries, sl.h_counters->visible);
         last = frame_stats(sl);
-        last_listed = sl.culled ? sl.h_counters->listed : sl.h_counters->instances;
-        have_frame = true;
+        last_frame.listed = sl.plan.culled ? sl.h_counters->listed : sl.h_counters->instances;
         const float v[7] = {last.ms_preprocess, last.ms_prefix_sum, last.ms_preprocess_sort, last.ms_sort,
                             last.ms_tile_boundary, last.ms_render, last.ms_total};
         for (int k = 0; k < 7; ++k) total_ms[k] += v[k];
@@ -728,9 +705,9 @@ struct gs_renderer {
             const FrameSlot& q = queued(k);
             const gs::Counters& c = *q.h_counters;
             redo.push_back({q.u, q.rgba, q.bgra});
-            ran.push_back({q.level, q.bin_shift, q.u.width, q.u.height, c.overflow, c.max_bin});
+            ran.push_back({q.plan.level, q.plan.geo.bin_shift, q.u.width, q.u.height, c.overflow, c.max_bin});
             // the one-pass level 1: a bin's region ran over (its cursor ended beyond it) -- the frames re-run on the three kernels
-            if (q.l1_fused && (c.overflow & 1u) && c.max_bin > q.l1_cap) l1_policy.region_overflowed();
+            if (q.plan.l1_fused && (c.overflow & 1u) && c.max_bin > q.plan.l1_cap) l1_policy.region_overflowed();
             if (c.overflow & 1u) {
                 // which of the two ran over: the level-1 candidates (E1: the frame's instance count then means nothing -- its
                 // bins were skipped) or the per-tile lists (D)
@@ -774,25 +751,26 @@ struct gs_renderer {
 
     void report_overflow() {  // GS_DEBUG_LEVELS: what made the renderer change its depth-order level
         std::fprintf(stderr, "[gs3d] frame %llu overflowed at level %d (refined %d, hold %u):", (unsigned long long)(frames_enqueued - pending),
-                     oldest().level, (int)policy.refined, policy.slab_hold);
+                     oldest().plan.level, (int)policy.refined, policy.slab_hold);
         for (int k = 0; k < pending; ++k) {
             const FrameSlot& q = queued(k);
-            std::fprintf(stderr, " [lvl %d bin 2^%d ovf %u max_bin %u E1 %u D %u slabs %u]", q.level, q.bin_shift, q.h_counters->overflow,
+            std::fprintf(stderr, " [lvl %d bin 2^%d ovf %u max_bin %u E1 %u D %u slabs %u]", q.plan.level, q.plan.geo.bin_shift, q.h_counters->overflow,
                          q.h_counters->max_bin, q.h_counters->bin_entries, q.h_counters->instances, q.h_counters->slabs);
         }
         std::fprintf(stderr, " capacity %u candidates %u\n", capacity, cand_capacity);
     }
 
     gs_frame_stats frame_stats(const FrameSlot& sl) const {
+        const FramePlan& p = sl.plan;
         gs_frame_stats st{};
         st.num_gaussians = scene->n;
         st.num_visible = sl.h_counters->visible;
         st.num_instances = sl.h_counters->instances;
         st.num_bin_entries = sl.h_counters->bin_entries;
         st.max_bin_entries = sl.h_counters->max_bin;
-        st.sort_path = sl.level < kGlobalLevel ? 2u : 1u;
-        st.sort_level = static_cast<uint32_t>(sl.level);
-        st.bin_tiles = 1u << sl.bin_shift;
+        st.sort_path = p.bin_local() ? 2u : 1u;
+        st.sort_level = static_cast<uint32_t>(p.level);
+        st.bin_tiles = 1u << p.geo.bin_shift;
         st.instance_capacity = capacity;
         // The frame's timeline as its kernels stamped it (gs_kernels.h: FrameStamp), in ticks of the device's constant-rate clock: a
         // span runs from the start of a pass's first kernel to the start of the next pass's -- the seam behind a pass belongs to it.
@@ -801,17 +779,17 @@ struct gs_renderer {
             const int64_t d = static_cast<int64_t>(ts[b] - ts[a]);
             return d > 0 ? static_cast<float>(static_cast<double>(d) * tick_ms) : 0.0f;
         };
-        if (sl.timed) st.ms_total = span(gs::ST_PREPROCESS, gs::ST_END);
-        if (sl.timed && timing) {
+        if (p.stamped) st.ms_total = span(gs::ST_PREPROCESS, gs::ST_END);
+        if (p.stamped && timing) {
             // The reference's six span names (Renderer.cpp:484-526, 580-699).  prefix_sum = the level-1 count + scan,
             // preprocess_sort = the level-1 scatter (what lands where), sort = the global depth order (when taken) +
             // k_bin_build.  k_bin_build also produces the tile ranges: tile_boundary.comp's work has no kernel of
             // its own any more, so that span is 0 by construction.
-            const bool global = sl.level >= kGlobalLevel;  // (only then is ST_ORDER this frame's)
+            const bool global = !p.bin_local();  // (only then is ST_ORDER this frame's)
             // (one-pass level 1: no level-1 kernel stamped -- the pass is part of k_preprocess, and its two spans are 0)
-            st.ms_preprocess = span(gs::ST_PREPROCESS, global ? gs::ST_ORDER : (sl.l1_fused ? gs::ST_L2 : gs::ST_L1_COUNT));
-            st.ms_prefix_sum = sl.l1_fused ? 0.0f : span(gs::ST_L1_COUNT, gs::ST_L1_SCATTER);
-            st.ms_preprocess_sort = sl.l1_fused ? 0.0f : span(gs::ST_L1_SCATTER, gs::ST_L2);
+            st.ms_preprocess = span(gs::ST_PREPROCESS, global ? gs::ST_ORDER : (p.l1_fused ? gs::ST_L2 : gs::ST_L1_COUNT));
+            st.ms_prefix_sum = p.l1_fused ? 0.0f : span(gs::ST_L1_COUNT, gs::ST_L1_SCATTER);
+            st.ms_preprocess_sort = p.l1_fused ? 0.0f : span(gs::ST_L1_SCATTER, gs::ST_L2);
             st.ms_sort = (global ? span(gs::ST_ORDER, gs::ST_L1_COUNT) : 0.0f) + span(gs::ST_L2, gs::ST_BLEND);
             st.ms_tile_boundary = 0.0f;
             st.ms_render = span(gs::ST_BLEND, gs::ST_END);
@@ -831,7 +809,7 @@ struct gs_renderer {
             if (intervals.size() >= kIntervalRing) intervals.erase(intervals.begin(), intervals.begin() + kIntervalRing / 2);
             intervals.push_back(dt);
             // the blend tuner compares completion rates (or, for a host-paced consumer, the frames' own spans: BlendTuner::cost)
-            tuners.sample(sl.tune_shape, sl.u.width, sl.u.height, dt, ms_total, sl.lockstep, sl.tune_round);
+            tuners.sample(sl.plan.tune_shape, sl.u.width, sl.u.height, dt, ms_total, sl.plan.lockstep, sl.plan.tune_round);
             if (dt > 0.0f) latest_done = idx;
         } else {
             latest_done = idx;
@@ -857,18 +835,121 @@ struct gs_renderer {
 
     // What the passes over the last frame's tile lists do after their own argument checks (gs_accumulate_contributions,
     // gs_blend_features, gs_lift_pixels), in this order: queued frames retire (an overflowed one is re-run: the lists are the last
-    // frame's, complete); without a frame the call is refused; with nothing asked for it is done; otherwise launch(fb) enqueues
-    // the pass on the last frame's stream and the call waits for it.
+    // frame's, complete); without a frame the call is refused; with nothing asked for it is done; otherwise launch(lists, stream)
+    // enqueues the pass over the frame's own lists on the last frame's stream and the call waits for it.
     template <class Launch>
     void over_last_frame(bool nothing_asked, Launch&& launch) {
         drain();
         if (!has_last_frame()) throw Error(GS_ERR_INVALID, "no frame rendered yet");
         if (nothing_asked) return;
         HIP_CHECK(hipSetDevice(scene->device));
-        const FrameBuffers& fb = *last_set;
-        launch(fb);
+        const FrameBuffers& fb = *last_frame.set;
+        launch(gs::TileLists{fb.ranges.p, fb.sorted.p, tile_order.p, fb.rec.p, last_frame.plan.width, last_frame.plan.height}, fb.stream);
         HIP_CHECK(hipGetLastError());
         fb.sync();
+    }
+
+    // ---- the stage taps of the last frame (gs_debug_download, which has drained and found a last frame) ----
+    // The reference's lists of the last frame.  An unculled frame's own lists are those.  For a culled one: level 2 once more over that
+    // frame's candidate records with BinLaunch::reference_boxes, into buffers and counters of the taps' own, which the renderer keeps
+    // across frames; whether they hold the last frame's lists is LastFrame::tap_lists.  Nothing of the frame moves.
+    DevBuf<uint32_t> tap_ranges, tap_sorted;
+    DevBuf<gs::Counters> tap_counters;
+    using Lists = std::pair<const uint32_t*, const uint32_t*>;  // (ranges, lists)
+    Lists reference_lists() {
+        LastFrame& lf = last_frame;
+        FrameBuffers& fb = *lf.set;
+        if (!lf.plan.culled) return {fb.ranges.p, fb.sorted.p};
+        if (!lf.tap_lists) {
+            tap_ranges.ensure(2 * lf.plan.num_tiles);
+            tap_sorted.ensure(static_cast<size_t>(capacity) + 4);
+            tap_counters.ensure(1);
+            HIP_CHECK(hipMemsetAsync(tap_counters.p, 0, sizeof(gs::Counters), fb.stream));
+            // l1_fused_words stays null: level 2 reads the counts and offsets the frame's bin workgroups left in bin_count
+            // (BuildArgs::bin_count_save); stamps stays null: the frame's timeline is the frame's
+            gs::BinLaunch b = bin_launch(fb, lf.plan);
+            b.ranges = tap_ranges.p, b.sorted_gid = tap_sorted.p, b.counters = tap_counters.p;
+            b.reference_boxes = true;
+            gs::launch_bin_level2(b, lf.plan.level, fb.stream);
+            HIP_CHECK(hipGetLastError());
+            gs::Counters c{};
+            HIP_CHECK(hipMemcpyAsync(&c, tap_counters.p, sizeof c, hipMemcpyDeviceToHost, fb.stream));
+            HIP_CHECK(hipStreamSynchronize(fb.stream));
+            if (c.overflow != 0 || c.instances != last.num_instances)
+                throw Error(GS_ERR_DEVICE, "the reference lists of a culled frame do not add up to the frame's instance count");
+            lf.tap_lists = true;
+        }
+        return {tap_ranges.p, tap_sorted.p};
+    }
+
+    // tiles / depth / aabb of a frame that wrote no per-Gaussian planes, rebuilt on the first tap that asks for one of them
+    void rebuild_planes() {
+        FrameBuffers& fb = *last_frame.set;
+        if (!fb.planes_stale) return;
+        const gs::AttrView pv{fb.tiles.p, fb.depth.p, fb.aabb.p, fb.rec.p, fb.vis.p, fb.vis_count.p, fb.vis_region_slots};
+        // the frame streamed the dense lists of visible Gaussians: from the lists
+        if (fb.planes_stale == 1) gs::launch_vis_to_planes(pv, static_cast<uint32_t>(scene->n), fb.stream);
+        // (... or took the one-pass level 1: from its visibility bits and the records)
+        else gs::launch_records_to_planes(fb.vis_mask.p, scene->perm.p, pv, static_cast<uint32_t>(scene->n), last_frame.plan.width, last_frame.plan.height, fb.stream);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipStreamSynchronize(fb.stream));
+        fb.planes_stale = 0;
+    }
+
+    // fields of the 64-byte attribute records (only the visible Gaussians' records are written: the rest
+    // of the tap is whatever an earlier frame left, like the reference's VertexAttribute buffer)
+    void tap_record_field(int stage, void* dst, uint64_t bytes) {
+        const uint64_t n = scene->n;
+        const size_t width = stage == GS_STAGE_RADIUS || stage == GS_STAGE_B || stage == GS_STAGE_ALPHA_CUT ? 1 : 4;
+        if (bytes < n * width * 4) throw Error(GS_ERR_INVALID, "destination too small for stage buffer");
+        std::vector<gs::AttrRecord> recs(n);
+        if (n) HIP_CHECK(hipMemcpy(recs.data(), last_frame.set->rec.p, n * sizeof(gs::AttrRecord), hipMemcpyDeviceToHost));
+        float* out = static_cast<float*>(dst);
+        for (uint64_t i = 0; i < n; ++i) {
+            const gs::AttrRecord& a = recs[i];
+            if (stage == GS_STAGE_RADIUS) out[i] = a.depth_radius.y;
+            else if (stage == GS_STAGE_B) out[i] = a.b_cut_r.x;
+            else if (stage == GS_STAGE_ALPHA_CUT) out[i] = a.b_cut_r.y;
+            else std::memcpy(out + 4 * i, stage == GS_STAGE_CONIC_OPACITY ? &a.conic_op : &a.uv_rg, 16);
+        }
+    }
+
+    // The per-tile lists are stored bin-major (the tiles of a bin consecutive, the bins wherever their workgroup's atomic add put
+    // them); `ranges` holds each tile's (start, end) in that buffer.  The reference's buffers are the same lists laid end to end in
+    // tile order: the taps present them so.  (The _CULLED pair: the frame's own lists, as the blend walked them; the others: the
+    // reference's lists, made once more from the reference boxes where the frame's are culled.)
+    void tap_lists(int stage, void* dst, uint64_t bytes) {
+        const bool own = stage == GS_STAGE_LISTS_CULLED || stage == GS_STAGE_RANGES_CULLED;
+        const auto [ranges_src, lists_src] = own ? Lists{last_frame.set->ranges.p, last_frame.set->sorted.p} : reference_lists();
+        const uint64_t d = std::min<uint64_t>(own ? last_frame.listed : last.num_instances, capacity);
+        if (stage == GS_STAGE_RANGES_CULLED) stage = GS_STAGE_RANGES;
+        if (stage == GS_STAGE_LISTS_CULLED) stage = GS_STAGE_SORTED_GID;
+        const uint64_t nt = last_frame.plan.num_tiles;
+        std::vector<uint32_t> rg(2 * nt);
+        if (nt) HIP_CHECK(hipMemcpy(rg.data(), ranges_src, rg.size() * 4, hipMemcpyDeviceToHost));
+        if (stage == GS_STAGE_RANGES) {
+            if (bytes < nt * 8) throw Error(GS_ERR_INVALID, "destination too small for stage buffer");
+            uint32_t* out = static_cast<uint32_t*>(dst);
+            uint64_t pos = 0;
+            for (uint64_t t = 0; t < nt; ++t) {
+                const uint32_t len = rg[2 * t + 1] - rg[2 * t];
+                out[2 * t] = len ? static_cast<uint32_t>(pos) : 0u;  // tile_boundary.comp leaves absent tiles (0, 0)
+                out[2 * t + 1] = len ? static_cast<uint32_t>(pos + len) : 0u;
+                pos += len;
+            }
+            return;
+        }
+        if (bytes < d * 4) throw Error(GS_ERR_INVALID, "destination too small for stage buffer");
+        std::vector<uint32_t> lists;
+        if (stage == GS_STAGE_SORTED_GID) {
+            lists.resize(capacity);
+            HIP_CHECK(hipMemcpy(lists.data(), lists_src, lists.size() * 4, hipMemcpyDeviceToHost));
+        }
+        uint32_t* out = static_cast<uint32_t*>(dst);
+        uint64_t pos = 0;
+        for (uint64_t t = 0; t < nt; ++t)
+            for (uint64_t i = rg[2 * t]; i < rg[2 * t + 1] && pos < d; ++i)
+                out[pos++] = stage == GS_STAGE_SORTED_GID ? lists[i] : static_cast<uint32_t>(t);
     }
 };
 
@@ -882,19 +963,8 @@ int gs_renderer_create(gs_scene* scene, gs_renderer** out) {
         if (!scene || !out) throw Error(GS_ERR_INVALID, "null argument");
         auto r = std::make_unique<gs_renderer>();
         r->scene = scene;
-        if (const char* e = std::getenv("GS_L1_DENSE_MIN")) r->dense_min = std::strtoull(e, nullptr, 10);  // (before init: sizes the buffer sets)
+        r->read_environment();  // (before init: GS_L1_DENSE_MIN sizes the buffer sets)
         r->init();
-        if (const char* e = std::getenv("GS_L1_FUSED")) r->l1_policy.mode = std::atoi(e) < 0 ? -1 : (std::atoi(e) != 0 ? 1 : 0);  // initial gs_set_level1_fused
-        if (const char* e = std::getenv("GS_GRAPH")) r->graph_mode = std::atoi(e) != 0;  // initial gs_set_graph_mode
-        if (const char* e = std::getenv("GS_EXP_MODE")) r->exp_mode = std::min(3, std::max(0, std::atoi(e)));  // initial gs_set_exp_mode
-        if (const char* e = std::getenv("GS_BLEND_CONTRACTION")) r->contract = std::atoi(e) != 0;  // initial gs_set_blend_contraction
-        if (const char* e = std::getenv("GS_ANTIALIASED")) r->antialiased = std::atoi(e) != 0;  // initial gs_set_antialiased
-        if (const char* e = std::getenv("GS_BIN_SHIFT")) r->policy.min_bin_shift = std::min(5, std::max(2, std::atoi(e)));  // default bin edge
-        if (const char* e = std::getenv("GS_SORT_PATH")) {  // initial gs_set_sort_path, for hosts that cannot call it (the viewer)
-            const int mode = std::atoi(e);
-            if (mode < 0 || mode > 2) throw Error(GS_ERR_INVALID, "GS_SORT_PATH must be 0 (auto), 1 (global) or 2 (bin-local)");
-            r->policy.sort_mode = mode;
-        }
         *out = r.release();
     });
 }
@@ -971,9 +1041,9 @@ int gs_get_stats(gs_renderer* r, gs_frame_stats* out) {
         r->drain();
         r->latest_stats(out);
         // written by the blend itself, after it published the other counters: read from the device (everything has retired)
-        if (r->has_last_frame() && r->last_set->counters.p) {
+        if (r->has_last_frame() && r->last_frame.set->counters.p) {
             gs::Counters c{};
-            HIP_CHECK(hipMemcpy(&c, r->last_set->counters.p, sizeof c, hipMemcpyDeviceToHost));
+            HIP_CHECK(hipMemcpy(&c, r->last_frame.set->counters.p, sizeof c, hipMemcpyDeviceToHost));
             out->blend_redo = c.blend_redo;
             out->blend_resolved = c.blend_resolved;
         }
@@ -1106,7 +1176,7 @@ int gs_get_level1_fused(gs_renderer* r) {
     int on = 0;
     const int rc = guarded([&] {
         if (!r) throw Error(GS_ERR_INVALID, "null argument");
-        on = r->last_l1_fused ? 1 : 0;  // (the most recently enqueued frame)
+        on = r->enqueued_l1_fused ? 1 : 0;  // (the most recently enqueued frame)
     });
     return rc != 0 ? rc : on;
 }
@@ -1124,7 +1194,7 @@ int gs_get_tile_cull(gs_renderer* r, int* last_frame_culled) {
     const int rc = guarded([&] {
         if (!r) throw Error(GS_ERR_INVALID, "null argument");
         on = r->tile_cull ? 1 : 0;
-        if (last_frame_culled) *last_frame_culled = r->last_set != nullptr && r->last_culled ? 1 : 0;  // (the most recently enqueued frame)
+        if (last_frame_culled) *last_frame_culled = r->last_frame.set != nullptr && r->last_frame.plan.culled ? 1 : 0;  // (the most recently enqueued frame)
     });
     return rc != 0 ? rc : on;
 }
@@ -1134,7 +1204,7 @@ int gs_get_listed_instances(gs_renderer* r, uint64_t* out) {
         if (!r || !out) throw Error(GS_ERR_INVALID, "null argument");
         r->drain();
         if (!r->has_last_frame()) throw Error(GS_ERR_INVALID, "no frame rendered yet");
-        *out = r->last_listed;
+        *out = r->last_frame.listed;
     });
 }
 
@@ -1153,100 +1223,33 @@ int gs_debug_download(gs_renderer* r, int stage, void* dst, uint64_t bytes) {
         if (!r || !dst) throw Error(GS_ERR_INVALID, "null argument");
         r->drain();
         if (!r->has_last_frame()) throw Error(GS_ERR_INVALID, "no frame rendered yet");
-        if (stage == GS_STAGE_DEPTH_ORDER && !r->depth_order)
+        const FrameBuffers& fb = *r->last_frame.set;
+        if (stage == GS_STAGE_DEPTH_ORDER && r->last_frame.plan.bin_local())
             throw Error(GS_ERR_INVALID, "the depth-order tap exists only on the global depth-order path (gs_set_sort_path(r, 1))");
-        const uint64_t n = r->scene->n, v = r->last.num_visible;
-        const uint64_t d = std::min<uint64_t>(r->last.num_instances, r->capacity), d_ref = d;
+        const uint64_t n = r->scene->n;
         const void* src = nullptr;
         uint64_t size = 0;
-        if (r->last_set->planes_stale && (stage == GS_STAGE_TILES || stage == GS_STAGE_DEPTH || stage == GS_STAGE_AABB)) {
-            // the frame streamed the dense lists of visible Gaussians and wrote no per-Gaussian planes: rebuild them from the lists
-            FrameBuffers& fb = *r->last_set;
-            const gs::AttrView pv{fb.tiles.p, fb.depth.p, fb.aabb.p, fb.rec.p, fb.vis.p, fb.vis_count.p, fb.vis_region_slots};
-            if (fb.planes_stale == 1) gs::launch_vis_to_planes(pv, static_cast<uint32_t>(n), fb.stream);
-            // (... or took the one-pass level 1: from its visibility bits and the records)
-            else gs::launch_records_to_planes(fb.vis_mask.p, r->scene->perm.p, pv, static_cast<uint32_t>(n), r->last_width, r->last_height, fb.stream);
-            HIP_CHECK(hipGetLastError());
-            HIP_CHECK(hipStreamSynchronize(fb.stream));
-            fb.planes_stale = 0;
-        }
         switch (stage) {
-            case GS_STAGE_TILES: src = r->last_set->tiles.p; size = n * 4; break;
-            case GS_STAGE_DEPTH: src = r->last_set->depth.p; size = n * 4; break;
+            case GS_STAGE_TILES: r->rebuild_planes(); src = fb.tiles.p; size = n * 4; break;
+            case GS_STAGE_DEPTH: r->rebuild_planes(); src = fb.depth.p; size = n * 4; break;
+            case GS_STAGE_AABB: r->rebuild_planes(); src = fb.aabb.p; size = n * 8; break;
             case GS_STAGE_RADIUS:
             case GS_STAGE_CONIC_OPACITY:
             case GS_STAGE_UV_RG:
             case GS_STAGE_B:
-            case GS_STAGE_ALPHA_CUT:
-                {   // fields of the 64-byte attribute records (only the visible Gaussians' records are written: the rest
-                    // of the tap is whatever an earlier frame left, like the reference's VertexAttribute buffer)
-                    const size_t width = stage == GS_STAGE_RADIUS || stage == GS_STAGE_B || stage == GS_STAGE_ALPHA_CUT ? 1 : 4;
-                    if (bytes < n * width * 4) throw Error(GS_ERR_INVALID, "destination too small for stage buffer");
-                    std::vector<gs::AttrRecord> recs(n);
-                    if (n) HIP_CHECK(hipMemcpy(recs.data(), r->last_set->rec.p, n * sizeof(gs::AttrRecord), hipMemcpyDeviceToHost));
-                    float* out = static_cast<float*>(dst);
-                    for (uint64_t i = 0; i < n; ++i) {
-                        const gs::AttrRecord& a = recs[i];
-                        if (stage == GS_STAGE_RADIUS) out[i] = a.depth_radius.y;
-                        else if (stage == GS_STAGE_B) out[i] = a.b_cut_r.x;
-                        else if (stage == GS_STAGE_ALPHA_CUT) out[i] = a.b_cut_r.y;
-                        else std::memcpy(out + 4 * i, stage == GS_STAGE_CONIC_OPACITY ? &a.conic_op : &a.uv_rg, 16);
-                    }
-                    return;
-                }
-            case GS_STAGE_AABB: src = r->last_set->aabb.p; size = n * 8; break;
-            case GS_STAGE_DEPTH_ORDER: src = r->depth_order; size = v * 4; break;
+            case GS_STAGE_ALPHA_CUT: r->tap_record_field(stage, dst, bytes); return;
+            case GS_STAGE_DEPTH_ORDER: src = fb.dvals[1].p; size = static_cast<uint64_t>(r->last.num_visible) * 4; break;
             case GS_STAGE_SORTED_TILE:
             case GS_STAGE_SORTED_GID:
             case GS_STAGE_RANGES:
             case GS_STAGE_LISTS_CULLED:
-            case GS_STAGE_RANGES_CULLED:
-                {   // The per-tile lists are stored bin-major (the tiles of a bin consecutive, the bins wherever their
-                    // workgroup's atomic add put them); `ranges` holds each tile's (start, end) in that buffer.  The
-                    // reference's buffers are the same lists laid end to end in tile order: the taps present them so.
-                    // (The _CULLED pair: the frame's own lists, as the blend walked them; the others: the reference's lists,
-                    // made once more from the reference boxes where the frame's are culled.)
-                    const bool own = stage == GS_STAGE_LISTS_CULLED || stage == GS_STAGE_RANGES_CULLED;
-                    const uint32_t *ranges_src = r->last_set->ranges.p, *lists_src = r->sorted_gid;
-                    if (!own) r->reference_lists(&ranges_src, &lists_src);
-                    const uint64_t d = own ? std::min<uint64_t>(r->last_listed, r->capacity) : d_ref;
-                    if (stage == GS_STAGE_RANGES_CULLED) stage = GS_STAGE_RANGES;
-                    if (stage == GS_STAGE_LISTS_CULLED) stage = GS_STAGE_SORTED_GID;
-                    const uint64_t nt = r->num_tiles;
-                    std::vector<uint32_t> rg(2 * nt);
-                    if (nt) HIP_CHECK(hipMemcpy(rg.data(), ranges_src, rg.size() * 4, hipMemcpyDeviceToHost));
-                    if (stage == GS_STAGE_RANGES) {
-                        if (bytes < nt * 8) throw Error(GS_ERR_INVALID, "destination too small for stage buffer");
-                        uint32_t* out = static_cast<uint32_t*>(dst);
-                        uint64_t pos = 0;
-                        for (uint64_t t = 0; t < nt; ++t) {
-                            const uint32_t len = rg[2 * t + 1] - rg[2 * t];
-                            out[2 * t] = len ? static_cast<uint32_t>(pos) : 0u;  // tile_boundary.comp leaves absent tiles (0, 0)
-                            out[2 * t + 1] = len ? static_cast<uint32_t>(pos + len) : 0u;
-                            pos += len;
-                        }
-                        return;
-                    }
-                    if (bytes < d * 4) throw Error(GS_ERR_INVALID, "destination too small for stage buffer");
-                    std::vector<uint32_t> lists;
-                    if (stage == GS_STAGE_SORTED_GID) {
-                        lists.resize(r->capacity);
-                        HIP_CHECK(hipMemcpy(lists.data(), lists_src, lists.size() * 4, hipMemcpyDeviceToHost));
-                    }
-                    uint32_t* out = static_cast<uint32_t*>(dst);
-                    uint64_t pos = 0;
-                    for (uint64_t t = 0; t < nt; ++t)
-                        for (uint64_t i = rg[2 * t]; i < rg[2 * t + 1] && pos < d; ++i)
-                            out[pos++] = stage == GS_STAGE_SORTED_GID ? lists[i] : static_cast<uint32_t>(t);
-                    return;
-                }
+            case GS_STAGE_RANGES_CULLED: r->tap_lists(stage, dst, bytes); return;
             case GS_STAGE_LISTS_RAW:
             case GS_STAGE_RANGES_RAW:
                 {
-                    const uint32_t *ranges_src = nullptr, *lists_src = nullptr;
-                    r->reference_lists(&ranges_src, &lists_src);
-                    if (stage == GS_STAGE_LISTS_RAW) src = lists_src, size = d * 4;
-                    else src = ranges_src, size = r->num_tiles * 8;
+                    const auto [ranges_src, lists_src] = r->reference_lists();
+                    if (stage == GS_STAGE_LISTS_RAW) src = lists_src, size = std::min<uint64_t>(r->last.num_instances, r->capacity) * 4;
+                    else src = ranges_src, size = r->last_frame.plan.num_tiles * 8;
                     break;
                 }
             default: throw Error(GS_ERR_INVALID, "unknown stage");
@@ -1263,9 +1266,8 @@ int gs_accumulate_contributions(gs_renderer* r, const gs_contributions* c) {
         if (reinterpret_cast<uintptr_t>(c->weight) % 8 != 0) throw Error(GS_ERR_INVALID, "weight must be 8-byte aligned");
         if (reinterpret_cast<uintptr_t>(c->pixels) % 4 != 0) throw Error(GS_ERR_INVALID, "pixels must be 4-byte aligned");
         if (reinterpret_cast<uintptr_t>(c->top_id) % 4 != 0) throw Error(GS_ERR_INVALID, "top_id must be 4-byte aligned");
-        r->over_last_frame(!c->weight && !c->pixels && !c->top_id, [&](const FrameBuffers& fb) {
-            gs::launch_contributions(fb.ranges.p, fb.sorted.p, r->tile_order.p, fb.rec.p, r->last_width, r->last_height, c->mask,
-                                     c->weight, c->pixels, c->top_id, fb.stream);
+        r->over_last_frame(!c->weight && !c->pixels && !c->top_id, [&](const gs::TileLists& lists, hipStream_t s) {
+            gs::launch_contributions(lists, c->mask, c->weight, c->pixels, c->top_id, s);
         });
     });
 }
@@ -1284,9 +1286,8 @@ int gs_blend_features(gs_renderer* r, const gs_feature_maps* m) {
         for (const auto& q : ptrs)
             if (reinterpret_cast<uintptr_t>(q.p) % 4 != 0) throw Error(GS_ERR_INVALID, q.what);
         float* out_features = m->channels > 0 ? m->out_features : nullptr;  // channels == 0: that output is not touched
-        r->over_last_frame(!out_features && !m->out_alpha && !m->out_depth && !m->out_depth_median, [&](const FrameBuffers& fb) {
-            gs::launch_features(fb.ranges.p, fb.sorted.p, r->tile_order.p, fb.rec.p, r->last_width, r->last_height, m->features,
-                                m->channels, out_features, m->out_alpha, m->out_depth, m->out_depth_median, fb.stream);
+        r->over_last_frame(!out_features && !m->out_alpha && !m->out_depth && !m->out_depth_median, [&](const gs::TileLists& lists, hipStream_t s) {
+            gs::launch_features(lists, m->features, m->channels, out_features, m->out_alpha, m->out_depth, m->out_depth_median, s);
         });
     });
 }
@@ -1302,9 +1303,8 @@ int gs_lift_pixels(gs_renderer* r, const gs_pixel_lift* l) {
         if (reinterpret_cast<uintptr_t>(l->out) % 8 != 0) throw Error(GS_ERR_INVALID, "out must be 8-byte aligned");
         if (reinterpret_cast<uintptr_t>(l->out_weight) % 8 != 0) throw Error(GS_ERR_INVALID, "out_weight must be 8-byte aligned");
         double* out = l->channels > 0 ? l->out : nullptr;  // channels == 0: that output is not touched
-        r->over_last_frame(!out && !l->out_weight, [&](const FrameBuffers& fb) {
-            gs::launch_lift(fb.ranges.p, fb.sorted.p, r->tile_order.p, fb.rec.p, r->last_width, r->last_height, l->mask, l->values,
-                            l->channels, out, l->out_weight, fb.stream);
+        r->over_last_frame(!out && !l->out_weight, [&](const gs::TileLists& lists, hipStream_t s) {
+            gs::launch_lift(lists, l->mask, l->values, l->channels, out, l->out_weight, s);
         });
     });
 }

@@ -6,7 +6,8 @@ A REFUSED call changes nothing (test_a_refused_call_changes_nothing).  The four 
 beyond 16 bits), 16400 x 64 (beyond the binning), null uniforms -- through gs_render and gs_render_host, after a frame of each
 form (three-kernel level 1 over the planes, dense lists, one-pass level 1 whose plane taps are rebuilt from the records, the
 global path with its depth_order tap, a slab frame), with one buffer set, with three, and under graph replay.  "Unchanged" is a
-self-comparison of the same renderer across the call: every stage tap (the raw lists and ranges too), the contributions
+self-comparison of the same renderer across the call: every stage tap (the raw lists and ranges and the frame's own, culled
+or not, too), level1_fused(), tile_cull() and listed_instances(), the contributions
 (weight, pixels, top id) and the feature maps (5 channels, alpha, both depths) bit for bit, the stats field for field.  The lift
 is not bit-reproducible by its definition: with non-negative values both results for a Gaussian with n terms lie within
 (n - 1) 2^-53 S of the exact sum S of its terms (gs_lift.hip's header), so they differ by at most
@@ -49,7 +50,7 @@ GUARD, SENTINEL = 37, -7777                           # guard words around the i
 CHANNELS, LIFT_CHANNELS = 5, 2
 NO_FRAME = "no frame rendered yet"
 ALL_TAPS = ("tiles", "depth", "radius", "aabb", "conic_opacity", "uv_rg", "b", "alpha_cut", "sorted_tile", "sorted_gid", "ranges",
-            "lists_raw", "ranges_raw")
+            "lists_raw", "ranges_raw", "lists_culled", "ranges_culled")   # (the _culled pair of an unculled frame: its own lists)
 _frames = {}
 
 
@@ -128,11 +129,13 @@ def _snapshot(rend, u, n, feats, vals):
     exact = {name: counts.get(name) for name in counts.t}
     exact.update({f"map {name}": maps.get(name) for name in maps.t})
     lift = {name: sums.get(name) for name in sums.t}
-    return dict(stats=st, taps=taps, exact=exact, lift=lift)
+    getters = dict(level1_fused=rend.level1_fused(), tile_cull=rend.tile_cull(), listed_instances=rend.listed_instances())
+    return dict(stats=st, getters=getters, taps=taps, exact=exact, lift=lift)
 
 
 def _assert_unchanged(before, after, label):
     assert after["stats"] == before["stats"], f"{label}: stats changed: {before['stats']} -> {after['stats']}"
+    assert after["getters"] == before["getters"], f"{label}: getters changed: {before['getters']} -> {after['getters']}"
     assert sorted(after["taps"]) == sorted(before["taps"])
     for kind in ("taps", "exact"):
         for name, a in before[kind].items():
@@ -338,8 +341,14 @@ class Failure:
         assert e.value.code == -5 and self.message in str(e.value), f"{label}: the error of another failure: {e.value}"
 
     def assert_no_last_frame(self, pkg, rend, label):
-        """Every tap and every pass refuses with the code and message of a renderer that has not rendered yet, and writes nothing."""
+        """Every tap and every pass refuses with the code and message of a renderer that has not rendered yet, and writes nothing;
+        so does listed_instances(), no frame's lists are culled, and level1_fused() still answers (for the frame that failed)."""
         (w, h), n = self.size, self.n
+        with pytest.raises(pkg.GsError) as e:
+            rend.listed_instances()
+        assert e.value.code == -1 and NO_FRAME in str(e.value), f"{label}: listed_instances: {e.value}"
+        assert rend.tile_cull()[1] is False, f"{label}: a renderer without a last frame reports culled lists"
+        assert rend.level1_fused() in (True, False)
         for name in pkg.binding.STAGES:
             with pytest.raises(pkg.GsError) as e:
                 rend.stage(name, self.u_fail)
