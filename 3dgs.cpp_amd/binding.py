@@ -24,7 +24,7 @@ BLOB_PLANES = 59
 
 # the device code of libgs3d_hip.so: one translation unit per stage + the shared device headers
 KERNEL_SOURCES = ("gs_device.h", "gs_bin.h", "gs_tile_cull.h", "gs_scene.hip", "gs_preprocess.hip", "gs_radix.hip", "gs_bin_l1.hip", "gs_bin_l2.hip",
-                  "gs_blend.hip", "gs_contrib.hip", "gs_features.hip", "gs_lift.hip", "gs_kernels.h")
+                  "gs_blend.hip", "gs_contrib.hip", "gs_features.hip", "gs_lift.hip", "gs_backward.hip", "gs_wave_f64.h", "gs_kernels.h")
 
 
 def library_source_hash():
@@ -62,7 +62,7 @@ SYMBOLS = ["gs_last_error", "gs_device_count", "gs_read_ply", "gs_activate_recor
            "gs_deactivate_vertices", "gs_write_ply", "gs_scene_to_device_arrays", "gs_scene_download_records", "gs_scene_save_ply",
            "gs_scene_destroy", "gs_renderer_create", "gs_renderer_destroy", "gs_camera_uniforms",
            "gs_render", "gs_render_host", "gs_synchronize", "gs_set_timing", "gs_set_frames_in_flight", "gs_set_sort_path", "gs_set_exp_mode", "gs_set_graph_mode", "gs_set_blend_lockstep", "gs_get_blend_lockstep", "gs_set_level1_fused", "gs_get_level1_fused", "gs_set_tile_cull", "gs_get_tile_cull", "gs_get_listed_instances", "gs_set_blend_contraction", "gs_set_antialiased", "gs_get_antialiased", "gs_get_timing_totals",
-           "gs_get_frame_intervals", "gs_get_stats", "gs_poll_stats", "gs_debug_download", "gs_accumulate_contributions", "gs_blend_features", "gs_lift_pixels", "gs_debug_expf_scan", "gs_debug_alpha_cut_scan", "gs_renderer_stream",
+           "gs_get_frame_intervals", "gs_get_stats", "gs_poll_stats", "gs_debug_download", "gs_accumulate_contributions", "gs_blend_features", "gs_lift_pixels", "gs_blend_backward", "gs_debug_expf_scan", "gs_debug_alpha_cut_scan", "gs_renderer_stream",
            "gs_dist_unique_id", "gs_dist_create", "gs_dist_rank", "gs_dist_world", "gs_dist_pose_count",
            "gs_dist_broadcast_scene", "gs_dist_broadcast_scene_ex", "gs_dist_verify", "gs_dist_destroy"]
 
@@ -195,11 +195,18 @@ class PixelLift(C.Structure):
 
 
 LIFT_CHANNELS_MAX = 256  # GS_LIFT_CHANNELS_MAX
+
+
+class BlendGrads(C.Structure):
+    """gs_blend_grads: the two per-pixel gradient maps and the four per-Gaussian sums of gs_blend_backward (include/gs3d_hip.h)."""
+    _fields_ = [("grad_rgb", C.c_void_p), ("grad_alpha", C.c_void_p), ("d_colour", C.c_void_p), ("d_opacity", C.c_void_p),
+                ("d_conic", C.c_void_p), ("d_uv", C.c_void_p)]
+
 _FEATURE_MAPS_FN = None  # the torch.autograd.Function of Renderer.differentiable_feature_maps, defined when first asked for
 
 
 def _complete_callers_work(*tensors):
-    """gs_lift_pixels (and gs_blend_features under autograd) run on the renderer's own stream, which is non-blocking: nothing
+    """gs_lift_pixels, gs_blend_backward (and gs_blend_features under autograd) run on the renderer's own stream, which is non-blocking: nothing
     orders it behind the stream the caller's tensors were produced on.  If any of `tensors` is a torch device tensor, wait on the
     host for torch's CURRENT stream of that device: a fill, a copy, an optimizer step or a backward kernel still queued there has
     then finished before the pass reads or adds to the tensor.  (The pass returns synchronised, so later work on torch's stream
@@ -672,6 +679,44 @@ class Renderer:
             result[name] = t
         _complete_callers_work(values, mask, *result.values())  # (the zeros allocated above among them: their fill is queued too)
         _check(lib().gs_lift_pixels(self._h, C.byref(l)))
+        return result
+
+    def blend_backward(self, grad_rgb, grad_alpha=None, colour=None, opacity=None, conic=None, uv=None):
+        """The backward of the last frame's blend (gs_blend_backward): from grad_rgb float32 (H, W, 3) = dL/d(image RGB) and
+        grad_alpha float32 (H, W) = dL/d(alpha of feature_maps), or None for zeros, the float64 sums per Gaussian colour (N, 3),
+        opacity (N,), conic (N, 3) = c00 c01 c11 and uv (N, 2): the gradients with respect to the splat's rgb, its opacity, its
+        conic and its screen position AS THE FRAME HOLDS THEM (stage("conic_opacity"), stage("uv_rg"), stage("b")), the walk's
+        decisions taken as constants.  Each output is a tensor to ADD into, True to have zeros allocated, or None to skip; the
+        conventions, the stream and the wait for torch's current stream are lift_pixels's.  The order of the adds is unspecified:
+        two calls agree to rounding.  There is no autograd wrapper: chain into your own projection with
+        (d_x.float() * x).sum().backward().  Returns synchronised, with a dict of what was asked for (keys
+        colour, opacity, conic, uv)."""
+        owner = "Renderer.blend_backward"
+        n = int(self.scene.num_vertices)
+        dev = self.scene.device
+        asked = dict(colour=colour, opacity=opacity, conic=conic, uv=uv)
+        if self._frame_hw is None and any(v is True for v in asked.values()):
+            _check(lib().gs_blend_backward(self._h, C.byref(BlendGrads())))  # (refuses: there is no frame to size an input by)
+        h, w = self._frame_hw if self._frame_hw is not None else (None, None)
+        g = BlendGrads()
+        if grad_rgb is not None:
+            g.grad_rgb = _tensor_exact("grad_rgb", grad_rgb, ("float32",), (h, w, 3), dev, owner)
+        elif any(v is not None for v in asked.values()):
+            raise ValueError("grad_rgb: an output is asked for but there is no grad_rgb")
+        if grad_alpha is not None:
+            g.grad_alpha = _tensor_exact("grad_alpha", grad_alpha, ("float32",), (h, w), dev, owner)
+        shapes = dict(colour=(n, 3), opacity=(n,), conic=(n, 3), uv=(n, 2))
+        result = {}
+        for name, t in asked.items():
+            if t is None:
+                continue
+            if t is True:
+                import torch
+                t = torch.zeros(shapes[name], dtype=torch.float64, device=f"cuda:{int(dev)}")
+            setattr(g, "d_" + name, _tensor_exact(name, t, ("float64",), shapes[name], dev, owner))
+            result[name] = t
+        _complete_callers_work(grad_rgb, grad_alpha, *result.values())  # (the zeros allocated above among them)
+        _check(lib().gs_blend_backward(self._h, C.byref(g)))
         return result
 
     def differentiable_feature_maps(self, features):

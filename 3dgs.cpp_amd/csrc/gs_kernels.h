@@ -1,4 +1,4 @@
-// gs_kernels.h -- launch wrappers of the gfx950 kernels (gs_scene / gs_preprocess / gs_radix / gs_bin_l1 / gs_bin_l2 / gs_blend / gs_contrib / gs_features / gs_lift .hip).
+// gs_kernels.h -- launch wrappers of the gfx950 kernels (gs_scene / gs_preprocess / gs_radix / gs_bin_l1 / gs_bin_l2 / gs_blend / gs_contrib / gs_features / gs_lift / gs_backward .hip).
 // Host-side declarations only; everything takes raw device pointers + a stream.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -265,7 +265,7 @@ void launch_blend(const uint32_t* ranges, const uint32_t* sorted_gid, const uint
                   uint64_t* stamps /* nullable: [ST_BLEND] = the kernel's start */,
                   hipStream_t s);
 
-// A finished frame's per-tile lists, as the three passes below walk them: the first six arguments of each of their kernels.
+// A finished frame's per-tile lists, as the four passes below walk them: the first six arguments of each of their kernels.
 struct TileLists {
     const uint32_t* ranges;      // [T][2]
     const uint32_t* sorted_gid;  // the lists, bin-major
@@ -295,5 +295,12 @@ void launch_features(const TileLists& t, const float* features, uint32_t channel
 constexpr int kLiftGroup = 16, kLiftGroupSmall = 4;  // (a last group of at most 4 channels runs a kernel of 4)
 void launch_lift(const TileLists& t, const uint8_t* mask, const float* values, uint32_t channels, double* out, double* out_weight,
                  hipStream_t s);
+
+// gs_blend_backward (gs3d_hip.h; gs_backward.hip): the backward of the blend over the same lists: from grad_rgb [height][width][3]
+// and grad_alpha [height][width] (nullable: zeros) the per-Gaussian sums d_colour [N][3], d_opacity [N], d_conic [N][3], d_uv [N][2],
+// binary64 atomic adds.  One launch that walks every tile's list twice (the suffix sums R_i), or once when d_colour alone is asked
+// for.  Every output is nullable, device memory; with all four null nothing is launched.
+void launch_blend_backward(const TileLists& t, const float* grad_rgb, const float* grad_alpha, double* d_colour, double* d_opacity,
+                           double* d_conic, double* d_uv, hipStream_t s);
 
 }  // namespace gs

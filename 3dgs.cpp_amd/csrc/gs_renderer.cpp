@@ -834,7 +834,7 @@ struct gs_renderer {
     }
 
     // What the passes over the last frame's tile lists do after their own argument checks (gs_accumulate_contributions,
-    // gs_blend_features, gs_lift_pixels), in this order: queued frames retire (an overflowed one is re-run: the lists are the last
+    // gs_blend_features, gs_lift_pixels, gs_blend_backward), in this order: queued frames retire (an overflowed one is re-run: the lists are the last
     // frame's, complete); without a frame the call is refused; with nothing asked for it is done; otherwise launch(lists, stream)
     // enqueues the pass over the frame's own lists on the last frame's stream and the call waits for it.
     template <class Launch>
@@ -1305,6 +1305,25 @@ int gs_lift_pixels(gs_renderer* r, const gs_pixel_lift* l) {
         double* out = l->channels > 0 ? l->out : nullptr;  // channels == 0: that output is not touched
         r->over_last_frame(!out && !l->out_weight, [&](const gs::TileLists& lists, hipStream_t s) {
             gs::launch_lift(lists, l->mask, l->values, l->channels, out, l->out_weight, s);
+        });
+    });
+}
+
+int gs_blend_backward(gs_renderer* r, const gs_blend_grads* g) {
+    return guarded([&] {
+        if (!r || !g) throw Error(GS_ERR_INVALID, "null argument");
+        // (all by the members' values alone: nothing is dereferenced and no device is touched before they pass)
+        const bool asked = g->d_colour || g->d_opacity || g->d_conic || g->d_uv;
+        if (asked && !g->grad_rgb) throw Error(GS_ERR_INVALID, "an output is given without grad_rgb");
+        if (reinterpret_cast<uintptr_t>(g->grad_rgb) % 4 != 0) throw Error(GS_ERR_INVALID, "grad_rgb must be 4-byte aligned");
+        if (reinterpret_cast<uintptr_t>(g->grad_alpha) % 4 != 0) throw Error(GS_ERR_INVALID, "grad_alpha must be 4-byte aligned");
+        const struct { const void* p; const char* what; } outs[] = {
+            {g->d_colour, "d_colour must be 8-byte aligned"}, {g->d_opacity, "d_opacity must be 8-byte aligned"},
+            {g->d_conic, "d_conic must be 8-byte aligned"},   {g->d_uv, "d_uv must be 8-byte aligned"}};
+        for (const auto& q : outs)
+            if (reinterpret_cast<uintptr_t>(q.p) % 8 != 0) throw Error(GS_ERR_INVALID, q.what);
+        r->over_last_frame(!asked, [&](const gs::TileLists& lists, hipStream_t s) {
+            gs::launch_blend_backward(lists, g->grad_rgb, g->grad_alpha, g->d_colour, g->d_opacity, g->d_conic, g->d_uv, s);
         });
     });
 }

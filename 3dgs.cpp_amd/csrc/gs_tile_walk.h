@@ -1,7 +1,8 @@
-// gs_tile_walk.h -- the walk of the last frame's tile lists that k_contrib (gs_contrib.hip), k_features (gs_features.hip) and
-// k_lift (gs_lift.hip) share, and the quadrant test they share with the blend (gs_blend.hip: blend_walk).
+// gs_tile_walk.h -- the walk of the last frame's tile lists that k_contrib (gs_contrib.hip), k_features (gs_features.hip),
+// k_lift (gs_lift.hip) and k_blend_backward (gs_backward.hip) share, and the quadrant test they share with the blend
+// (gs_blend.hip: blend_walk).
 //
-// Device code, included by those four translation units; built with -ffp-contract=off like them: every product and sum of the
+// Device code, included by those five translation units; built with -ffp-contract=off like them: every product and sum of the
 // walk is rounded on its own.  Reference restated: render.comp:61-89 (the shader gs_blend.hip restates).  Each piece stands here
 // ONCE, with the one comment that explains it: a change to the slack, to the record layout or to the exit rule is made here.
 #pragma once

@@ -302,7 +302,7 @@ int gs_camera_uniforms(const gs_camera* cam, uint32_t width, uint32_t height, gs
  * an overflow of the instance buffers is detected at the next gs_synchronize/gs_get_stats,
  * which grows them and re-runs the frame (Renderer.cpp:541-563).
  *
- * "The last frame" -- what the stage taps, gs_accumulate_contributions, gs_blend_features and gs_lift_pixels answer from -- is the
+ * "The last frame" -- what the stage taps, gs_accumulate_contributions, gs_blend_features, gs_lift_pixels and gs_blend_backward answer from -- is the
  * most recently enqueued frame, once it has retired.  What an error of gs_render / gs_render_host leaves of it:
  *   * A REFUSED call changes nothing.  Refused (GS_ERR_INVALID, before any queued frame is waited for and before anything is
  *     allocated): a null argument, an empty framebuffer, a tile box beyond 16 bits, a resolution beyond the tile binning.  The
@@ -311,7 +311,7 @@ int gs_camera_uniforms(const gs_camera* cam, uint32_t width, uint32_t height, gs
  *   * A call that FAILS WHILE RETIRING queued frames -- GS_ERR_OVERFLOW: a bin too full or depths too crowded for the forced
  *     bin-local path (gs_set_sort_path(r, 2)), instance buffers that overflowed repeatedly, more than 2^30 tile instances or
  *     level-1 candidates -- leaves the renderer WITHOUT a last frame.  Every queued frame was dropped: none of their targets is
- *     valid, and the frame of the failing call, if any, was not enqueued.  The taps and the three passes return GS_ERR_INVALID
+ *     valid, and the frame of the failing call, if any, was not enqueued.  The taps and the four passes return GS_ERR_INVALID
  *     ("no frame rendered yet") until a frame rendered after the failure has retired; gs_get_stats keeps describing the last
  *     frame that did retire (blend_redo / blend_resolved, which are read from the device, are 0 meanwhile).  The renderer
  *     renders on: after gs_set_sort_path(r, 0) the same pose gives the right frame.  The same holds for gs_synchronize,
@@ -621,6 +621,56 @@ typedef struct {
     double*        out_weight;  /* [N], ADDED to: the sum of w itself */
 } gs_pixel_lift;
 int gs_lift_pixels(gs_renderer* r, const gs_pixel_lift* l);
+/* The backward of the blend of the LAST frame: from dL/d(image RGB) and dL/d(out_alpha of gs_blend_features) the gradients with
+ * respect to what shapes each splat on the screen -- its colour, opacity, conic and screen position -- summed per Gaussian.  It
+ * is what the rasteriser backward of a 3DGS trainer computes; the projection half (means, scales, quaternions, SH -> uv, conic,
+ * rgb) is left to the caller's autograd.  No reference counterpart.  One more kernel (gs_backward.hip)
+ * walks the per-tile lists and attribute records the frame left in HBM, twice per tile inside one launch; it reads ranges, lists
+ * and records of that frame and the caller's two maps, adds to the caller's four arrays and writes nothing the renderer owns.
+ *
+ * Per pixel the list is walked exactly as gs_lift_pixels documents it (render.comp:61-89), with the reference's arithmetic
+ * whatever mode the frame ran in.  For the pixel's blended entries i = 1 .. L (those that reach :87), in list order:
+ *     alpha_i, T_i   the binary32 values :87 reads, T_i before :88
+ *     prod_i         fl32(o * e_i), e_i the exp of :77 (glibc's expf restated); alpha_i = min(0.99, prod_i)
+ *     dx_i, dy_i     the binary32 values of :66
+ *     m_i            fl32(1 - alpha_i), at least 0.01
+ *     T_f            the binary32 T at the end of the walk (a break at :83 leaves it as it was, as in gs_blend_features)
+ *     c00 c01 c11 o, u v r g, b   the entry's record;   G = grad_rgb[p];   ga = grad_alpha[p], 0 when grad_alpha is NULL
+ * The decisions -- the `power > 0` skip, the 1/255 skip, the break -- are constants and carry no gradient.  Everything below is
+ * binary64 on exact conversions of those binary32 values:
+ *     a_i  = G_r r + G_g g + G_b b        w_i = (double)fl32(alpha_i T_i)        R_i = sum over j > i of a_j w_j
+ *     d_colour[g] += w_i * G                                   (this IS gs_lift_pixels of grad_rgb)
+ *     galpha_i = T_i a_i - (R_i - ga T_f) / m_i
+ *     flows_i  = (prod_i <= 0.99f)        false for a clamped alpha and for a NaN product: those pairs add only to d_colour
+ *     if flows_i:
+ *       d_opacity[g] += galpha_i * e_i
+ *       gp = galpha_i * alpha_i
+ *       d_conic[g]   += gp * (-0.5 dx^2, -dx dy, -0.5 dy^2)
+ *       d_uv[g]      += gp * (-(c00 dx + c01 dy), -(c01 dx + c11 dy))
+ * A term exists only for a (pixel, blended entry) pair inside the image: a NaN in grad_rgb at a pixel reaches only the Gaussians
+ * blended there (a term is selected, never multiplied by zero), and the maps are not read at all under a tile whose list is
+ * empty.  Every add is a binary64 add.  The order of the adds is unspecified, and so is the association inside a term, including
+ * whether R_i is a suffix sum or a total minus a prefix: the contract is a bound, not a bit pattern.  With n_g the number of terms
+ * Gaussian g receives and A the sum of the terms' magnitudes (every constituent by its absolute value, R_i entering as
+ * (L + 2) sum_j |a_j| w_j), the result is within (n_g + 8) 2^-53 A of the exact sum; tests/backward_reference.py derives it.
+ * Tile cull (gs_set_tile_cull) changes no sum: an entry the cull drops is one every pixel of the tile skips.
+ *
+ * Scene ids, ordinary device allocations for the outputs (global_atomic_add_f64), inputs and the contents of the outputs COMPLETE
+ * before the call, the renderer's own NON-BLOCKING stream, the synchronisation (queued frames retire, an overflowed frame is
+ * re-run, the call returns when the arrays are written), "no frame rendered yet" and the behaviour after a refused or failed
+ * gs_render: all as gs_lift_pixels states them.
+ * GS_ERR_INVALID, checked before any device is touched: r or g NULL; an output given while grad_rgb is NULL; a float pointer
+ * that is not 4-byte aligned or a double pointer that is not 8-byte aligned (judged by its value alone).  All four outputs NULL:
+ * success, nothing is launched.  width and height are those of the last frame, N = gs_scene_num_vertices.  Cost: INTEGRATION.md, 3g. */
+typedef struct {
+    const float* grad_rgb;    /* [height][width][3] dL/d(image RGB); required unless every output is NULL */
+    const float* grad_alpha;  /* [height][width]    dL/d(out_alpha of gs_blend_features); nullable = zeros */
+    double* d_colour;         /* [N][3]  ADDED to */
+    double* d_opacity;        /* [N]     ADDED to */
+    double* d_conic;          /* [N][3]  c00 c01 c11, ADDED to */
+    double* d_uv;             /* [N][2]  ADDED to */
+} gs_blend_grads;
+int gs_blend_backward(gs_renderer* r, const gs_blend_grads* g);
 /* Test hook (tests/test_gpu_expf.py): evaluate the blend's exp() implementations ON THE DEVICE over the binary32 values with
  * bit patterns [first_bits, first_bits + count) (the negative floats run from 0x80000000 = -0 to 0xFF800000 = -inf).
  * block_sums[j] = sum over block j of 2^20 consecutive patterns of  bits(expf(x)) * ((bits(x) * 0x9E3779B1) | 1)  mod 2^64,
