@@ -24,7 +24,7 @@ BLOB_PLANES = 59
 
 # the device code of libgs3d_hip.so: one translation unit per stage + the shared device headers
 KERNEL_SOURCES = ("gs_device.h", "gs_bin.h", "gs_tile_cull.h", "gs_scene.hip", "gs_preprocess.hip", "gs_radix.hip", "gs_bin_l1.hip", "gs_bin_l2.hip",
-                  "gs_blend.hip", "gs_contrib.hip", "gs_features.hip", "gs_lift.hip", "gs_backward.hip", "gs_wave_f64.h", "gs_kernels.h")
+                  "gs_blend.hip", "gs_contrib.hip", "gs_features.hip", "gs_lift.hip", "gs_backward.hip", "gs_project_backward.hip", "gs_wave_f64.h", "gs_kernels.h")
 
 
 def library_source_hash():
@@ -62,7 +62,7 @@ SYMBOLS = ["gs_last_error", "gs_device_count", "gs_read_ply", "gs_activate_recor
            "gs_deactivate_vertices", "gs_write_ply", "gs_scene_to_device_arrays", "gs_scene_download_records", "gs_scene_save_ply",
            "gs_scene_destroy", "gs_renderer_create", "gs_renderer_destroy", "gs_camera_uniforms",
            "gs_render", "gs_render_host", "gs_synchronize", "gs_set_timing", "gs_set_frames_in_flight", "gs_set_sort_path", "gs_set_exp_mode", "gs_set_graph_mode", "gs_set_blend_lockstep", "gs_get_blend_lockstep", "gs_set_level1_fused", "gs_get_level1_fused", "gs_set_tile_cull", "gs_get_tile_cull", "gs_get_listed_instances", "gs_set_blend_contraction", "gs_set_antialiased", "gs_get_antialiased", "gs_get_timing_totals",
-           "gs_get_frame_intervals", "gs_get_stats", "gs_poll_stats", "gs_debug_download", "gs_accumulate_contributions", "gs_blend_features", "gs_lift_pixels", "gs_blend_backward", "gs_debug_expf_scan", "gs_debug_alpha_cut_scan", "gs_renderer_stream",
+           "gs_get_frame_intervals", "gs_get_stats", "gs_poll_stats", "gs_debug_download", "gs_accumulate_contributions", "gs_blend_features", "gs_lift_pixels", "gs_blend_backward", "gs_project_backward", "gs_debug_expf_scan", "gs_debug_alpha_cut_scan", "gs_renderer_stream",
            "gs_dist_unique_id", "gs_dist_create", "gs_dist_rank", "gs_dist_world", "gs_dist_pose_count",
            "gs_dist_broadcast_scene", "gs_dist_broadcast_scene_ex", "gs_dist_verify", "gs_dist_destroy"]
 
@@ -202,7 +202,18 @@ class BlendGrads(C.Structure):
     _fields_ = [("grad_rgb", C.c_void_p), ("grad_alpha", C.c_void_p), ("d_colour", C.c_void_p), ("d_opacity", C.c_void_p),
                 ("d_conic", C.c_void_p), ("d_uv", C.c_void_p)]
 
+
+
+class ProjectGrads(C.Structure):
+    """gs_project_grads: the four per-Gaussian input gradients and the six parameter-gradient sums of gs_project_backward
+    (include/gs3d_hip.h)."""
+    _fields_ = [("d_colour", C.c_void_p), ("d_opacity", C.c_void_p), ("d_conic", C.c_void_p), ("d_uv", C.c_void_p),
+                ("d_means", C.c_void_p), ("d_log_scales", C.c_void_p), ("d_quats", C.c_void_p), ("d_opacity_logits", C.c_void_p),
+                ("d_sh_dc", C.c_void_p), ("d_sh_rest", C.c_void_p), ("sh_rest_coeffs", C.c_uint32)]
+
+
 _FEATURE_MAPS_FN = None  # the torch.autograd.Function of Renderer.differentiable_feature_maps, defined when first asked for
+_RENDER_FN = None        # ... and of Renderer.differentiable_render
 
 
 def _complete_callers_work(*tensors):
@@ -247,6 +258,59 @@ def _feature_maps_function():
 
         _FEATURE_MAPS_FN = FeatureMapsFunction
     return _FEATURE_MAPS_FN
+
+
+def _render_function():
+    """The autograd function behind Renderer.differentiable_render; torch is imported here, not with the module."""
+    global _RENDER_FN
+    if _RENDER_FN is None:
+        import torch
+
+        class RenderFunction(torch.autograd.Function):
+            """rgb (and alpha) of one frame of the renderer's scene, refreshed from the six parameter tensors; the backward is
+            blend_backward then project_backward, at the frame's values, rounded to float32."""
+
+            @staticmethod
+            def forward(ctx, renderer, uniforms, want_alpha, means, log_scales, quats, opacity_logits, sh_dc, sh_rest):
+                params = dict(means=means, log_scales=log_scales, quats=quats, opacity_logits=opacity_logits, sh_dc=sh_dc, sh_rest=sh_rest)
+                renderer.synchronize()  # (no frame of this renderer may straddle the update)
+                renderer.scene.update_from_tensors(0, **{k: (None if v is None else v.detach().contiguous()) for k, v in params.items()})
+                h, w = int(uniforms["height"][0]), int(uniforms["width"][0])
+                rgba = torch.empty((h, w, 4), dtype=torch.float32, device=f"cuda:{int(renderer.scene.device)}")
+                renderer.render(uniforms, rgba.data_ptr())
+                renderer.synchronize()
+                ctx.renderer, ctx.frame, ctx.want_alpha = renderer, renderer._frames, bool(want_alpha)
+                ctx.shapes = {k: (None if v is None else tuple(v.shape)) for k, v in params.items()}
+                rgb = rgba[..., :3].contiguous()
+                if not want_alpha:
+                    return rgb
+                return rgb, renderer.feature_maps(alpha=True)["alpha"]
+
+            @staticmethod
+            def backward(ctx, grad_rgb, grad_alpha=None):
+                rend = ctx.renderer
+                if rend._frames != ctx.frame:
+                    raise RuntimeError(f"differentiable_render: the forward rendered frame {ctx.frame} of this renderer, which has "
+                                       f"rendered frame {rend._frames} since; the gradient of another frame is not returned")
+                if grad_rgb is None:
+                    grad_rgb = torch.zeros(rend._frame_hw + (3,), dtype=torch.float32, device=f"cuda:{int(rend.scene.device)}")
+                d = rend.blend_backward(grad_rgb.contiguous().float(), None if grad_alpha is None else grad_alpha.contiguous().float(),
+                                        colour=True, opacity=True, conic=True, uv=True)
+                rest = ctx.shapes["sh_rest"]
+                k = 0 if rest is None else int(rest[-2])
+                n = int(rend.scene.num_vertices)
+                names = ("means", "log_scales", "quats", "opacity_logits", "sh_dc") + (("sh_rest",) if k else ())
+                shapes = dict(means=(n, 3), log_scales=(n, 3), quats=(n, 4), opacity_logits=(n,), sh_dc=(n, 3), sh_rest=(n, k, 3))
+                out = {name: torch.zeros(shapes[name], dtype=torch.float64, device=grad_rgb.device) for name in names}
+                rend.project_backward(out=out, **d)
+                grads = [None if ctx.shapes[name] is None or name not in out else out[name].to(torch.float32).reshape(ctx.shapes[name])
+                         for name in ("means", "log_scales", "quats", "opacity_logits", "sh_dc", "sh_rest")]
+                if ctx.shapes["sh_rest"] is not None and not k:
+                    grads[5] = torch.zeros(ctx.shapes["sh_rest"], dtype=torch.float32, device=grad_rgb.device)
+                return (None, None, None, *grads)
+
+        _RENDER_FN = RenderFunction
+    return _RENDER_FN
 
 
 def _tensor_exact(name, t, dtypes, shape, device, owner="Renderer.contributions"):
@@ -688,9 +752,9 @@ class Renderer:
         conic and its screen position AS THE FRAME HOLDS THEM (stage("conic_opacity"), stage("uv_rg"), stage("b")), the walk's
         decisions taken as constants.  Each output is a tensor to ADD into, True to have zeros allocated, or None to skip; the
         conventions, the stream and the wait for torch's current stream are lift_pixels's.  The order of the adds is unspecified:
-        two calls agree to rounding.  There is no autograd wrapper: chain into your own projection with
-        (d_x.float() * x).sum().backward().  Returns synchronised, with a dict of what was asked for (keys
-        colour, opacity, conic, uv)."""
+        two calls agree to rounding.  project_backward takes these four sums on to the trainer's parameters, and
+        differentiable_render is both passes behind one autograd function.  Returns synchronised,
+        with a dict of what was asked for (keys colour, opacity, conic, uv)."""
         owner = "Renderer.blend_backward"
         n = int(self.scene.num_vertices)
         dev = self.scene.device
@@ -718,6 +782,65 @@ class Renderer:
         _complete_callers_work(grad_rgb, grad_alpha, *result.values())  # (the zeros allocated above among them)
         _check(lib().gs_blend_backward(self._h, C.byref(g)))
         return result
+
+    def project_backward(self, colour=None, opacity=None, conic=None, uv=None, out=None, sh_degree=3):
+        """The projection half of the last frame's backward (gs_project_backward): from the float64 gradients per Gaussian with
+        respect to its record -- colour (N, 3), opacity (N,), conic (N, 3), uv (N, 2), exactly what blend_backward returns; None =
+        zeros -- the float64 gradients with respect to the six tensors Scene.to_tensors() returns.  out: a dict under
+        from_tensors' keyword names (means (N, 3), log_scales (N, 3), quats (N, 4), opacity_logits (N,), sh_dc (N, 3), sh_rest
+        (N, k, 3) with k in 0, 3, 8, 15) holding float64 tensors to ADD into -- a name it lacks or holds None for is skipped -- or
+        None, and zeros are allocated for all six, sh_rest with the k of sh_degree.  Only the Gaussians the frame found visible
+        are touched; the gradient is the one AT THE FRAME'S VALUES with the frame's decisions (culls, the clamp's branch, red's
+        max(0, .)) as constants, and the scene must still hold what the frame rendered.  The stream and the wait for torch's
+        current stream are lift_pixels's.  Returns synchronised, with the dict."""
+        owner = "Renderer.project_backward"
+        n = int(self.scene.num_vertices)
+        dev = self.scene.device
+        names = ("means", "log_scales", "quats", "opacity_logits", "sh_dc", "sh_rest")
+        g = ProjectGrads()
+        if out is None:
+            if sh_degree not in SH_REST_COEFFS:
+                raise ValueError(f"sh_degree must be 0, 1, 2 or 3, not {sh_degree!r}")
+        else:
+            unknown = sorted(set(out) - set(names))
+            if unknown:
+                raise TypeError(f"out: unknown member(s) {unknown}")
+        ins = dict(colour=(colour, (n, 3)), opacity=(opacity, (n,)), conic=(conic, (n, 3)), uv=(uv, (n, 2)))
+        for name, (t, shape) in ins.items():
+            if t is not None:
+                setattr(g, "d_" + name, _tensor_exact(name, t, ("float64",), shape, dev, owner))
+        if out is None:
+            import torch
+            k = SH_REST_COEFFS[sh_degree]
+            shapes = dict(means=(n, 3), log_scales=(n, 3), quats=(n, 4), opacity_logits=(n,), sh_dc=(n, 3), sh_rest=(n, k, 3))
+            out = {name: torch.zeros(shapes[name], dtype=torch.float64, device=f"cuda:{int(dev)}") for name in names}
+        shapes = dict(means=(n, 3), log_scales=(n, 3), quats=(n, 4), opacity_logits=(n,), sh_dc=(n, 3), sh_rest=(n, None, 3))
+        for name in names:
+            t = out.get(name)
+            if t is None:
+                continue
+            ptr = _tensor_exact(name, t, ("float64",), shapes[name], dev, owner)
+            if name == "sh_rest":
+                k = int(t.shape[1])
+                if k not in SH_REST_COEFFS.values():
+                    raise ValueError(f"sh_rest: shape {tuple(int(d) for d in t.shape)} is not (rows, k, 3) with k in 0, 3, 8, 15")
+                g.sh_rest_coeffs = k if ptr else 0
+            setattr(g, "d_" + name, ptr)
+        _complete_callers_work(colour, opacity, conic, uv, *[t for t in out.values() if t is not None])
+        _check(lib().gs_project_backward(self._h, C.byref(g)))
+        return out
+
+    def differentiable_render(self, uniforms, means, log_scales, quats, opacity_logits, sh_dc, sh_rest=None, want_alpha=False):
+        """One frame as a torch.autograd.Function of the trainer's six parameter tensors (float32, on the renderer's device, as
+        Scene.from_tensors takes them, one row per Gaussian of the scene): the forward refreshes the scene from them
+        (update_from_tensors(0, ...); sh_rest None keeps the bands the scene holds), renders `uniforms` into a fresh tensor and
+        synchronises; it returns rgb (H, W, 3), and with want_alpha also alpha (H, W) of feature_maps.  The backward is
+        blend_backward then project_backward and returns the six gradients ROUNDED TO FLOAT32: the gradient AT THE FRAME'S VALUES
+        -- the stored binary32 parameters, the records the frame holds -- WITH ITS DECISIONS AS CONSTANTS (visibility, the tile
+        lists, the 1/255 and 1e-4 cuts, the 0.99 clamp, the Jacobian clamp's branch, red's max(0, .)).  The camera carries no
+        gradient.  A backward after this renderer has been handed another frame raises RuntimeError instead of returning the
+        gradient of a different frame; so one backward per forward, before the next forward."""
+        return _render_function().apply(self, uniforms, bool(want_alpha), means, log_scales, quats, opacity_logits, sh_dc, sh_rest)
 
     def differentiable_feature_maps(self, features):
         """feature_maps(features)["out"] as a torch.autograd.Function: features (N, C) float32 on the renderer's device -> the

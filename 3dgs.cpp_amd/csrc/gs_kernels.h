@@ -1,4 +1,4 @@
-// gs_kernels.h -- launch wrappers of the gfx950 kernels (gs_scene / gs_preprocess / gs_radix / gs_bin_l1 / gs_bin_l2 / gs_blend / gs_contrib / gs_features / gs_lift / gs_backward .hip).
+// gs_kernels.h -- launch wrappers of the gfx950 kernels (gs_scene / gs_preprocess / gs_radix / gs_bin_l1 / gs_bin_l2 / gs_blend / gs_contrib / gs_features / gs_lift / gs_backward / gs_project_backward .hip).
 // Host-side declarations only; everything takes raw device pointers + a stream.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -302,5 +302,12 @@ void launch_lift(const TileLists& t, const uint8_t* mask, const float* values, u
 // for.  Every output is nullable, device memory; with all four null nothing is launched.
 void launch_blend_backward(const TileLists& t, const float* grad_rgb, const float* grad_alpha, double* d_colour, double* d_opacity,
                            double* d_conic, double* d_uv, hipStream_t s);
+
+// gs_project_backward (gs3d_hip.h; gs_project_backward.hip): the projection half of the backward, one lane per Gaussian of sv in the
+// order the frame read it: from g's four input arrays (nullable: zeros) the sums of g's six output arrays (nullable: skipped), by
+// scene id, for the Gaussians with tiles[id] != 0.  tiles, rec: the frame's tiles_overlap plane and records, by scene id; u,
+// antialiased: what the frame ran with.  One writer per element, no atomics.
+void launch_project_backward(const SceneView& sv, const uint32_t* tiles, const AttrRecord* rec, const gs_uniforms& u, bool antialiased,
+                             const gs_project_grads& g, hipStream_t s);
 
 }  // namespace gs

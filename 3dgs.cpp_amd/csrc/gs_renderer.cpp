@@ -180,6 +180,8 @@ struct LastFrame {
     FramePlan plan;
     uint64_t listed = 0;          // tile instances in the lists of the frame that retired last (once nothing is queued: this frame's)
     bool tap_lists = false;       // the renderer's tap buffers hold THIS frame's reference lists (gs_renderer::reference_lists)
+    gs_uniforms u{};              // the uniforms the frame ran with ...
+    bool antialiased = false;     // ... and its antialiased mode (gs_project_backward answers for the frame, not for a later setter)
 };
 
 struct gs_renderer {
@@ -653,6 +655,7 @@ struct gs_renderer {
 
         // every launch has been issued: this is the last frame now
         last_frame = LastFrame{&fb, plan};
+        last_frame.u = u, last_frame.antialiased = antialiased;
         enqueued_l1_fused = plan.l1_fused;
 
         sl.plan = plan;
@@ -834,7 +837,7 @@ struct gs_renderer {
     }
 
     // What the passes over the last frame's tile lists do after their own argument checks (gs_accumulate_contributions,
-    // gs_blend_features, gs_lift_pixels, gs_blend_backward), in this order: queued frames retire (an overflowed one is re-run: the lists are the last
+    // gs_blend_features, gs_lift_pixels, gs_blend_backward, gs_project_backward), in this order: queued frames retire (an overflowed one is re-run: the lists are the last
     // frame's, complete); without a frame the call is refused; with nothing asked for it is done; otherwise launch(lists, stream)
     // enqueues the pass over the frame's own lists on the last frame's stream and the call waits for it.
     template <class Launch>
@@ -1324,6 +1327,33 @@ int gs_blend_backward(gs_renderer* r, const gs_blend_grads* g) {
             if (reinterpret_cast<uintptr_t>(q.p) % 8 != 0) throw Error(GS_ERR_INVALID, q.what);
         r->over_last_frame(!asked, [&](const gs::TileLists& lists, hipStream_t s) {
             gs::launch_blend_backward(lists, g->grad_rgb, g->grad_alpha, g->d_colour, g->d_opacity, g->d_conic, g->d_uv, s);
+        });
+    });
+}
+
+int gs_project_backward(gs_renderer* r, const gs_project_grads* g) {
+    return guarded([&] {
+        if (!r || !g) throw Error(GS_ERR_INVALID, "null argument");
+        // (all by the members' values alone: nothing is dereferenced and no device is touched before they pass)
+        const struct { const void* p; const char* what; } ptrs[] = {
+            {g->d_colour, "d_colour must be 8-byte aligned"},   {g->d_opacity, "d_opacity must be 8-byte aligned"},
+            {g->d_conic, "d_conic must be 8-byte aligned"},     {g->d_uv, "d_uv must be 8-byte aligned"},
+            {g->d_means, "d_means must be 8-byte aligned"},     {g->d_log_scales, "d_log_scales must be 8-byte aligned"},
+            {g->d_quats, "d_quats must be 8-byte aligned"},     {g->d_opacity_logits, "d_opacity_logits must be 8-byte aligned"},
+            {g->d_sh_dc, "d_sh_dc must be 8-byte aligned"},     {g->d_sh_rest, "d_sh_rest must be 8-byte aligned"}};
+        for (const auto& q : ptrs)
+            if (reinterpret_cast<uintptr_t>(q.p) % 8 != 0) throw Error(GS_ERR_INVALID, q.what);
+        const uint32_t k = g->sh_rest_coeffs;
+        if (k != 0 && k != 3 && k != 8 && k != 15) throw Error(GS_ERR_INVALID, "sh_rest_coeffs must be 0, 3, 8 or 15");
+        if (k != 0 && !g->d_sh_rest) throw Error(GS_ERR_INVALID, "sh_rest_coeffs > 0 needs d_sh_rest");
+        const bool asked = g->d_means || g->d_log_scales || g->d_quats || g->d_opacity_logits || g->d_sh_dc || (g->d_sh_rest && k != 0);
+        r->over_last_frame(!asked, [&](const gs::TileLists& lists, hipStream_t s) {
+            r->rebuild_planes();  // visibility is the tiles tap's answer (a frame of the dense lists or the one-pass level 1 wrote no planes)
+            const gs_scene* sc = r->scene;
+            const uint32_t n = static_cast<uint32_t>(sc->n);
+            const gs::SceneView sv{sc->render_blob(), sc->cov3d.p, n, static_cast<uint32_t>(gs::blob_stride(n)),
+                                   sc->sh_half ? sc->sh16.p : nullptr, sc->acut.p, sc->perm.p};
+            gs::launch_project_backward(sv, r->last_frame.set->tiles.p, lists.rec, r->last_frame.u, r->last_frame.antialiased, *g, s);
         });
     });
 }

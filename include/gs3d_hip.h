@@ -302,7 +302,7 @@ int gs_camera_uniforms(const gs_camera* cam, uint32_t width, uint32_t height, gs
  * an overflow of the instance buffers is detected at the next gs_synchronize/gs_get_stats,
  * which grows them and re-runs the frame (Renderer.cpp:541-563).
  *
- * "The last frame" -- what the stage taps, gs_accumulate_contributions, gs_blend_features, gs_lift_pixels and gs_blend_backward answer from -- is the
+ * "The last frame" -- what the stage taps, gs_accumulate_contributions, gs_blend_features, gs_lift_pixels, gs_blend_backward and gs_project_backward answer from -- is the
  * most recently enqueued frame, once it has retired.  What an error of gs_render / gs_render_host leaves of it:
  *   * A REFUSED call changes nothing.  Refused (GS_ERR_INVALID, before any queued frame is waited for and before anything is
  *     allocated): a null argument, an empty framebuffer, a tile box beyond 16 bits, a resolution beyond the tile binning.  The
@@ -624,7 +624,7 @@ int gs_lift_pixels(gs_renderer* r, const gs_pixel_lift* l);
 /* The backward of the blend of the LAST frame: from dL/d(image RGB) and dL/d(out_alpha of gs_blend_features) the gradients with
  * respect to what shapes each splat on the screen -- its colour, opacity, conic and screen position -- summed per Gaussian.  It
  * is what the rasteriser backward of a 3DGS trainer computes; the projection half (means, scales, quaternions, SH -> uv, conic,
- * rgb) is left to the caller's autograd.  No reference counterpart.  One more kernel (gs_backward.hip)
+ * rgb) is gs_project_backward, below.  No reference counterpart.  One more kernel (gs_backward.hip)
  * walks the per-tile lists and attribute records the frame left in HBM, twice per tile inside one launch; it reads ranges, lists
  * and records of that frame and the caller's two maps, adds to the caller's four arrays and writes nothing the renderer owns.
  *
@@ -671,6 +671,76 @@ typedef struct {
     double* d_uv;             /* [N][2]  ADDED to */
 } gs_blend_grads;
 int gs_blend_backward(gs_renderer* r, const gs_blend_grads* g);
+/* The projection half of the backward of the LAST frame: from the gradients with respect to each visible Gaussian's screen-space
+ * record -- what gs_blend_backward sums -- to the gradients with respect to the six tensors gs_scene_to_device_arrays exports
+ * (means, log-scales, quaternions, opacity logits, SH DC and rest).  With gs_blend_backward in front of it this is the whole
+ * backward of a frame, at the frame's values.  No reference counterpart.  One kernel (gs_project_backward.hip), one lane per
+ * Gaussian; it reads the scene, the frame's records and visibility and the caller's four arrays, adds to the caller's six and
+ * writes nothing the renderer or the scene owns.  No per-frame kernel is involved.
+ *
+ * THE FUNCTION.  For a Gaussian with stored binary32 position p, activated scale s, stored quaternion q (w x y z), activated opacity
+ * o and the 16 x 3 SH coefficients AS STORED (binary16 storage widened exactly), and the frame's gs_uniforms, the record is this
+ * exact real function F.  Every constant is the frame's binary32 constant converted exactly (0.3f, 0.5f, the constants of the SH
+ * basis; lim_x = the binary32 product 1.3f * tan_fovx); P[r][c] = proj_mat[4 c + r], V[r][c] = view_mat[4 c + r]; W, H = width, height.
+ *     h = P (p, 1)                       t = V (p, 1), rows 0..2
+ *     u = ((h0 / h3 + 1) W - 1) / 2      v = ((h1 / h3 + 1) H - 1) / 2
+ *     tx = clamp(t0 / t2, +-lim_x) t2,  ty likewise.  THE BRANCH OF EACH CLAMP IS A CONSTANT, taken as the frame took it: by the
+ *          binary32 comparison of k_preprocess on its binary32 t0 / t2.  Where the clamp binds, tx = c t2 with c = +-lim_x is still
+ *          differentiated through t2.
+ *     J = [[fx / t2, 0, -fx tx / t2^2], [0, fy / t2, -fy ty / t2^2]]       fx = W / (2 tan_fovx), fy = H / (2 tan_fovy)
+ *     A = J V(3 x 3)
+ *     Sigma = R(q^) diag(s^2) R(q^)^T,  q^ = q / |q|,  R the standard rotation matrix of a unit quaternion: the matrix the scene's
+ *          cov3D planes hold, recomputed from s and q, not read from the rounded planes
+ *     cov = A Sigma A^T
+ *     m00 = cov00 + 0.3    m11 = cov11 + 0.3    m01 = cov01    det = m00 m11 - m01^2
+ *     (c00, c01, c11) = (m11, -m01, m00) / det
+ *     o' = o                                  in a frame rendered with gs_set_antialiased off
+ *     o' = o comp,  comp = sqrt(det_raw / det),  det_raw = cov00 cov11 - cov01^2          in an antialiased frame.  There is no
+ *          min(1, .): in exact arithmetic it never binds.  Where the binary64 det_raw <= 0, comp is the constant 0.
+ *     d = (p - camera_position) / |p - camera_position|
+ *     rgb_k = 0.5 + sum_j B_j(d) sh[j][k],  B_j the sixteen basis polynomials (signs and constants included) of preprocess.comp's
+ *          compute_sh, as polynomials in three independent variables.  Channel 0 is max(0, .): ITS BRANCH IS A CONSTANT, it flows
+ *          iff the frame's record holds r > 0.
+ *     parameters:  s = exp(ls),  o = 1 / (1 + exp(-l)),  q^ = q / |q|:  the derivatives are s d/ds, o (1 - o) d/do and
+ *          (g - q^ (q^ . g)) / |q|, evaluated at the STORED values, |q| the stored quaternion's own norm in binary64 -- the
+ *          gradients with respect to the six tensors gs_scene_to_device_arrays returns.
+ * Radius, tile box, depth, alpha cut and the culls carry no gradient; neither does the camera.
+ * With inputs g_colour[3], g_opacity, g_conic[3] (c00 c01 c11), g_uv[2] per Gaussian (binary64; a NULL array = zeros) every parameter
+ * theta of a VISIBLE Gaussian -- one whose GS_STAGE_TILES value of that frame is not 0 -- receives  sum_x g_x dx/dtheta  over the
+ * nine record values x (o' for the opacity), by the chain rule over the nodes above.  Everything is binary64 on exact conversions
+ * of the stored binary32 values and the uniforms; the association is unspecified: the contract is a bound, not a bit pattern --
+ * with every input gradient, partial and product taken by its absolute value and the condition factor of each cancelling
+ * intermediate (h3, t2, the cov2D entries, det, det_raw) carried along into a magnitude A, |result - exact| <= 660 * 2^-53 * A;
+ * tests/project_backward_reference.py derives it and counts the 660.
+ *   * Outputs are ADDED to (zero them once; gradients accumulate over a camera set).  One writer per element: two calls give the
+ *     same bits.  An add of an exact zero may be omitted (it is: an element no gradient reaches keeps its bits).
+ *   * A Gaussian the frame culled is not touched at all: neither its inputs nor its outputs are read or written.
+ *   * A NaN among one Gaussian's inputs reaches that Gaussian's rows only.
+ *   * sh_rest_coeffs = K in {0, 3, 8, 15}: d_sh_rest is [N][K][3], the coefficients 1 .. K; higher bands are not written (they
+ *     still shape rgb, and through d the means).
+ * THE SCENE MUST STILL HOLD WHAT THE FRAME RENDERED: the pass reads positions, scales, rotations, opacities and SH from the scene
+ * as it is now.  gs_scene_update_from_device_arrays, gs_scene_transform or gs_scene_quantize_sh between the frame and this call
+ * give the gradient of no frame.  It answers for the frame, not for a gs_set_antialiased made after it.
+ * Scene ids, ordinary device allocations, inputs and the contents of the outputs COMPLETE before the call, the renderer's own
+ * NON-BLOCKING stream, the synchronisation (queued frames retire, an overflowed frame is re-run, the call returns when the arrays
+ * are written), "no frame rendered yet" and the behaviour after a refused or failed gs_render: all as gs_lift_pixels states them.
+ * GS_ERR_INVALID, checked before any device is touched: r or g NULL; a pointer that is not 8-byte aligned (judged by its value
+ * alone); sh_rest_coeffs not in {0, 3, 8, 15}, or not 0 while d_sh_rest is NULL.  All six outputs NULL: success, nothing is
+ * launched.  N = gs_scene_num_vertices.  Cost: INTEGRATION.md, 3h. */
+typedef struct {
+    const double* d_colour;   /* [N][3]  dL/d(r g b of the record); nullable = zeros */
+    const double* d_opacity;  /* [N]     dL/d(opacity of the record); nullable = zeros */
+    const double* d_conic;    /* [N][3]  c00 c01 c11; nullable = zeros */
+    const double* d_uv;       /* [N][2]  nullable = zeros */
+    double* d_means;          /* [N][3]  ADDED to */
+    double* d_log_scales;     /* [N][3]  ADDED to */
+    double* d_quats;          /* [N][4]  w x y z, ADDED to */
+    double* d_opacity_logits; /* [N]     ADDED to */
+    double* d_sh_dc;          /* [N][3]  ADDED to */
+    double* d_sh_rest;        /* [N][sh_rest_coeffs][3], RGB innermost, ADDED to */
+    uint32_t sh_rest_coeffs;  /* 0, 3, 8 or 15: higher bands are not written */
+} gs_project_grads;
+int gs_project_backward(gs_renderer* r, const gs_project_grads* g);
 /* Test hook (tests/test_gpu_expf.py): evaluate the blend's exp() implementations ON THE DEVICE over the binary32 values with
  * bit patterns [first_bits, first_bits + count) (the negative floats run from 0x80000000 = -0 to 0xFF800000 = -inf).
  * block_sums[j] = sum over block j of 2^20 consecutive patterns of  bits(expf(x)) * ((bits(x) * 0x9E3779B1) | 1)  mod 2^64,
