@@ -44,7 +44,12 @@ U53 = 2.0 ** -53
 K_PATH = 660
 OUTPUTS = {"means": (3,), "log_scales": (3,), "quats": (4,), "opacity_logits": (), "sh_dc": (3,), "sh_rest": None}   # sh_rest: (K, 3)
 INPUTS = {"colour": (3,), "opacity": (), "conic": (3,), "uv": (2,)}
-MUTATIONS = ("no_direction", "clamp_is_constant", "no_tangent_projection", "no_comp_cov", "red_always_flows", "s_not_squared")
+MUTATIONS = ("no_direction", "clamp_is_constant", "no_tangent_projection", "no_comp_cov", "red_always_flows", "s_not_squared",
+             "view_transposed", "view_transposed_in_a", "view_transposed_in_g_j", "camera_at_origin")
+# the last four are invisible under a camera at the origin with a symmetric view rotation (the default one): each of the first three
+# reads the view matrix's 3 x 3 block transposed in ONE of its uses (g_p <- g_t; A = J V; g_Jaa, g_Ja2 <- g_A), the fourth takes the
+# view direction from p instead of p - camera_position.  tests/test_backward_cameras_api.py asserts both halves of that.
+RECORD = {"uv": 2, "conic": 3, "opacity": 1, "rgb_raw": 3, "rgb": 3}
 
 _F = np.float32
 SH_C0, SH_C1 = float(_F(0.28209479177387814)), float(_F(0.4886025119029199))
@@ -184,7 +189,10 @@ def backward(pos, scale, quat, opacity, sh, uniforms, visible, red_flows, colour
     record.  visible, red_flows: bool [n], the frame's decisions.  colour [n][3], opacity_grad [n], conic [n][3], uv [n][2]:
     float64 input gradients, None = zeros.  Returns dict(means, log_scales, quats, opacity_logits, sh_dc, sh_rest: float64 sums of
     the shapes gs_project_grads documents (culled rows 0); A = {name: magnitudes}; k = {name: the counted roundings};
-    visible; binds = bool [n][2]; det_raw = float64 [n] (NaN where culled); margin = {"clamp": |tx/tz| / lim, "r": rgb0}."""
+    visible; binds = bool [n][2]; det_raw = float64 [n] (NaN where culled); margin = {"clamp": |tx/tz| / lim, "r": rgb0};
+    record = {field of RECORD: (value [n][c], magnitude [n][c], counted roundings)}, the forward value of F (NaN where culled): uv,
+    the conic's three numbers, the opacity after the antialiased factor, rgb before and after red's clamp -- each within
+    count 2^-53 magnitude of exact, by the rules above."""
     assert mutate is None or mutate in MUTATIONS, mutate
     assert sh_rest_coeffs in (0, 3, 8, 15)
     n = len(pos)
@@ -198,6 +206,10 @@ def backward(pos, scale, quat, opacity, sh, uniforms, visible, red_flows, colour
     cam = np.asarray(u["camera_position"], f64).reshape(-1)[:3]
     P = lambda r, c: float(pm[c * 4 + r])   # noqa: E731
     Vm = lambda r, c: float(vm[c * 4 + r])  # noqa: E731
+    Vt = lambda r, c: float(vm[r * 4 + c])  # noqa: E731  (the transposed read of the mutations)
+    V_a = Vt if mutate == "view_transposed_in_a" else Vm
+    V_gj = Vt if mutate == "view_transposed_in_g_j" else Vm
+    V_gp = Vt if mutate == "view_transposed" else Vm
 
     def g_in(a, shape):
         if a is None:
@@ -227,7 +239,7 @@ def backward(pos, scale, quat, opacity, sh, uniforms, visible, red_flows, colour
     j_a2 = [(-(f * t[a]) / t2sq).where(~binds[:, a], -(f * V(cconst[:, a])) / t[2]) for a, f in ((0, fx), (1, fy))]
     j_aa = [fx / t[2], fy / t[2]]
     # A = J V  (2 x 3)
-    A = [[j_aa[i] * Vm(i, c) + j_a2[i] * Vm(2, c) for c in range(3)] for i in range(2)]
+    A = [[j_aa[i] * V_a(i, c) + j_a2[i] * V_a(2, c) for c in range(3)] for i in range(2)]
     nrm = _sum([q[0] * q[0], q[1] * q[1], q[2] * q[2], q[3] * q[3]]).sqrt()
     qh = [qq / nrm for qq in q]
     w_, x_, y_, z_ = qh
@@ -242,6 +254,8 @@ def backward(pos, scale, quat, opacity, sh, uniforms, visible, red_flows, colour
     m00, m11, m01 = cov00 + DILATION, cov11 + DILATION, cov01
     det = m00 * m11 - m01 * m01
     c00, c01, c11 = m11 / det, -m01 / det, m00 / det
+    rec_uv = [((h[0] / h[3] + 1.0) * W - 1.0).pow2(-1), ((h[1] / h[3] + 1.0) * H - 1.0).pow2(-1)]
+    rec_op = o
 
     # ---- backward: conic (and comp) -> cov
     gc00, gc01, gc11 = V(g_con[:, 0]), V(g_con[:, 1]), V(g_con[:, 2])
@@ -257,6 +271,7 @@ def backward(pos, scale, quat, opacity, sh, uniforms, visible, red_flows, colour
         comp = (safe / det).sqrt()
         g_comp = V(g_op) * o
         g_o = (V(g_op) * comp).where(pos_raw, 0.0)
+        rec_op = (o * comp).where(pos_raw, 0.0)
         if mutate != "no_comp_cov":
             g_detraw = (g_comp.pow2(-1) / (comp * det)).where(pos_raw, 0.0)
             g_det = g_det + (-(g_comp * comp).pow2(-1) / det).where(pos_raw, 0.0)
@@ -276,8 +291,8 @@ def backward(pos, scale, quat, opacity, sh, uniforms, visible, red_flows, colour
     g_A = [[_sum([g_M[i][k] * R[c][k] for k in range(3)]) for c in range(3)] for i in range(2)]
     g_R = [[A[0][c] * g_M[0][k] + A[1][c] * g_M[1][k] for k in range(3)] for c in range(3)]
     # A = J V
-    g_Jaa = [_sum([g_A[i][c] * Vm(i, c) for c in range(3)]) for i in range(2)]
-    g_Ja2 = [_sum([g_A[i][c] * Vm(2, c) for c in range(3)]) for i in range(2)]
+    g_Jaa = [_sum([g_A[i][c] * V_gj(i, c) for c in range(3)]) for i in range(2)]
+    g_Ja2 = [_sum([g_A[i][c] * V_gj(2, c) for c in range(3)]) for i in range(2)]
     # J -> t
     t2cu = t2sq * t[2]
     g_t = [None, None, None]
@@ -291,7 +306,7 @@ def backward(pos, scale, quat, opacity, sh, uniforms, visible, red_flows, colour
             bound = (g_Ja2[a] * f * V(cconst[:, a])) / t2sq
         g_t2_terms += [-(g_Jaa[a] * f) / t2sq, free.where(~binds[:, a], bound)]
     g_t[2] = _sum(g_t2_terms)
-    g_p = [_sum([g_t[r] * Vm(r, c) for r in range(3)]) for c in range(3)]
+    g_p = [_sum([g_t[r] * V_gp(r, c) for r in range(3)]) for c in range(3)]
     # uv -> p
     h3sq = h[3] * h[3]
     for c in range(3):
@@ -313,7 +328,7 @@ def backward(pos, scale, quat, opacity, sh, uniforms, visible, red_flows, colour
         dot = _sum([qh[c] * g_qh[c] for c in range(4)])
         d_q = [(g_qh[c] - qh[c] * dot) / nrm for c in range(4)]
     # rgb -> sh, and -> d -> p
-    rel = [p[c] - float(cam[c]) for c in range(3)]
+    rel = [p[c] - (0.0 if mutate == "camera_at_origin" else float(cam[c])) for c in range(3)]
     ln = _sum([rel[0] * rel[0], rel[1] * rel[1], rel[2] * rel[2]]).sqrt()
     d = [r / ln for r in rel]
     basis = sh_basis(*d)
@@ -348,14 +363,23 @@ def backward(pos, scale, quat, opacity, sh, uniforms, visible, red_flows, colour
         out[name], mags[name] = val.reshape(shapes[name]), mag.reshape(shapes[name])
         counts[name] = max([v.k for v in vs], default=0)
         assert counts[name] <= K_PATH, (name, counts[name])
+    rgb_raw = [_sum([basis[j][0] * V(shv[:, j, k]) for j in range(16)]) + 0.5 for k in range(3)]
     rgb0 = np.full(n, np.nan)
-    rgb0[idx] = (_sum([basis[j][0] * V(shv[:, j, 0]) for j in range(16)]) + 0.5).v
+    rgb0[idx] = rgb_raw[0].v
+    fields = dict(uv=rec_uv, conic=[c00, c01, c11], opacity=[rec_op], rgb_raw=rgb_raw,
+                  rgb=[rgb_raw[0].where(np.asarray(red_flows, bool)[idx], 0.0), rgb_raw[1], rgb_raw[2]])
+    record = {}
+    for name, vs in fields.items():
+        val, mag = np.full((n, len(vs)), np.nan), np.full((n, len(vs)), np.nan)
+        for c, v in enumerate(vs):
+            val[idx, c], mag[idx, c] = v.v, v.m
+        record[name] = (val, mag, max(v.k for v in vs))
     lim_ratio = np.full((n, 2), np.nan)
     with np.errstate(divide="ignore", invalid="ignore"):
         _, _, _, lim = clamp_branches(pos, u)
         lim_ratio[idx] = np.abs(ratio[idx].astype(f64)) / lim.astype(f64)[None, :]
     out.update(A=mags, k=counts, visible=np.asarray(visible, bool), binds=binds_all & np.asarray(visible, bool)[:, None],
-               det_raw=det_raw_full, margin=dict(clamp=lim_ratio, r=rgb0))
+               det_raw=det_raw_full, margin=dict(clamp=lim_ratio, r=rgb0), record=record)
     return out
 
 

@@ -49,18 +49,14 @@ def test_d_colour_is_the_lift_of_grad_rgb_bit_for_bit(walked, oracle):
     assert got["terms"]["colour"].sum() - got["terms"]["opacity"].sum() == got["clamped"]
 
 
-def _dense_autograd(ref, w, h, pairs, G, ga):
+def _dense_loss(conic, opac, uv, col, ref, w, h, pairs, G, ga):
     """render.comp:66-88 over the given pair sets as one dense differentiable function per tile, in torch float64 on the CPU:
     image = sum_e colour_e alpha_e T_e, T_e the product of (1 - alpha) over the blended entries in front, out_alpha = 1 - T_f;
     alpha = o exp(power) where the pair flows, the constant 0.99 where it is clamped, 0 where the pixel does not blend the
-    entry.  Returns the gradients of  sum(G image) + sum(ga out_alpha)  with respect to the records' colour, opacity, conic, uv."""
+    entry.  conic [N][3], opac [N], uv [N][2], col [N][3]: torch float64 records of all N Gaussians.  Returns the scalar
+    sum(G image) + sum(ga out_alpha)."""
     import torch
-    attr, bounds, payload = ref["attr"], ref["boundaries"].astype(np.int64), ref["sorted_payload"]
-
-    def leaf(a):
-        return torch.tensor(np.asarray(a, np.float64), requires_grad=True)
-    conic, opac = leaf(attr["conic_opacity"][:, :3]), leaf(attr["conic_opacity"][:, 3])
-    uv, col = leaf(attr["uv"][:, :2]), leaf(attr["color_radii"][:, :3])
+    bounds, payload = ref["boundaries"].astype(np.int64), ref["sorted_payload"]
     clamp = float(np.float32(0.99))
     tx = (w + 15) // 16
     loss = torch.zeros((), dtype=torch.float64)
@@ -89,7 +85,19 @@ def _dense_autograd(ref, w, h, pairs, G, ga):
         image = torch.einsum("ep,ec->pc", alpha * T, col[ids])
         loss = loss + (image * torch.as_tensor(G[ys, xs].astype(np.float64))).sum()
         loss = loss + ((1.0 - through[-1]) * torch.as_tensor(ga[ys, xs].astype(np.float64))).sum()
-    loss.backward()
+    return loss
+
+
+def _dense_autograd(ref, w, h, pairs, G, ga):
+    """The gradients of _dense_loss with respect to the oracle's records' colour, opacity, conic, uv."""
+    import torch
+    attr = ref["attr"]
+
+    def leaf(a):
+        return torch.tensor(np.asarray(a, np.float64), requires_grad=True)
+    conic, opac = leaf(attr["conic_opacity"][:, :3]), leaf(attr["conic_opacity"][:, 3])
+    uv, col = leaf(attr["uv"][:, :2]), leaf(attr["color_radii"][:, :3])
+    _dense_loss(conic, opac, uv, col, ref, w, h, pairs, G, ga).backward()
     return dict(colour=col.grad.numpy(), opacity=opac.grad.numpy(), conic=conic.grad.numpy(), uv=uv.grad.numpy())
 
 
