@@ -24,7 +24,8 @@ BLOB_PLANES = 59
 
 # the device code of libgs3d_hip.so: one translation unit per stage + the shared device headers
 KERNEL_SOURCES = ("gs_device.h", "gs_bin.h", "gs_tile_cull.h", "gs_scene.hip", "gs_preprocess.hip", "gs_radix.hip", "gs_bin_l1.hip", "gs_bin_l2.hip",
-                  "gs_blend.hip", "gs_contrib.hip", "gs_features.hip", "gs_lift.hip", "gs_backward.hip", "gs_project_backward.hip", "gs_wave_f64.h", "gs_kernels.h")
+                  "gs_blend.hip", "gs_contrib.hip", "gs_features.hip", "gs_lift.hip", "gs_backward.hip", "gs_project_backward.hip", "gs_camera_backward.hip", "gs_project_chain.h",
+                  "gs_wave_f64.h", "gs_kernels.h")
 
 
 def library_source_hash():
@@ -62,7 +63,7 @@ SYMBOLS = ["gs_last_error", "gs_device_count", "gs_read_ply", "gs_activate_recor
            "gs_deactivate_vertices", "gs_write_ply", "gs_scene_to_device_arrays", "gs_scene_download_records", "gs_scene_save_ply",
            "gs_scene_destroy", "gs_renderer_create", "gs_renderer_destroy", "gs_camera_uniforms",
            "gs_render", "gs_render_host", "gs_synchronize", "gs_set_timing", "gs_set_frames_in_flight", "gs_set_sort_path", "gs_set_exp_mode", "gs_set_graph_mode", "gs_set_blend_lockstep", "gs_get_blend_lockstep", "gs_set_level1_fused", "gs_get_level1_fused", "gs_set_tile_cull", "gs_get_tile_cull", "gs_get_listed_instances", "gs_set_blend_contraction", "gs_set_antialiased", "gs_get_antialiased", "gs_get_timing_totals",
-           "gs_get_frame_intervals", "gs_get_stats", "gs_poll_stats", "gs_debug_download", "gs_accumulate_contributions", "gs_blend_features", "gs_lift_pixels", "gs_blend_backward", "gs_project_backward", "gs_debug_expf_scan", "gs_debug_alpha_cut_scan", "gs_renderer_stream",
+           "gs_get_frame_intervals", "gs_get_stats", "gs_poll_stats", "gs_debug_download", "gs_accumulate_contributions", "gs_blend_features", "gs_lift_pixels", "gs_blend_backward", "gs_project_backward", "gs_camera_backward", "gs_camera_uniforms_backward", "gs_debug_expf_scan", "gs_debug_alpha_cut_scan", "gs_renderer_stream",
            "gs_dist_unique_id", "gs_dist_create", "gs_dist_rank", "gs_dist_world", "gs_dist_pose_count",
            "gs_dist_broadcast_scene", "gs_dist_broadcast_scene_ex", "gs_dist_verify", "gs_dist_destroy"]
 
@@ -212,8 +213,18 @@ class ProjectGrads(C.Structure):
                 ("d_sh_dc", C.c_void_p), ("d_sh_rest", C.c_void_p), ("sh_rest_coeffs", C.c_uint32)]
 
 
+class CameraGrads(C.Structure):
+    """gs_camera_grads: the four per-Gaussian input gradients and the three uniform-gradient sums of gs_camera_backward
+    (include/gs3d_hip.h)."""
+    _fields_ = [("d_colour", C.c_void_p), ("d_opacity", C.c_void_p), ("d_conic", C.c_void_p), ("d_uv", C.c_void_p),
+                ("d_view_mat", C.c_void_p), ("d_proj_mat", C.c_void_p), ("d_camera_position", C.c_void_p)]
+
+
+CAMERA_BACKWARD_LANES = 131072  # GS_CAMERA_BACKWARD_LANES: a scene with more Gaussians is strided over by gs_camera_backward's lanes
+
 _FEATURE_MAPS_FN = None  # the torch.autograd.Function of Renderer.differentiable_feature_maps, defined when first asked for
 _RENDER_FN = None        # ... and of Renderer.differentiable_render
+_RENDER_POSED_FN = None  # ... and of Renderer.differentiable_render_posed
 
 
 def _complete_callers_work(*tensors):
@@ -311,6 +322,98 @@ def _render_function():
 
         _RENDER_FN = RenderFunction
     return _RENDER_FN
+
+
+def _render_posed_function():
+    """The autograd function behind Renderer.differentiable_render_posed; torch is imported here, not with the module."""
+    global _RENDER_POSED_FN
+    if _RENDER_POSED_FN is None:
+        import torch
+
+        class RenderPosedFunction(torch.autograd.Function):
+            """rgb (and alpha) of one frame seen from the pose (position, rotation); the backward is blend_backward, then
+            camera_backward and camera_pose_gradient for the pose, and project_backward only for scene tensors that ask."""
+
+            @staticmethod
+            def forward(ctx, renderer, width, height, fov, near, far, want_alpha, position, rotation, means, log_scales, quats,
+                        opacity_logits, sh_dc, sh_rest):
+                params = dict(means=means, log_scales=log_scales, quats=quats, opacity_logits=opacity_logits, sh_dc=sh_dc, sh_rest=sh_rest)
+                pose = [np.ascontiguousarray(t.detach().to("cpu", torch.float32).numpy().reshape(-1)) for t in (position, rotation)]
+                if pose[0].shape != (3,) or pose[1].shape != (4,):
+                    raise ValueError(f"position must hold 3 values and rotation 4 (w x y z), not {pose[0].shape[0]} and {pose[1].shape[0]}")
+                cam = make_camera(position=pose[0], rotation=pose[1], fov=fov, near=near, far=far)
+                uniforms = camera_uniforms(cam, int(width), int(height))
+                renderer.synchronize()  # (no frame of this renderer may straddle the update)
+                if any(v is not None for v in params.values()):
+                    renderer.scene.update_from_tensors(0, **{k: (None if v is None else v.detach().contiguous()) for k, v in params.items()})
+                rgba = torch.empty((int(height), int(width), 4), dtype=torch.float32, device=f"cuda:{int(renderer.scene.device)}")
+                renderer.render(uniforms, rgba.data_ptr())
+                renderer.synchronize()
+                ctx.renderer, ctx.frame, ctx.cam, ctx.size = renderer, renderer._frames, cam, (int(width), int(height))
+                ctx.pose = [(t.dtype, t.device, tuple(t.shape)) for t in (position, rotation)]
+                ctx.shapes = {k: (None if v is None else tuple(v.shape)) for k, v in params.items()}
+                rgb = rgba[..., :3].contiguous()
+                if not want_alpha:
+                    return rgb
+                return rgb, renderer.feature_maps(alpha=True)["alpha"]
+
+            @staticmethod
+            def backward(ctx, grad_rgb, grad_alpha=None):
+                rend = ctx.renderer
+                if rend._frames != ctx.frame:
+                    raise RuntimeError(f"differentiable_render_posed: the forward rendered frame {ctx.frame} of this renderer, which has "
+                                       f"rendered frame {rend._frames} since; the gradient of another frame is not returned")
+                dev = f"cuda:{int(rend.scene.device)}"
+                if grad_rgb is None:
+                    grad_rgb = torch.zeros(rend._frame_hw + (3,), dtype=torch.float32, device=dev)
+                d = rend.blend_backward(grad_rgb.contiguous().float(), None if grad_alpha is None else grad_alpha.contiguous().float(),
+                                        colour=True, opacity=True, conic=True, uv=True)
+                pose = [None, None]
+                if ctx.needs_input_grad[7] or ctx.needs_input_grad[8]:
+                    found = camera_pose_gradient(ctx.cam, ctx.size[0], ctx.size[1], rend.camera_backward(**d))
+                    pose = [torch.as_tensor(g).to(device=device, dtype=dtype).reshape(shape) if need else None
+                            for g, (dtype, device, shape), need in zip(found, ctx.pose, ctx.needs_input_grad[7:9])]
+                names = ("means", "log_scales", "quats", "opacity_logits", "sh_dc", "sh_rest")
+                grads = [None] * 6
+                if any(ctx.needs_input_grad[9:]):
+                    rest = ctx.shapes["sh_rest"]
+                    k = 0 if rest is None else int(rest[-2])
+                    n = int(rend.scene.num_vertices)
+                    shapes = dict(means=(n, 3), log_scales=(n, 3), quats=(n, 4), opacity_logits=(n,), sh_dc=(n, 3), sh_rest=(n, k, 3))
+                    out = {name: torch.zeros(shapes[name], dtype=torch.float64, device=dev)
+                           for name, need in zip(names, ctx.needs_input_grad[9:]) if need and (name != "sh_rest" or k)}
+                    rend.project_backward(out=out, **d)
+                    grads = [out[name].to(torch.float32).reshape(ctx.shapes[name]) if name in out else None for name in names]
+                    if ctx.needs_input_grad[14] and not k:
+                        grads[5] = torch.zeros(ctx.shapes["sh_rest"], dtype=torch.float32, device=dev)
+                return (None, None, None, None, None, None, None, *pose, *grads)
+
+        _RENDER_POSED_FN = RenderPosedFunction
+    return _RENDER_POSED_FN
+
+
+def camera_pose_gradient(cam, width, height, d):
+    """(d_position (3,), d_rotation (4,)) float64 numpy: the gradients with respect to a camera's position and RAW quaternion
+    (w x y z; a caller who keeps it unit projects onto the sphere's tangent themselves) from `d`, the dict of
+    Renderer.camera_backward -- view_mat (16,), proj_mat (16,), camera_position (3,), float64; a missing or None entry is zeros;
+    device tensors are brought to the host here (gs_camera_uniforms_backward: host arithmetic, binary64)."""
+    def host(name, count):
+        t = d.get(name)
+        if t is None:
+            return np.zeros(count, np.float64)
+        a = np.ascontiguousarray(t.detach().cpu().numpy() if hasattr(t, "detach") else t, np.float64).reshape(-1)
+        if a.shape != (count,):
+            raise ValueError(f"{name}: {a.shape[0]} values, {count} are needed")
+        return a
+    unknown = sorted(set(d) - {"view_mat", "proj_mat", "camera_position"})
+    if unknown:
+        raise TypeError(f"d: unknown member(s) {unknown}")
+    gv, gp, gc = host("view_mat", 16), host("proj_mat", 16), host("camera_position", 3)
+    cam = np.ascontiguousarray(cam, CAMERA_DT)
+    d_position, d_rotation = np.zeros(3, np.float64), np.zeros(4, np.float64)
+    _check(lib().gs_camera_uniforms_backward(_p(cam), C.c_uint32(int(width)), C.c_uint32(int(height)), _p(gv), _p(gp), _p(gc),
+                                             _p(d_position), _p(d_rotation)))
+    return d_position, d_rotation
 
 
 def _tensor_exact(name, t, dtypes, shape, device, owner="Renderer.contributions"):
@@ -841,6 +944,53 @@ class Renderer:
         gradient.  A backward after this renderer has been handed another frame raises RuntimeError instead of returning the
         gradient of a different frame; so one backward per forward, before the next forward."""
         return _render_function().apply(self, uniforms, bool(want_alpha), means, log_scales, quats, opacity_logits, sh_dc, sh_rest)
+
+    def camera_backward(self, colour=None, opacity=None, conic=None, uv=None, view_mat=True, proj_mat=True, camera_position=True):
+        """The camera half of the last frame's backward (gs_camera_backward): from the same four float64 per-Gaussian gradients
+        project_backward takes (what blend_backward returns; None = zeros) the float64 gradients with respect to the frame's
+        uniforms, summed over its visible Gaussians: view_mat (16,) and proj_mat (16,) laid out as the uniforms' matrices
+        (element 4 c + r; row 3 of view_mat and row 2 of proj_mat are not touched), camera_position (3,).  Each output is a
+        tensor to ADD into, True to have zeros allocated, or None to skip.  The gradient is the one AT THE FRAME'S VALUES with the
+        frame's decisions as constants; the intrinsics carry none.  No atomics: two calls give the same bits.  The stream and the
+        wait for torch's current stream are lift_pixels's.  camera_pose_gradient carries the result on to a camera's position
+        and rotation; differentiable_render_posed is all of it behind one autograd function.  Returns
+        synchronised, with a dict of what was asked for (keys view_mat, proj_mat, camera_position)."""
+        owner = "Renderer.camera_backward"
+        n = int(self.scene.num_vertices)
+        dev = self.scene.device
+        g = CameraGrads()
+        ins = dict(colour=(colour, (n, 3)), opacity=(opacity, (n,)), conic=(conic, (n, 3)), uv=(uv, (n, 2)))
+        for name, (t, shape) in ins.items():
+            if t is not None:
+                setattr(g, "d_" + name, _tensor_exact(name, t, ("float64",), shape, dev, owner))
+        shapes = dict(view_mat=(16,), proj_mat=(16,), camera_position=(3,))
+        result = {}
+        for name, t in dict(view_mat=view_mat, proj_mat=proj_mat, camera_position=camera_position).items():
+            if t is None:
+                continue
+            if t is True:
+                import torch
+                t = torch.zeros(shapes[name], dtype=torch.float64, device=f"cuda:{int(dev)}")
+            setattr(g, "d_" + name, _tensor_exact(name, t, ("float64",), shapes[name], dev, owner))
+            result[name] = t
+        _complete_callers_work(colour, opacity, conic, uv, *result.values())  # (the zeros allocated above among them)
+        _check(lib().gs_camera_backward(self._h, C.byref(g)))
+        return result
+
+    def differentiable_render_posed(self, width, height, position, rotation, means=None, log_scales=None, quats=None, opacity_logits=None,
+                                    sh_dc=None, sh_rest=None, fov=45.0, near=0.1, far=1000.0, want_alpha=False):
+        """One frame as a torch.autograd.Function of the camera's pose -- position (3,) and rotation (4,) (w x y z), torch tensors
+        on any device, float32 or float64 -- and, where given, of the six scene tensors of differentiable_render.  The forward
+        builds make_camera / camera_uniforms from the pose's values ROUNDED TO FLOAT32 (the quaternion as it is, not normalised),
+        refreshes the scene from whichever of the six tensors are given (all None: the scene stays as it is), renders and
+        synchronises; it returns rgb (H, W, 3), and with want_alpha also alpha (H, W).  The backward is blend_backward, then
+        camera_backward and camera_pose_gradient for the pose, returned in the leaves' dtype and on their device, and
+        project_backward only if a scene tensor requires a gradient.  The gradient is the one AT THE FRAME'S VALUES with its
+        decisions as constants, as differentiable_render states it; rotation's is that of the RAW quaternion (an optimiser that
+        normalises after each step needs no more; fov, near and far carry none).  One backward per forward, before the next
+        forward: a backward after this renderer has been handed another frame raises RuntimeError."""
+        return _render_posed_function().apply(self, int(width), int(height), float(fov), float(near), float(far), bool(want_alpha),
+                                              position, rotation, means, log_scales, quats, opacity_logits, sh_dc, sh_rest)
 
     def differentiable_feature_maps(self, features):
         """feature_maps(features)["out"] as a torch.autograd.Function: features (N, C) float32 on the renderer's device -> the

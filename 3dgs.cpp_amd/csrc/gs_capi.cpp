@@ -41,4 +41,14 @@ int gs_camera_uniforms(const gs_camera* cam, uint32_t width, uint32_t height, gs
     });
 }
 
+int gs_camera_uniforms_backward(const gs_camera* cam, uint32_t width, uint32_t height, const double d_view_mat[16],
+                                const double d_proj_mat[16], const double d_camera_position[3], double d_position[3], double d_rotation[4]) {
+    return guarded([&] {
+        if (!cam || !d_view_mat || !d_proj_mat || !d_camera_position || !d_position || !d_rotation)
+            throw Error(GS_ERR_INVALID, "null argument");
+        if (width == 0 || height == 0) throw Error(GS_ERR_INVALID, "empty framebuffer");
+        gs::host::camera_uniforms_backward(*cam, width, height, d_view_mat, d_proj_mat, d_camera_position, d_position, d_rotation);
+    });
+}
+
 }  // extern "C"

@@ -150,6 +150,70 @@ inline void camera_uniforms(const gs_camera& cam, uint32_t width, uint32_t heigh
     out->tan_fovy = tan_fovy;
 }
 
+// gs_camera_uniforms_backward (gs3d_hip.h): the gradient of the exact real function behind camera_uniforms with respect to the
+// camera's position and raw quaternion, binary64, at the binary32 camera values.  No reference counterpart.  [row][column] here.
+//     M = [R(q) | position; 0 0 0 1],  R = mat4_cast(q), q not normalised;   view = M^-1;   proj = persp view;
+//     view rows 1, 2 and proj row 1 negated;   camera_position = position.
+// g arrays are laid out as the uniforms' matrices (element 4 c + r); every row of them is taken.
+inline void camera_uniforms_backward(const gs_camera& cam, uint32_t width, uint32_t height, const double* g_view_mat, const double* g_proj_mat,
+                                     const double* g_camera_position, double* d_position, double* d_rotation) {
+    const double w = cam.rotation[0], x = cam.rotation[1], y = cam.rotation[2], z = cam.rotation[3];
+    const double R[3][3] = {{1.0 - 2.0 * (y * y + z * z), 2.0 * (x * y - w * z), 2.0 * (x * z + w * y)},
+                            {2.0 * (x * y + w * z), 1.0 - 2.0 * (x * x + z * z), 2.0 * (y * z - w * x)},
+                            {2.0 * (x * z - w * y), 2.0 * (y * z + w * x), 1.0 - 2.0 * (x * x + y * y)}};
+    // M^-1 = [R^-1 | -R^-1 position]: R is orthogonal only for a unit quaternion, so the adjugate over the determinant
+    double Ri[3][3];
+    const double det = R[0][0] * (R[1][1] * R[2][2] - R[1][2] * R[2][1]) - R[0][1] * (R[1][0] * R[2][2] - R[1][2] * R[2][0]) +
+                       R[0][2] * (R[1][0] * R[2][1] - R[1][1] * R[2][0]);
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) {
+            const int r1 = (c + 1) % 3, r2 = (c + 2) % 3, c1 = (r + 1) % 3, c2 = (r + 2) % 3;  // cofactor of R[c][r]
+            Ri[r][c] = (R[r1][c1] * R[r2][c2] - R[r1][c2] * R[r2][c1]) / det;
+        }
+    double Mi[4][4] = {};
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) Mi[r][c] = Ri[r][c];
+        Mi[r][3] = -((Ri[r][0] * (double)cam.position[0] + Ri[r][1] * (double)cam.position[1]) + Ri[r][2] * (double)cam.position[2]);
+    }
+    Mi[3][3] = 1.0;
+    // persp, as the forward's real function: tan(atan(tan_fovy) * 2 / 2) = tan_fovy, aspect * tan_fovy = tan_fovx
+    const double tan_fovx = std::tan((double)cam.fov * 0.01745329251994329576923690768489 / 2.0);
+    const double tan_fovy = tan_fovx * (double)height / (double)width;
+    const double nearp = cam.near_plane, farp = cam.far_plane;
+    double persp[4][4] = {};
+    persp[0][0] = 1.0 / tan_fovx;
+    persp[1][1] = 1.0 / tan_fovy;
+    persp[2][2] = -(farp + nearp) / (farp - nearp);
+    persp[3][2] = -1.0;
+    persp[2][3] = -(2.0 * farp * nearp) / (farp - nearp);
+    // the flips undone, then g_view += persp^T g_proj
+    double gv[4][4], gp[4][4];
+    for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 4; ++c) {
+            gv[r][c] = (r == 1 || r == 2) ? -g_view_mat[c * 4 + r] : g_view_mat[c * 4 + r];
+            gp[r][c] = (r == 1) ? -g_proj_mat[c * 4 + r] : g_proj_mat[c * 4 + r];
+        }
+    for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 4; ++c)
+            for (int e = 0; e < 4; ++e) gv[r][c] += persp[e][r] * gp[e][c];
+    // g_M = -M^-T g_view M^-T
+    double tmp[4][4] = {}, gM[4][4] = {};
+    for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 4; ++c)
+            for (int e = 0; e < 4; ++e) tmp[r][c] += Mi[e][r] * gv[e][c];
+    for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 4; ++c) {
+            for (int e = 0; e < 4; ++e) gM[r][c] += tmp[r][e] * Mi[c][e];
+            gM[r][c] = -gM[r][c];
+        }
+    for (int c = 0; c < 3; ++c) d_position[c] = gM[c][3] + g_camera_position[c];
+    const double(*G)[4] = gM;  // the 3 x 3 block is dL/dR
+    d_rotation[0] = 2.0 * (z * G[1][0] - y * G[2][0] - z * G[0][1] + x * G[2][1] + y * G[0][2] - x * G[1][2]);
+    d_rotation[1] = 2.0 * (y * G[1][0] + z * G[2][0] + y * G[0][1] - 2.0 * x * G[1][1] + w * G[2][1] + z * G[0][2] - w * G[1][2] - 2.0 * x * G[2][2]);
+    d_rotation[2] = 2.0 * (-2.0 * y * G[0][0] + x * G[1][0] - w * G[2][0] + x * G[0][1] + z * G[2][1] + w * G[0][2] + z * G[1][2] - 2.0 * y * G[2][2]);
+    d_rotation[3] = 2.0 * (-2.0 * z * G[0][0] + w * G[1][0] + x * G[2][0] - w * G[0][1] - 2.0 * z * G[1][1] + y * G[2][1] + x * G[0][2] + y * G[1][2]);
+}
+
 constexpr int kRecordFloats = 62;  // VertexStorage, GSScene.cpp:17-24
 constexpr int kVertexFloats = 60;  // GSScene::Vertex, GSScene.h:41-46
 

@@ -1,4 +1,4 @@
-// gs_kernels.h -- launch wrappers of the gfx950 kernels (gs_scene / gs_preprocess / gs_radix / gs_bin_l1 / gs_bin_l2 / gs_blend / gs_contrib / gs_features / gs_lift / gs_backward / gs_project_backward .hip).
+// gs_kernels.h -- launch wrappers of the gfx950 kernels (gs_scene / gs_preprocess / gs_radix / gs_bin_l1 / gs_bin_l2 / gs_blend / gs_contrib / gs_features / gs_lift / gs_backward / gs_project_backward / gs_camera_backward .hip).
 // Host-side declarations only; everything takes raw device pointers + a stream.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -309,5 +309,13 @@ void launch_blend_backward(const TileLists& t, const float* grad_rgb, const floa
 // antialiased: what the frame ran with.  One writer per element, no atomics.
 void launch_project_backward(const SceneView& sv, const uint32_t* tiles, const AttrRecord* rec, const gs_uniforms& u, bool antialiased,
                              const gs_project_grads& g, hipStream_t s);
+
+// gs_camera_backward (gs3d_hip.h; gs_camera_backward.hip): the camera half of the backward over the same inputs: the 27 sums over
+// the Gaussians with tiles[id] != 0 are ADDED to g's three output arrays (nullable: skipped).  Two launches: at most
+// GS_CAMERA_BACKWARD_LANES lanes striding over sv, one row of 27 partials per workgroup into `partials` (the renderer's, at least
+// camera_backward_partials() doubles), then one wave that adds the rows in index order.  No atomics: the same bits every call.
+size_t camera_backward_partials();
+void launch_camera_backward(const SceneView& sv, const uint32_t* tiles, const AttrRecord* rec, const gs_uniforms& u, bool antialiased,
+                            const gs_camera_grads& g, double* partials, hipStream_t s);
 
 }  // namespace gs

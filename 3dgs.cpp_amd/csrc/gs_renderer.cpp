@@ -837,7 +837,7 @@ struct gs_renderer {
     }
 
     // What the passes over the last frame's tile lists do after their own argument checks (gs_accumulate_contributions,
-    // gs_blend_features, gs_lift_pixels, gs_blend_backward, gs_project_backward), in this order: queued frames retire (an overflowed one is re-run: the lists are the last
+    // gs_blend_features, gs_lift_pixels, gs_blend_backward, gs_project_backward, gs_camera_backward), in this order: queued frames retire (an overflowed one is re-run: the lists are the last
     // frame's, complete); without a frame the call is refused; with nothing asked for it is done; otherwise launch(lists, stream)
     // enqueues the pass over the frame's own lists on the last frame's stream and the call waits for it.
     template <class Launch>
@@ -856,6 +856,7 @@ struct gs_renderer {
     // The reference's lists of the last frame.  An unculled frame's own lists are those.  For a culled one: level 2 once more over that
     // frame's candidate records with BinLaunch::reference_boxes, into buffers and counters of the taps' own, which the renderer keeps
     // across frames; whether they hold the last frame's lists is LastFrame::tap_lists.  Nothing of the frame moves.
+    DevBuf<double> camera_partials;  // gs_camera_backward's rows of 27 partial sums, one per workgroup (allocated on first use)
     DevBuf<uint32_t> tap_ranges, tap_sorted;
     DevBuf<gs::Counters> tap_counters;
     using Lists = std::pair<const uint32_t*, const uint32_t*>;  // (ranges, lists)
@@ -1354,6 +1355,31 @@ int gs_project_backward(gs_renderer* r, const gs_project_grads* g) {
             const gs::SceneView sv{sc->render_blob(), sc->cov3d.p, n, static_cast<uint32_t>(gs::blob_stride(n)),
                                    sc->sh_half ? sc->sh16.p : nullptr, sc->acut.p, sc->perm.p};
             gs::launch_project_backward(sv, r->last_frame.set->tiles.p, lists.rec, r->last_frame.u, r->last_frame.antialiased, *g, s);
+        });
+    });
+}
+
+int gs_camera_backward(gs_renderer* r, const gs_camera_grads* g) {
+    return guarded([&] {
+        if (!r || !g) throw Error(GS_ERR_INVALID, "null argument");
+        // (all by the members' values alone: nothing is dereferenced and no device is touched before they pass)
+        const struct { const void* p; const char* what; } ptrs[] = {
+            {g->d_colour, "d_colour must be 8-byte aligned"},     {g->d_opacity, "d_opacity must be 8-byte aligned"},
+            {g->d_conic, "d_conic must be 8-byte aligned"},       {g->d_uv, "d_uv must be 8-byte aligned"},
+            {g->d_view_mat, "d_view_mat must be 8-byte aligned"}, {g->d_proj_mat, "d_proj_mat must be 8-byte aligned"},
+            {g->d_camera_position, "d_camera_position must be 8-byte aligned"}};
+        for (const auto& q : ptrs)
+            if (reinterpret_cast<uintptr_t>(q.p) % 8 != 0) throw Error(GS_ERR_INVALID, q.what);
+        const bool asked = g->d_view_mat || g->d_proj_mat || g->d_camera_position;
+        r->over_last_frame(!asked, [&](const gs::TileLists& lists, hipStream_t s) {
+            r->rebuild_planes();  // visibility is the tiles tap's answer, as in gs_project_backward
+            r->camera_partials.ensure(gs::camera_backward_partials());
+            const gs_scene* sc = r->scene;
+            const uint32_t n = static_cast<uint32_t>(sc->n);
+            const gs::SceneView sv{sc->render_blob(), sc->cov3d.p, n, static_cast<uint32_t>(gs::blob_stride(n)),
+                                   sc->sh_half ? sc->sh16.p : nullptr, sc->acut.p, sc->perm.p};
+            gs::launch_camera_backward(sv, r->last_frame.set->tiles.p, lists.rec, r->last_frame.u, r->last_frame.antialiased, *g,
+                                       r->camera_partials.p, s);
         });
     });
 }

@@ -302,7 +302,7 @@ int gs_camera_uniforms(const gs_camera* cam, uint32_t width, uint32_t height, gs
  * an overflow of the instance buffers is detected at the next gs_synchronize/gs_get_stats,
  * which grows them and re-runs the frame (Renderer.cpp:541-563).
  *
- * "The last frame" -- what the stage taps, gs_accumulate_contributions, gs_blend_features, gs_lift_pixels, gs_blend_backward and gs_project_backward answer from -- is the
+ * "The last frame" -- what the stage taps, gs_accumulate_contributions, gs_blend_features, gs_lift_pixels, gs_blend_backward, gs_project_backward and gs_camera_backward answer from -- is the
  * most recently enqueued frame, once it has retired.  What an error of gs_render / gs_render_host leaves of it:
  *   * A REFUSED call changes nothing.  Refused (GS_ERR_INVALID, before any queued frame is waited for and before anything is
  *     allocated): a null argument, an empty framebuffer, a tile box beyond 16 bits, a resolution beyond the tile binning.  The
@@ -704,7 +704,8 @@ int gs_blend_backward(gs_renderer* r, const gs_blend_grads* g);
  *     parameters:  s = exp(ls),  o = 1 / (1 + exp(-l)),  q^ = q / |q|:  the derivatives are s d/ds, o (1 - o) d/do and
  *          (g - q^ (q^ . g)) / |q|, evaluated at the STORED values, |q| the stored quaternion's own norm in binary64 -- the
  *          gradients with respect to the six tensors gs_scene_to_device_arrays returns.
- * Radius, tile box, depth, alpha cut and the culls carry no gradient; neither does the camera.
+ * Radius, tile box, depth, alpha cut and the culls carry no gradient; neither does the camera HERE: its gradient is
+ * gs_camera_backward's, below.
  * With inputs g_colour[3], g_opacity, g_conic[3] (c00 c01 c11), g_uv[2] per Gaussian (binary64; a NULL array = zeros) every parameter
  * theta of a VISIBLE Gaussian -- one whose GS_STAGE_TILES value of that frame is not 0 -- receives  sum_x g_x dx/dtheta  over the
  * nine record values x (o' for the opacity), by the chain rule over the nodes above.  Everything is binary64 on exact conversions
@@ -741,6 +742,73 @@ typedef struct {
     uint32_t sh_rest_coeffs;  /* 0, 3, 8 or 15: higher bands are not written */
 } gs_project_grads;
 int gs_project_backward(gs_renderer* r, const gs_project_grads* g);
+/* The camera half of the backward of the LAST frame, gs_project_backward's sibling: from the same four per-Gaussian input
+ * gradients to the gradients with respect to the frame's gs_uniforms -- what refining a pose, tracking a camera against a held
+ * scene or registering a photograph need.  gs_camera_uniforms_backward (host) carries them on to the gs_camera's position and
+ * rotation.  No reference counterpart.  Two launches (gs_camera_backward.hip): the per-Gaussian chain is the very one
+ * gs_project_backward evaluates (gs_project_chain.h), followed by a reduction over the visible Gaussians; the pass reads the scene,
+ * the frame's records and visibility and the caller's four arrays, adds to the caller's three and writes nothing else but a
+ * scratch buffer of partial sums the renderer owns.  No per-frame kernel is involved.
+ *
+ * THE FUNCTION is the record function F above with the same branches as constants, exactly as they are there: each clamp's
+ * branch as k_preprocess took it in binary32, red's max(0, .) by the record, visibility by GS_STAGE_TILES, det_raw <= 0 in an
+ * antialiased frame.  It is differentiated with respect to the frame's uniforms instead of the Gaussian's parameters:
+ *     V[r][c] = view_mat[4 c + r], rows 0..2, columns 0..3: enters through t = V (p, 1) and through A = J V(3 x 3).  Row 3 is
+ *         not read by F: it carries no gradient and the element is left untouched.
+ *     P[r][c] = proj_mat[4 c + r], rows 0, 1 and 3: enters through h = P (p, 1) to u v.  Row 2 is not read by F: left untouched.
+ *     camera_position[0..2]: enters through d = (p - c) / |p - c| to rgb.
+ * CARRYING NO GRADIENT: tan_fovx, tan_fovy, width, height, lim_x, lim_y (the intrinsics -- fx, fy and the clamp's limits are
+ * constants here); the culls, radius, depth, tile box and alpha cut.
+ * For each of these 27 uniforms x the result is  sum over the visible Gaussians i of the last frame of  sum_y g_y[i] dy_i/dx
+ * over the nine record values y gs_project_backward lists.  With the chain's nodes (g_t = dL/dt, gA = dL/dA, g_h = dL/dh rows
+ * 0, 1, 3, g_d = dL/dd, jaa = J[a][a], ja2 = J[a][2]) Gaussian i's terms are
+ *     dV[r][c] = g_t[r] (p, 1)[c] + (r < 2 ? jaa[r] gA[r][c] : ja2[0] gA[0][c] + ja2[1] gA[1][c])  for c < 3;   dV[r][3] = g_t[r]
+ *     dP[r][c] = g_h[r] (p, 1)[c]
+ *     dc       = -(g_d - d (d . g_d)) / |p - c|
+ * Every operation is binary64 on exact conversions of the stored binary32 values and of the frame's binary32 uniforms; the
+ * association is unspecified, so the contract is a bound: with A_i the magnitude of Gaussian i's term (every input gradient,
+ * partial and product by its absolute value, the condition factors of h3, t2, the cov2D entries, det and det_raw carried along),
+ *     |result - exact| <= 650 * 2^-53 * sum_i A_i  +  (n_visible + 1) * 2^-53 * sum_i A_i   (+ 2^-53 of what the element held)
+ * -- the per-term path constant, and the summation of n_visible terms in any order plus the add into the caller's array.
+ * tests/camera_backward_reference.py derives it and counts both constants.
+ *   * Outputs are ADDED to: one add per element of what the call computed (zero them once; gradients accumulate over a camera
+ *     set).  An add of an exact zero may be omitted (it is: the element keeps its bits).
+ *   * All three outputs NULL: success, nothing is launched.  Every Gaussian culled: nothing is added.
+ *   * A Gaussian the frame culled is not touched: its inputs are not read, a NaN in its rows changes nothing.  A NaN in a visible
+ *     Gaussian's row reaches every output element that Gaussian has a term in.
+ *   * Two calls on the same frame with the same inputs give the same bits: no floating-point atomics anywhere in the pass, and
+ *     the association is fixed for a given N and build.  At most GS_CAMERA_BACKWARD_LANES lanes are launched, one per Gaussian in
+ *     the order the frame read the scene; a scene with more Gaussians is strided over (lane l takes l, l + LANES, ...).
+ *   * It answers for the last frame and ITS uniforms, not for a gs_set_antialiased made after it; the scene must still hold what
+ *     the frame rendered (as gs_project_backward states it).
+ * Scene ids, ordinary device allocations, inputs and the contents of the outputs COMPLETE before the call, the renderer's own
+ * NON-BLOCKING stream, the synchronisation (queued frames retire, an overflowed frame is re-run, the call returns when the arrays
+ * are written), "no frame rendered yet" and the behaviour after a refused or failed gs_render: all as gs_lift_pixels states them.
+ * GS_ERR_INVALID, checked before any device is touched: r or g NULL; a pointer that is not 8-byte aligned (judged by its value
+ * alone).  N = gs_scene_num_vertices.  Cost: INTEGRATION.md, 3i. */
+#define GS_CAMERA_BACKWARD_LANES 131072u
+typedef struct {
+    const double* d_colour;          /* [N][3] inputs exactly as gs_project_grads: nullable = zeros */
+    const double* d_opacity;         /* [N]    */
+    const double* d_conic;           /* [N][3] */
+    const double* d_uv;              /* [N][2] */
+    double* d_view_mat;              /* [16] device, laid out as view_mat; rows 0..2 ADDED to, row 3 untouched; nullable */
+    double* d_proj_mat;              /* [16] device, laid out as proj_mat; rows 0, 1, 3 ADDED to, row 2 untouched; nullable */
+    double* d_camera_position;       /* [3]  device, ADDED to; nullable */
+} gs_camera_grads;
+int gs_camera_backward(gs_renderer* r, const gs_camera_grads* g);
+/* Host only, no device: from the gradients with respect to gs_camera_uniforms' view_mat, proj_mat and camera_position (host
+ * copies of what gs_camera_backward summed; any values are taken, every row included) to the gradients with respect to the
+ * gs_camera's position and rotation.  Binary64.  It is the gradient of the exact real function behind gs_camera_uniforms,
+ *     M = T(position) mat4_cast(rotation)  (the quaternion NOT normalised, as the forward),   view = M^-1,   proj = persp view,
+ *     then the y and z rows of view and the y row of proj negated;   camera_position = position  (the direct term),
+ * evaluated at the binary32 camera values converted exactly (persp from fov, near_plane, far_plane, width and height, which
+ * carry no gradient):  g_M = -M^-T g_view M^-T.  Outputs are WRITTEN.  d_rotation (w x y z) is the gradient with respect to the
+ * RAW quaternion: a caller who keeps a unit quaternion projects it onto the tangent of the sphere themselves (as
+ * gs_transform_camera, nothing here normalises).  GS_ERR_INVALID: a null argument, an empty framebuffer. */
+int gs_camera_uniforms_backward(const gs_camera* cam, uint32_t width, uint32_t height,
+                                const double d_view_mat[16], const double d_proj_mat[16], const double d_camera_position[3],
+                                double d_position[3], double d_rotation[4]);   /* host pointers; outputs WRITTEN */
 /* Test hook (tests/test_gpu_expf.py): evaluate the blend's exp() implementations ON THE DEVICE over the binary32 values with
  * bit patterns [first_bits, first_bits + count) (the negative floats run from 0x80000000 = -0 to 0xFF800000 = -inf).
  * block_sums[j] = sum over block j of 2^20 consecutive patterns of  bits(expf(x)) * ((bits(x) * 0x9E3779B1) | 1)  mod 2^64,
