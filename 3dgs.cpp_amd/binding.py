@@ -24,7 +24,7 @@ BLOB_PLANES = 59
 
 # the device code of libgs3d_hip.so: one translation unit per stage + the shared device headers
 KERNEL_SOURCES = ("gs_device.h", "gs_bin.h", "gs_tile_cull.h", "gs_scene.hip", "gs_preprocess.hip", "gs_radix.hip", "gs_bin_l1.hip", "gs_bin_l2.hip",
-                  "gs_blend.hip", "gs_contrib.hip", "gs_features.hip", "gs_lift.hip", "gs_backward.hip", "gs_project_backward.hip", "gs_camera_backward.hip", "gs_project_chain.h",
+                  "gs_blend.hip", "gs_contrib.hip", "gs_features.hip", "gs_lift.hip", "gs_backward.hip", "gs_project_backward.hip", "gs_camera_backward.hip", "gs_loss.hip", "gs_project_chain.h",
                   "gs_wave_f64.h", "gs_kernels.h")
 
 
@@ -63,7 +63,7 @@ SYMBOLS = ["gs_last_error", "gs_device_count", "gs_read_ply", "gs_activate_recor
            "gs_deactivate_vertices", "gs_write_ply", "gs_scene_to_device_arrays", "gs_scene_download_records", "gs_scene_save_ply",
            "gs_scene_destroy", "gs_renderer_create", "gs_renderer_destroy", "gs_camera_uniforms",
            "gs_render", "gs_render_host", "gs_synchronize", "gs_set_timing", "gs_set_frames_in_flight", "gs_set_sort_path", "gs_set_exp_mode", "gs_set_graph_mode", "gs_set_blend_lockstep", "gs_get_blend_lockstep", "gs_set_level1_fused", "gs_get_level1_fused", "gs_set_tile_cull", "gs_get_tile_cull", "gs_get_listed_instances", "gs_set_blend_contraction", "gs_set_antialiased", "gs_get_antialiased", "gs_get_timing_totals",
-           "gs_get_frame_intervals", "gs_get_stats", "gs_poll_stats", "gs_debug_download", "gs_accumulate_contributions", "gs_blend_features", "gs_lift_pixels", "gs_blend_backward", "gs_project_backward", "gs_camera_backward", "gs_camera_uniforms_backward", "gs_debug_expf_scan", "gs_debug_alpha_cut_scan", "gs_renderer_stream",
+           "gs_get_frame_intervals", "gs_get_stats", "gs_poll_stats", "gs_debug_download", "gs_accumulate_contributions", "gs_blend_features", "gs_lift_pixels", "gs_blend_backward", "gs_project_backward", "gs_camera_backward", "gs_camera_uniforms_backward", "gs_photometric_loss", "gs_debug_expf_scan", "gs_debug_alpha_cut_scan", "gs_renderer_stream",
            "gs_dist_unique_id", "gs_dist_create", "gs_dist_rank", "gs_dist_world", "gs_dist_pose_count",
            "gs_dist_broadcast_scene", "gs_dist_broadcast_scene_ex", "gs_dist_verify", "gs_dist_destroy"]
 
@@ -220,11 +220,21 @@ class CameraGrads(C.Structure):
                 ("d_view_mat", C.c_void_p), ("d_proj_mat", C.c_void_p), ("d_camera_position", C.c_void_p)]
 
 
+class PhotoLoss(C.Structure):
+    """gs_photo_loss: the two images, their size and pixel strides, lambda and the two outputs of gs_photometric_loss
+    (include/gs3d_hip.h)."""
+    _fields_ = [("image", C.c_void_p), ("target", C.c_void_p), ("width", C.c_int), ("height", C.c_int),
+                ("image_stride", C.c_int), ("target_stride", C.c_int), ("lambda_dssim", C.c_double),
+                ("terms", C.c_void_p), ("grad_rgb", C.c_void_p)]
+
+
+PHOTO_LOSS_MAX_EXTENT = 16384   # GS_PHOTO_LOSS_MAX_EXTENT: width and height of gs_photometric_loss
 CAMERA_BACKWARD_LANES = 131072  # GS_CAMERA_BACKWARD_LANES: a scene with more Gaussians is strided over by gs_camera_backward's lanes
 
 _FEATURE_MAPS_FN = None  # the torch.autograd.Function of Renderer.differentiable_feature_maps, defined when first asked for
 _RENDER_FN = None        # ... and of Renderer.differentiable_render
 _RENDER_POSED_FN = None  # ... and of Renderer.differentiable_render_posed
+_PHOTO_LOSS_FN = None    # ... and of Renderer.differentiable_photometric_loss
 
 
 def _complete_callers_work(*tensors):
@@ -390,6 +400,36 @@ def _render_posed_function():
 
         _RENDER_POSED_FN = RenderPosedFunction
     return _RENDER_POSED_FN
+
+
+def _photo_loss_function():
+    """The autograd function behind Renderer.differentiable_photometric_loss; torch is imported here, not with the module."""
+    global _PHOTO_LOSS_FN
+    if _PHOTO_LOSS_FN is None:
+        import torch
+
+        class PhotoLossFunction(torch.autograd.Function):
+            """loss(image, target) as a 0-dim float64 tensor; the forward's one call also finds d loss / d image, which the
+            backward scales.  The target carries no gradient.  Nothing of the renderer's last frame is involved."""
+
+            @staticmethod
+            def forward(ctx, renderer, lambda_dssim, image, target):
+                got = renderer.photometric_loss(image.detach().contiguous(), target.detach().contiguous(), lambda_dssim, grad=True, terms=True)
+                ctx.save_for_backward(got["grad_rgb"])
+                ctx.image = (tuple(image.shape), image.dtype)
+                return got["loss"].clone()
+
+            @staticmethod
+            def backward(ctx, grad_output):
+                (saved,) = ctx.saved_tensors
+                shape, dtype = ctx.image
+                g = grad_output.float() * saved
+                if shape[-1] == 4:   # (an RGBA image: the fourth float is not read, its gradient is zero)
+                    g = torch.cat([g, torch.zeros(shape[:2] + (1,), dtype=g.dtype, device=g.device)], dim=2)
+                return None, None, g.to(dtype), None
+
+        _PHOTO_LOSS_FN = PhotoLossFunction
+    return _PHOTO_LOSS_FN
 
 
 def camera_pose_gradient(cam, width, height, d):
@@ -976,6 +1016,66 @@ class Renderer:
         _complete_callers_work(colour, opacity, conic, uv, *result.values())  # (the zeros allocated above among them)
         _check(lib().gs_camera_backward(self._h, C.byref(g)))
         return result
+
+    def photometric_loss(self, image, target, lambda_dssim=0.2, grad=True, terms=True):
+        """The trainer's loss of `image` against `target` and its image gradient (gs_photometric_loss):
+        loss = (1 - lambda_dssim) L1 + lambda_dssim (1 - SSIM), 11 x 11 Gaussian window of sigma 1.5, zeros outside the image
+        (the Inria loss_utils.ssim / fused-ssim convention), evaluated in binary64.  image and target: float32 device tensors
+        (H, W, 3) or (H, W, 4), contiguous, of one H and W; the pixel stride is the last dimension, so a frame rendered into an
+        RGBA tensor goes in uncopied (its fourth float is never read).  The size is NOT tied to the renderer's last frame, which
+        the call neither reads nor changes.  grad: a float32 (H, W, 3) tensor to WRITE d loss / d image into -- exactly what
+        blend_backward takes --, True to have one allocated, or None: forward only.  terms: a float64 (4,) tensor to WRITE
+        loss, l1, ssim, mse into, True, or None.  lambda_dssim == 0 runs one pass without the window and writes ssim as NaN.
+        No atomics: two calls give the same bits.  The call is ordered behind this renderer's queued frames (so `image` may be
+        the target of a render that has not been synchronised) and waits for torch's current stream as lift_pixels does.
+        Returns synchronised, with a dict: loss (a 0-dim float64 view of terms[0]; None without terms), terms, grad_rgb."""
+        owner = "Renderer.photometric_loss"
+        dev = self.scene.device
+        lam = float(lambda_dssim)
+        if not 0.0 <= lam <= 1.0:
+            raise ValueError(f"lambda_dssim must lie in [0, 1], not {lambda_dssim!r}")
+        l = PhotoLoss()
+        l.lambda_dssim = lam
+        shape = tuple(int(d) for d in getattr(image, "shape", ()))
+        if len(shape) != 3 or shape[2] not in (3, 4):
+            raise ValueError(f"image: shape {shape} is not (H, W, 3) or (H, W, 4)")
+        h, w = shape[:2]
+        if not (1 <= h <= PHOTO_LOSS_MAX_EXTENT and 1 <= w <= PHOTO_LOSS_MAX_EXTENT):
+            raise ValueError(f"image: height and width must be 1 .. {PHOTO_LOSS_MAX_EXTENT}, not {h} and {w}")
+        tshape = tuple(int(d) for d in getattr(target, "shape", ()))
+        if len(tshape) != 3 or tshape[2] not in (3, 4):
+            raise ValueError(f"target: shape {tshape} is not ({h}, {w}, 3) or ({h}, {w}, 4)")
+        l.image = _tensor_exact("image", image, ("float32",), (h, w, shape[2]), dev, owner)
+        l.target = _tensor_exact("target", target, ("float32",), (h, w, tshape[2]), dev, owner)
+        l.width, l.height, l.image_stride, l.target_stride = w, h, shape[2], tshape[2]
+        result = dict(loss=None, terms=None, grad_rgb=None)
+        if grad is not None:
+            if grad is True:
+                import torch
+                grad = torch.empty((h, w, 3), dtype=torch.float32, device=f"cuda:{int(dev)}")
+            l.grad_rgb = _tensor_exact("grad", grad, ("float32",), (h, w, 3), dev, owner)
+            result["grad_rgb"] = grad
+        if terms is not None:
+            if terms is True:
+                import torch
+                terms = torch.empty((4,), dtype=torch.float64, device=f"cuda:{int(dev)}")
+            l.terms = _tensor_exact("terms", terms, ("float64",), (4,), dev, owner)
+            result["terms"] = terms
+        _complete_callers_work(image, target, grad, terms)
+        _check(lib().gs_photometric_loss(self._h, C.byref(l)))
+        if terms is not None:
+            result["loss"] = terms[0]
+        return result
+
+    def differentiable_photometric_loss(self, image, target, lambda_dssim=0.2):
+        """photometric_loss as a torch.autograd.Function of `image`: returns the loss as a 0-dim float64 device tensor; the
+        forward makes ONE call for the loss and d loss / d image and keeps the gradient, the backward returns
+        grad_output.float() * that gradient for `image` (zeros for the fourth float of an RGBA image) and nothing for `target`.
+        It does not involve the renderer's last frame, so the "one backward per forward" rule of differentiable_render does not
+        bind it.  A trainer's step:
+            rgb = rend.differentiable_render(u, **params)
+            rend.differentiable_photometric_loss(rgb, photo).backward()"""
+        return _photo_loss_function().apply(self, float(lambda_dssim), image, target)
 
     def differentiable_render_posed(self, width, height, position, rotation, means=None, log_scales=None, quats=None, opacity_logits=None,
                                     sh_dc=None, sh_rest=None, fov=45.0, near=0.1, far=1000.0, want_alpha=False):

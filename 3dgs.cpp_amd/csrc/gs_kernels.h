@@ -1,4 +1,4 @@
-// gs_kernels.h -- launch wrappers of the gfx950 kernels (gs_scene / gs_preprocess / gs_radix / gs_bin_l1 / gs_bin_l2 / gs_blend / gs_contrib / gs_features / gs_lift / gs_backward / gs_project_backward / gs_camera_backward .hip).
+// gs_kernels.h -- launch wrappers of the gfx950 kernels (gs_scene / gs_preprocess / gs_radix / gs_bin_l1 / gs_bin_l2 / gs_blend / gs_contrib / gs_features / gs_lift / gs_backward / gs_project_backward / gs_camera_backward / gs_loss .hip).
 // Host-side declarations only; everything takes raw device pointers + a stream.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -317,5 +317,14 @@ void launch_project_backward(const SceneView& sv, const uint32_t* tiles, const A
 size_t camera_backward_partials();
 void launch_camera_backward(const SceneView& sv, const uint32_t* tiles, const AttrRecord* rec, const gs_uniforms& u, bool antialiased,
                             const gs_camera_grads& g, double* partials, hipStream_t s);
+
+// gs_photometric_loss (gs3d_hip.h; gs_loss.hip): l's terms and grad_rgb (at least one not null; l checked by the caller) of l's two
+// images.  lambda > 0: k_loss_ssim over tiles of 16 x 16 pixels, one row of three partial sums per workgroup into `partials` (the
+// renderer's, at least photo_loss_partials() doubles) and, where grad_rgb is asked for, the three P maps into `maps` (the renderer's,
+// at least photo_loss_maps() doubles; not touched otherwise) for k_loss_grad to convolve.  lambda == 0: k_loss_l1 alone.  terms:
+// k_loss_finish, one workgroup that adds the rows in a fixed order.  No atomics: the same bits every call.
+size_t photo_loss_partials(int width, int height);
+size_t photo_loss_maps(int width, int height);
+void launch_photo_loss(const gs_photo_loss& l, double* maps, double* partials, hipStream_t s);
 
 }  // namespace gs

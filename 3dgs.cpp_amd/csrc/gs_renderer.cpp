@@ -857,6 +857,9 @@ struct gs_renderer {
     // frame's candidate records with BinLaunch::reference_boxes, into buffers and counters of the taps' own, which the renderer keeps
     // across frames; whether they hold the last frame's lists is LastFrame::tap_lists.  Nothing of the frame moves.
     DevBuf<double> camera_partials;  // gs_camera_backward's rows of 27 partial sums, one per workgroup (allocated on first use)
+    // gs_photometric_loss's scratch: the three binary64 P maps of an image (only a call that asks for grad_rgb with lambda > 0 needs
+    // them) and the rows of three partial sums, one per workgroup.  Both grow on demand and are never shrunk.
+    DevBuf<double> loss_maps, loss_partials;
     DevBuf<uint32_t> tap_ranges, tap_sorted;
     DevBuf<gs::Counters> tap_counters;
     using Lists = std::pair<const uint32_t*, const uint32_t*>;  // (ranges, lists)
@@ -1381,6 +1384,36 @@ int gs_camera_backward(gs_renderer* r, const gs_camera_grads* g) {
             gs::launch_camera_backward(sv, r->last_frame.set->tiles.p, lists.rec, r->last_frame.u, r->last_frame.antialiased, *g,
                                        r->camera_partials.p, s);
         });
+    });
+}
+
+int gs_photometric_loss(gs_renderer* r, const gs_photo_loss* l) {
+    return guarded([&] {
+        if (!r || !l) throw Error(GS_ERR_INVALID, "null argument");
+        // (all by the members' values alone: nothing is dereferenced and no device is touched before they pass)
+        const bool asked = l->terms || l->grad_rgb;
+        if (asked && !l->image) throw Error(GS_ERR_INVALID, "an output is given without image");
+        if (asked && !l->target) throw Error(GS_ERR_INVALID, "an output is given without target");
+        if (l->width < 1 || l->width > GS_PHOTO_LOSS_MAX_EXTENT) throw Error(GS_ERR_INVALID, "width must be 1 .. 16384");
+        if (l->height < 1 || l->height > GS_PHOTO_LOSS_MAX_EXTENT) throw Error(GS_ERR_INVALID, "height must be 1 .. 16384");
+        if (l->image_stride != 3 && l->image_stride != 4) throw Error(GS_ERR_INVALID, "image_stride must be 3 or 4");
+        if (l->target_stride != 3 && l->target_stride != 4) throw Error(GS_ERR_INVALID, "target_stride must be 3 or 4");
+        if (!(l->lambda_dssim >= 0.0 && l->lambda_dssim <= 1.0)) throw Error(GS_ERR_INVALID, "lambda_dssim must lie in [0, 1]");
+        if (reinterpret_cast<uintptr_t>(l->image) % 4 != 0) throw Error(GS_ERR_INVALID, "image must be 4-byte aligned");
+        if (reinterpret_cast<uintptr_t>(l->target) % 4 != 0) throw Error(GS_ERR_INVALID, "target must be 4-byte aligned");
+        if (reinterpret_cast<uintptr_t>(l->grad_rgb) % 4 != 0) throw Error(GS_ERR_INVALID, "grad_rgb must be 4-byte aligned");
+        if (reinterpret_cast<uintptr_t>(l->terms) % 8 != 0) throw Error(GS_ERR_INVALID, "terms must be 8-byte aligned");
+        if (!asked) return;
+        // Behind queued frames: they retire first, as for the passes over the last frame (an overflowed one is re-run, so `image`
+        // may be the target of a gs_render that has not retired).  Nothing of the last frame is read or written from here on.
+        r->drain();
+        HIP_CHECK(hipSetDevice(r->scene->device));
+        if (l->grad_rgb && l->lambda_dssim != 0.0) r->loss_maps.ensure(gs::photo_loss_maps(l->width, l->height));
+        r->loss_partials.ensure(gs::photo_loss_partials(l->width, l->height));
+        const FrameBuffers& fb = r->sets[0];
+        gs::launch_photo_loss(*l, r->loss_maps.p, r->loss_partials.p, fb.stream);
+        HIP_CHECK(hipGetLastError());
+        fb.sync();
     });
 }
 

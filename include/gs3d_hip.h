@@ -809,6 +809,65 @@ int gs_camera_backward(gs_renderer* r, const gs_camera_grads* g);
 int gs_camera_uniforms_backward(const gs_camera* cam, uint32_t width, uint32_t height,
                                 const double d_view_mat[16], const double d_proj_mat[16], const double d_camera_position[3],
                                 double d_position[3], double d_rotation[4]);   /* host pointers; outputs WRITTEN */
+/* The photometric loss of a trainer's step and its image gradient: what stands between a rendered frame and gs_blend_backward.
+ * No reference counterpart.  The loss is the one the 3DGS trainers minimise (Inria loss_utils.ssim, gsplat, fused-ssim):
+ * (1 - lambda) L1 + lambda (1 - SSIM), an 11 x 11 Gaussian window of sigma 1.5, "same" zero padding, lambda = 0.2 by custom.
+ *
+ * THE FUNCTION, in exact real arithmetic.  x = image, y = target: binary32, [height][width] pixels of 3 channels with a pixel
+ * stride of 3 or 4 floats each (stride 4 lets the renderer's RGBA go in uncopied; its fourth float is never read).
+ *     g[k] = exp(-(k - 5)^2 / 4.5) / sum,  k = 0..10;    w = g g^T;
+ *     a*  = the 11 x 11 correlation of a map with w, per channel, with zeros outside the image;
+ *     n = 3 height width;    C1 = 1e-4;    C2 = 9e-4.
+ * Forward:
+ *     mu1 = x*   mu2 = y*   s11 = (x^2)* - mu1^2   s22 = (y^2)* - mu2^2   s12 = (x y)* - mu1 mu2
+ *     A = 2 mu1 mu2 + C1    B = 2 s12 + C2    C = mu1^2 + mu2^2 + C1    D = s11 + s22 + C2    S = A B / (C D)
+ *     l1 = sum |x - y| / n    ssim = sum S / n    mse = sum (x - y)^2 / n    loss = (1 - lambda) l1 + lambda (1 - ssim)
+ * Gradient:
+ *     P1 = 2 mu2 (B - A) / (C D) + 2 mu1 S (1 / D - 1 / C)      P2 = -S / D      P3 = 2 A / (C D)
+ *     d loss / d x = (1 - lambda) sign(x - y) / n  -  (lambda / n) (P1* + 2 x P2* + y P3*)        sign(0) = 0
+ * (w is symmetric, so the zero-padded correlation is its own transpose.)
+ *
+ * NUMERICAL CONTRACT.  Binary64 on exact conversions of the binary32 inputs (a product of two of them is exact); g is the
+ * binary64 rounding of its definition; C1 and C2 are the binary64 roundings of theirs.  The association is open -- separable or
+ * direct, fused multiply-add or not -- so the contract is a bound against the exact value: the roundings of the loosest
+ * permitted association, times 2^-53, times the magnitude, where each cancelling intermediate (s11, s22, s12, B - A,
+ * 1 / D - 1 / C) enters by the sum of its constituents' absolute values and each division by its condition.  A grad_rgb element
+ * is the binary64 value rounded once to binary32: it adds 2^-24 |want| and a denormal floor of 2^-149.  A term adds
+ * (n + K) 2^-53 sum |addends|.  tests/photometric_loss_reference.py derives the bound and counts its constants (K_CONV = 124 per
+ * correlation); tests/test_photometric_loss_api.py holds that module to torch.autograd and to binary80.
+ *   * No atomics: per-workgroup partial sums go to a row of the renderer's scratch and one workgroup adds the rows in a fixed
+ *     order.  Two calls with the same inputs and size give the same bits in terms and grad_rgb.  Outputs are WRITTEN.
+ *   * A NaN or infinity goes where the arithmetic takes it: the terms, and grad_rgb within 10 pixels (Chebyshev distance) of the
+ *     bad pixel.  Everywhere else grad_rgb is the finite value the contract bounds.  The zero padding is a zero, never a product
+ *     with data.
+ *   * lambda_dssim == 0: the window is never evaluated, one pass runs, terms[2] is written as a quiet NaN ("not evaluated"),
+ *     and grad_rgb = fl32(sign(x - y) / n).
+ *   * grad_rgb == NULL: forward only -- the evaluation call, for logging PSNR and SSIM.  Both outputs NULL: success, nothing
+ *     is launched.
+ * THE RENDERER gives the call its device, its non-blocking stream and a home for scratch (gs_loss.hip: three binary64 maps of
+ * the image's size, 72 bytes per pixel, when grad_rgb is asked for with lambda > 0; 24 bytes per tile of 16 x 16 pixels
+ * otherwise).  Scratch grows on demand and is freed with the renderer.  width and height are NOT tied to the last frame: the
+ * call neither reads nor changes it, works before any frame was rendered and after a refused or failed gs_render, and a pass
+ * over the last frame made after it answers as if it had not been called.  It is ordered behind queued frames -- they retire
+ * first, as for the passes over the last frame, so image may be the buffer a gs_render that has not retired is still writing
+ * (an error of a retiring frame is this call's error) -- and returns synchronised.  Inputs written on other streams must be
+ * COMPLETE before the call, as gs_lift_pixels states.
+ * GS_ERR_INVALID, checked before any device is touched (r is not dereferenced first): r or l NULL; image or target NULL while
+ * an output is asked for; width or height outside 1 .. GS_PHOTO_LOSS_MAX_EXTENT; a stride other than 3 or 4; lambda_dssim
+ * outside [0, 1] or NaN; a float pointer that is not 4-byte aligned or terms not 8-byte aligned (judged by its value alone).
+ * Cost: INTEGRATION.md, 3j. */
+#define GS_PHOTO_LOSS_MAX_EXTENT 16384
+typedef struct {
+    const float* image;    /* [height][width][image_stride]   first 3 floats of a pixel are read */
+    const float* target;   /* [height][width][target_stride] */
+    int width, height;     /* 1 .. 16384 each; NOT tied to the last frame */
+    int image_stride, target_stride;   /* 3 or 4 */
+    double lambda_dssim;   /* in [0, 1] */
+    double* terms;         /* device, [4] = loss, l1, ssim, mse; WRITTEN; nullable */
+    float*  grad_rgb;      /* device, [height][width][3] = d loss / d image, WRITTEN; nullable;
+                              exactly what gs_blend_backward takes */
+} gs_photo_loss;
+int gs_photometric_loss(gs_renderer* r, const gs_photo_loss* l);
 /* Test hook (tests/test_gpu_expf.py): evaluate the blend's exp() implementations ON THE DEVICE over the binary32 values with
  * bit patterns [first_bits, first_bits + count) (the negative floats run from 0x80000000 = -0 to 0xFF800000 = -inf).
  * block_sums[j] = sum over block j of 2^20 consecutive patterns of  bits(expf(x)) * ((bits(x) * 0x9E3779B1) | 1)  mod 2^64,
