@@ -24,7 +24,7 @@ BLOB_PLANES = 59
 
 # the device code of libgs3d_hip.so: one translation unit per stage + the shared device headers
 KERNEL_SOURCES = ("gs_device.h", "gs_bin.h", "gs_tile_cull.h", "gs_scene.hip", "gs_preprocess.hip", "gs_radix.hip", "gs_bin_l1.hip", "gs_bin_l2.hip",
-                  "gs_blend.hip", "gs_contrib.hip", "gs_features.hip", "gs_lift.hip", "gs_backward.hip", "gs_project_backward.hip", "gs_camera_backward.hip", "gs_loss.hip", "gs_project_chain.h",
+                  "gs_blend.hip", "gs_contrib.hip", "gs_features.hip", "gs_lift.hip", "gs_backward.hip", "gs_project_backward.hip", "gs_camera_backward.hip", "gs_loss.hip", "gs_optim.hip", "gs_project_chain.h",
                   "gs_wave_f64.h", "gs_kernels.h")
 
 
@@ -63,7 +63,7 @@ SYMBOLS = ["gs_last_error", "gs_device_count", "gs_read_ply", "gs_activate_recor
            "gs_deactivate_vertices", "gs_write_ply", "gs_scene_to_device_arrays", "gs_scene_download_records", "gs_scene_save_ply",
            "gs_scene_destroy", "gs_renderer_create", "gs_renderer_destroy", "gs_camera_uniforms",
            "gs_render", "gs_render_host", "gs_synchronize", "gs_set_timing", "gs_set_frames_in_flight", "gs_set_sort_path", "gs_set_exp_mode", "gs_set_graph_mode", "gs_set_blend_lockstep", "gs_get_blend_lockstep", "gs_set_level1_fused", "gs_get_level1_fused", "gs_set_tile_cull", "gs_get_tile_cull", "gs_get_listed_instances", "gs_set_blend_contraction", "gs_set_antialiased", "gs_get_antialiased", "gs_get_timing_totals",
-           "gs_get_frame_intervals", "gs_get_stats", "gs_poll_stats", "gs_debug_download", "gs_accumulate_contributions", "gs_blend_features", "gs_lift_pixels", "gs_blend_backward", "gs_project_backward", "gs_camera_backward", "gs_camera_uniforms_backward", "gs_photometric_loss", "gs_debug_expf_scan", "gs_debug_alpha_cut_scan", "gs_renderer_stream",
+           "gs_get_frame_intervals", "gs_get_stats", "gs_poll_stats", "gs_debug_download", "gs_accumulate_contributions", "gs_blend_features", "gs_lift_pixels", "gs_blend_backward", "gs_project_backward", "gs_camera_backward", "gs_camera_uniforms_backward", "gs_photometric_loss", "gs_visible_mask", "gs_scene_adam_step", "gs_debug_expf_scan", "gs_debug_alpha_cut_scan", "gs_renderer_stream",
            "gs_dist_unique_id", "gs_dist_create", "gs_dist_rank", "gs_dist_world", "gs_dist_pose_count",
            "gs_dist_broadcast_scene", "gs_dist_broadcast_scene_ex", "gs_dist_verify", "gs_dist_destroy"]
 
@@ -227,6 +227,21 @@ class PhotoLoss(C.Structure):
                 ("image_stride", C.c_int), ("target_stride", C.c_int), ("lambda_dssim", C.c_double),
                 ("terms", C.c_void_p), ("grad_rgb", C.c_void_p)]
 
+
+class AdamGroup(C.Structure):
+    """gs_adam_group: one parameter tensor of the trainer with its gradient and moments, and its learning rate."""
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p), ("lr", C.c_double)]
+
+
+class AdamStep(C.Structure):
+    """gs_adam_step: the six groups, the mask and the constants of gs_scene_adam_step (include/gs3d_hip.h)."""
+    _fields_ = [("means", AdamGroup), ("log_scales", AdamGroup), ("quats", AdamGroup), ("opacity_logits", AdamGroup),
+                ("sh_dc", AdamGroup), ("sh_rest", AdamGroup), ("sh_rest_coeffs", C.c_uint32), ("mask", C.c_void_p),
+                ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double),
+                ("bias_correction1", C.c_double), ("bias_correction2", C.c_double), ("zero_grads", C.c_int)]
+
+
+PARAMETER_NAMES = ("means", "log_scales", "quats", "opacity_logits", "sh_dc", "sh_rest")  # Scene.from_tensors' keywords
 
 PHOTO_LOSS_MAX_EXTENT = 16384   # GS_PHOTO_LOSS_MAX_EXTENT: width and height of gs_photometric_loss
 CAMERA_BACKWARD_LANES = 131072  # GS_CAMERA_BACKWARD_LANES: a scene with more Gaussians is strided over by gs_camera_backward's lanes
@@ -666,6 +681,65 @@ class Scene:
                                       sh_rest=sh_rest), device, require=False)
         _check(lib().gs_scene_update_from_device_arrays(self._h, C.byref(a), C.c_uint64(first), C.c_uint64(rows), _stream_handle(stream)))
 
+    def adam_step(self, params, grads, exp_avg, exp_avg_sq, lr, betas=(0.9, 0.999), eps=1e-15, step=1, mask=None, zero_grads=True,
+                  stream=None):
+        """One sparse Adam step on the device, in the trainer's tensors and in this scene (gs_scene_adam_step): the thin layer
+        over the C call.  params, grads, exp_avg, exp_avg_sq: dicts under from_tensors' keyword names; a name is a GROUP and is
+        stepped when params holds a tensor for it -- then all four dicts must (a name absent or None in all four is not stepped
+        and the scene keeps what it holds for it).  params and the moments are float32, grads float64 (what project_backward
+        adds to), all contiguous on the scene's device, one row per Gaussian: means (n, 3), log_scales (n, 3), quats (n, 4),
+        opacity_logits (n,), sh_dc (n, 3), sh_rest (n, k, 3) with k in 3, 8, 15 (k = 0: nothing to step).  lr: a float, or a dict
+        per name.  step: t >= 1, the number of this step; the bias corrections are 1 - beta ** step in Python floats.
+        mask: a uint8 tensor (n,) by scene id, nonzero = step this Gaussian (Renderer.visible_mask), None = every Gaussian.
+        zero_grads: the gradient elements that were consumed are set to +0.0.  Parameters, moments and the scene's planes of
+        every stepped group are updated for the masked Gaussians only; what is derived is redone.  Waits for torch's current
+        stream first; runs on `stream` (None: torch's current stream) and returns synchronised.  Synchronize every renderer of
+        the scene first."""
+        owner = "Scene.adam_step"
+        n, dev = int(self.num_vertices), self.device
+        dicts = dict(params=params, grads=grads, exp_avg=exp_avg, exp_avg_sq=exp_avg_sq)
+        for what, d in dicts.items():
+            unknown = sorted(set(d) - set(PARAMETER_NAMES))
+            if unknown:
+                raise TypeError(f"{what}: unknown member(s) {unknown}")
+        beta1, beta2 = (float(b) for b in betas)
+        if int(step) != step or step < 1:
+            raise ValueError(f"step must be an integer >= 1, not {step!r}")
+        a = AdamStep()
+        shapes = dict(means=(n, 3), log_scales=(n, 3), quats=(n, 4), opacity_logits=(n,), sh_dc=(n, 3), sh_rest=(n, None, 3))
+        members = dict(params=("param", "float32"), grads=("grad", "float64"), exp_avg=("exp_avg", "float32"), exp_avg_sq=("exp_avg_sq", "float32"))
+        used = []
+        for name in PARAMETER_NAMES:
+            have = [what for what, d in dicts.items() if d.get(name) is not None]
+            if not have:
+                continue
+            if len(have) != 4:
+                raise ValueError(f"{name}: a partial group -- given in {', '.join(have)} but not in "
+                                 f"{', '.join(w for w in dicts if w not in have)}")
+            group, shape = getattr(a, name), shapes[name]
+            for what, (member, dtype) in members.items():
+                t = dicts[what][name]
+                ptr = _tensor_exact(f"{what}[{name!r}]", t, (dtype,), shape, dev, owner)
+                if name == "sh_rest":
+                    k = int(t.shape[1])
+                    if k not in SH_REST_COEFFS.values():
+                        raise ValueError(f"{what}['sh_rest']: shape {tuple(int(d) for d in t.shape)} is not (rows, k, 3) with k in 0, 3, 8, 15")
+                    if what != "params" and k != a.sh_rest_coeffs:
+                        raise ValueError(f"{what}['sh_rest']: shape {tuple(int(d) for d in t.shape)} is not params['sh_rest']'s")
+                    a.sh_rest_coeffs = k
+                setattr(group, member, ptr)
+                used.append(t)
+            rate = lr[name] if isinstance(lr, dict) else lr
+            group.lr = float(rate)
+        if mask is not None:
+            a.mask = _tensor_exact("mask", mask, ("uint8",), (n,), dev, owner)
+            used.append(mask)
+        a.beta1, a.beta2, a.eps = beta1, beta2, float(eps)
+        a.bias_correction1, a.bias_correction2 = 1.0 - beta1 ** int(step), 1.0 - beta2 ** int(step)
+        a.zero_grads = 1 if zero_grads else 0
+        _complete_callers_work(*used)
+        _check(lib().gs_scene_adam_step(self._h, C.byref(a), _stream_handle(stream)))
+
     def transform(self, rotation=(1, 0, 0, 0), translation=(0, 0, 0), scale=1.0, first=0, count=None, stream=None):
         """Move Gaussians [first, first + count) (count None: to the end) by x -> scale * R(rotation) x + translation, in place
         on the device: positions, scales, rotations and the SH bands, rotated with the splats (gs_scene_transform).
@@ -973,6 +1047,22 @@ class Renderer:
         _check(lib().gs_project_backward(self._h, C.byref(g)))
         return out
 
+    def visible_mask(self, out=None, accumulate=False):
+        """The last frame's visibility as Scene.adam_step's mask (gs_visible_mask): a uint8 tensor (N,) on the scene's device, by
+        scene id, 1 where stage("tiles") != 0.  out: the tensor to write (None: a new one); accumulate: OR into what `out` holds
+        -- the union over a camera set (zero it once).  The stream and the wait for torch's current stream are lift_pixels's;
+        raises GsError before any frame was rendered.  Returns synchronised, with the tensor."""
+        n, dev = int(self.scene.num_vertices), self.scene.device
+        if out is None:
+            import torch
+            out = torch.zeros(n, dtype=torch.uint8, device=f"cuda:{int(dev)}")
+        ptr = _tensor_exact("out", out, ("uint8",), (n,), dev, "Renderer.visible_mask")
+        if ptr is None:  # a scene of no Gaussians has no mask to write
+            return out
+        _complete_callers_work(out)
+        _check(lib().gs_visible_mask(self._h, C.c_void_p(ptr), C.c_int(1 if accumulate else 0)))
+        return out
+
     def differentiable_render(self, uniforms, means, log_scales, quats, opacity_logits, sh_dc, sh_rest=None, want_alpha=False):
         """One frame as a torch.autograd.Function of the trainer's six parameter tensors (float32, on the renderer's device, as
         Scene.from_tensors takes them, one row per Gaussian of the scene): the forward refreshes the scene from them
@@ -1250,6 +1340,30 @@ class Renderer:
             self.close()
         except Exception:
             pass
+
+
+class Adam:
+    """The optimiser of a trainer on this rasteriser: the moments and the step count around Scene.adam_step.
+    params: {name: float32 device tensor} under from_tensors' names -- the tensors the scene was built from; they are updated
+    in place and the scene with them.  lr: a float or a dict per name.  A sparse Adam: step(mask=...) moves the masked Gaussians
+    only and the others' moments do not decay."""
+
+    def __init__(self, scene, params, lr, betas=(0.9, 0.999), eps=1e-15):
+        import torch
+        self.scene, self.lr, self.betas, self.eps, self.t = scene, lr, tuple(betas), eps, 0
+        self.params = {k: v for k, v in params.items() if v is not None}
+        self.state = dict(exp_avg={k: torch.zeros_like(v, dtype=torch.float32) for k, v in self.params.items()},
+                          exp_avg_sq={k: torch.zeros_like(v, dtype=torch.float32) for k, v in self.params.items()})
+
+    def step(self, grads, mask=None, zero_grads=True):
+        """One step with the float64 gradients `grads` (a dict under the same names as params); see Scene.adam_step."""
+        self.t += 1
+        try:
+            self.scene.adam_step(self.params, grads, self.state["exp_avg"], self.state["exp_avg_sq"], self.lr, self.betas, self.eps,
+                                 self.t, mask=mask, zero_grads=zero_grads)
+        except Exception:
+            self.t -= 1  # a refused step is no step
+            raise
 
 
 class Dist:

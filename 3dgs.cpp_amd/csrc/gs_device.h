@@ -154,6 +154,15 @@ __device__ __forceinline__ float gs_expf_libm_full(float x, const uint2* __restr
     return x < -0x1.9fe368p6f ? 0.0f : gs_expf_libm(x, tab);
 }
 
+// libm's expf on the WHOLE domain: gs_expf_libm_full (x <= 0, with glibc's underflow branch) continued to x > 0.  The general
+// path's sequence equals libm on every binary32 in [0, 0x42B17218] (oracle: expf_device_mismatches, tests/test_device_arrays_api.py)
+// but not above it, where glibc leaves through its overflow branch (e_expf.c: x > 0x1.62e42ep6f -> __math_oflowf): stated here.
+// NaN falls through both comparisons and comes out of the sequence as NaN.  What the activation of a trainer's log-scales and
+// opacity logits is made of (k_ingest_arrays in gs_scene.hip, k_adam_step in gs_optim.hip).
+__device__ __forceinline__ float gs_expf_libm_domain(float x, const uint2* __restrict__ tab) {
+    return x > 0x1.62e42ep6f ? __uint_as_float(0x7F800000u) : gs_expf_libm_full(x, tab);
+}
+
 // render.comp:77-79 as a predicate on `power`:  alpha = min(0.99, o * exp(power));  if (alpha < 1/255) continue;
 __device__ __forceinline__ bool alpha_kept(float o, float power, const uint2* __restrict__ tab) {
     const float alpha = fminf(0.99f, o * gs_expf_libm_full(power, tab));  // min(0.99, NaN) = 0.99: the pipeline's definition

@@ -1,4 +1,4 @@
-// gs_kernels.h -- launch wrappers of the gfx950 kernels (gs_scene / gs_preprocess / gs_radix / gs_bin_l1 / gs_bin_l2 / gs_blend / gs_contrib / gs_features / gs_lift / gs_backward / gs_project_backward / gs_camera_backward / gs_loss .hip).
+// gs_kernels.h -- launch wrappers of the gfx950 kernels (gs_scene / gs_preprocess / gs_radix / gs_bin_l1 / gs_bin_l2 / gs_blend / gs_contrib / gs_features / gs_lift / gs_backward / gs_project_backward / gs_camera_backward / gs_loss / gs_optim .hip).
 // Host-side declarations only; everything takes raw device pointers + a stream.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -326,5 +326,27 @@ void launch_camera_backward(const SceneView& sv, const uint32_t* tiles, const At
 size_t photo_loss_partials(int width, int height);
 size_t photo_loss_maps(int width, int height);
 void launch_photo_loss(const gs_photo_loss& l, double* maps, double* partials, hipStream_t s);
+
+// gs_scene_adam_step (gs3d_hip.h; gs_optim.hip): one Adam step of the Gaussians of a mask, in the caller's tensors and in the blob.
+// A group is a gs_adam_group with its step size lr / bias_correction1 formed by the caller; all four pointers null: not stepped.
+struct AdamGroup {
+    float* param;
+    double* grad;
+    float* exp_avg;
+    float* exp_avg_sq;
+    double step;  // lr / bias_correction1
+};
+struct AdamStep {
+    AdamGroup means, log_scales, quats, opacity_logits, sh_dc, sh_rest;
+    uint32_t sh_rest_coeffs;  // 3, 8 or 15 where sh_rest is stepped
+    const uint8_t* mask;      // [n] by scene id, nullable: every Gaussian
+    double beta1, beta2, one_minus_beta1, one_minus_beta2, sqrt_bc2, eps;
+    bool zero_grads;
+};
+// One launch over the n Gaussians of `blob` (the scene's own, in scene order: not the copy in spatial order), a workgroup per 256 of
+// them; what is derived from the planes it writes is the caller's to redo.
+void launch_adam_step(const AdamStep& a, float* blob, uint32_t stride, uint32_t n, hipStream_t s);
+// gs_visible_mask: mask[id] = tiles[id] != 0, or that ORed into mask[id]; tiles: the frame's tiles_overlap plane, by scene id.
+void launch_visible_mask(const uint32_t* tiles, uint8_t* mask, uint32_t n, bool accumulate, hipStream_t s);
 
 }  // namespace gs

@@ -837,7 +837,7 @@ struct gs_renderer {
     }
 
     // What the passes over the last frame's tile lists do after their own argument checks (gs_accumulate_contributions,
-    // gs_blend_features, gs_lift_pixels, gs_blend_backward, gs_project_backward, gs_camera_backward), in this order: queued frames retire (an overflowed one is re-run: the lists are the last
+    // gs_blend_features, gs_lift_pixels, gs_blend_backward, gs_project_backward, gs_camera_backward, gs_visible_mask), in this order: queued frames retire (an overflowed one is re-run: the lists are the last
     // frame's, complete); without a frame the call is refused; with nothing asked for it is done; otherwise launch(lists, stream)
     // enqueues the pass over the frame's own lists on the last frame's stream and the call waits for it.
     template <class Launch>
@@ -1414,6 +1414,16 @@ int gs_photometric_loss(gs_renderer* r, const gs_photo_loss* l) {
         gs::launch_photo_loss(*l, r->loss_maps.p, r->loss_partials.p, fb.stream);
         HIP_CHECK(hipGetLastError());
         fb.sync();
+    });
+}
+
+int gs_visible_mask(gs_renderer* r, uint8_t* mask, int accumulate) {
+    return guarded([&] {
+        if (!r || !mask) throw Error(GS_ERR_INVALID, "null argument");
+        r->over_last_frame(false, [&](const gs::TileLists&, hipStream_t s) {
+            r->rebuild_planes();  // visibility is the tiles tap's answer, as in gs_project_backward
+            gs::launch_visible_mask(r->last_frame.set->tiles.p, mask, static_cast<uint32_t>(r->scene->n), accumulate != 0, s);
+        });
     });
 }
 

@@ -163,14 +163,7 @@ void launch_cov3d(const float* blob, float* cov3d, uint32_t n, uint32_t stride, 
 // A trainer's device arrays -> the blob (gs_scene_from_device_arrays / gs_scene_update_from_device_arrays): GSScene::load's
 // per-record conversion (GSScene.cpp:42-55, gs_host_math.h: activate_record) on the device, bit for bit.
 // ---------------------------------------------------------------------------------------
-// libm's expf on the WHOLE domain: gs_expf_libm_full (x <= 0, with glibc's underflow branch) continued to x > 0.  The general
-// path's sequence equals libm on every binary32 in [0, 0x42B17218] (oracle: expf_device_mismatches, tests/test_device_arrays_api.py)
-// but not above it, where glibc leaves through its overflow branch (e_expf.c: x > 0x1.62e42ep6f -> __math_oflowf): stated here.
-// NaN falls through both comparisons and comes out of the sequence as NaN.
-__device__ __forceinline__ float gs_expf_libm_domain(float x, const uint2* __restrict__ tab) {
-    return x > 0x1.62e42ep6f ? __uint_as_float(0x7F800000u) : gs_expf_libm_full(x, tab);
-}
-
+// (exp is gs_expf_libm_domain, gs_device.h: libm's expf on the whole domain.)
 // One workgroup takes BLOCK consecutive Gaussians of the range: Gaussian i of the arrays is Gaussian first + i of the scene.
 //   * the [n][3] / [n][4] arrays are read as the runs of floats they are (lane-contiguous: the sources are only 4-byte
 //     aligned) into LDS and picked up per Gaussian -- a stride of 3 dwords is conflict-free on 32 banks, the quaternion is one

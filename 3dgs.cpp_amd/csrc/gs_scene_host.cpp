@@ -127,18 +127,14 @@ void check_device_arrays(const gs_device_arrays* a, uint64_t rows, bool build) {
     }
 }
 
-// gs_scene_update_from_device_arrays: the ingest over the range, then whatever is derived from the members that changed --
-// whole planes, into the buffers the scene's renderers already hold -- all on `stream`, which is synchronised at the end.
-void update_from_device_arrays(gs_scene* s, const gs_device_arrays& a, uint64_t first, uint64_t count, hipStream_t stream) {
-    HIP_CHECK(hipSetDevice(s->device));
+// What is derived from the blob's planes, redone after they were rewritten in place (the ingest of an update, the optimiser's
+// step) -- whole planes, into the buffers the scene's renderers already hold -- on `stream`, which is synchronised at the end.
+static void redo_derived(gs_scene* s, bool shape, bool sh, bool opacity, hipStream_t stream) {
     const uint32_t n = static_cast<uint32_t>(s->n), st = static_cast<uint32_t>(gs::blob_stride(s->n));
-    gs_device_arrays in = a;
-    if (!in.sh_rest) in.sh_rest_coeffs = 0;
-    gs::launch_ingest_arrays(in, s->blob, st, static_cast<uint32_t>(first), static_cast<uint32_t>(count), in.sh_rest != nullptr, stream);
     if (s->spatial_blob.p) gs::launch_permute_blob(s->blob, s->perm.p, s->spatial_blob.p, n, st, stream);  // the order stays
-    if (a.log_scales || a.quats) gs::launch_cov3d(s->render_blob(), s->cov3d.p, n, st, 0, n, stream);
-    if (s->sh_half && (a.sh_dc || a.sh_rest)) gs::launch_sh_to_half(s->render_blob(), s->sh16.p, st, 0, n, stream);
-    if (a.opacity_logits) {
+    if (shape) gs::launch_cov3d(s->render_blob(), s->cov3d.p, n, st, 0, n, stream);
+    if (s->sh_half && sh) gs::launch_sh_to_half(s->render_blob(), s->sh16.p, st, 0, n, stream);
+    if (opacity) {
         DevBuf<uint32_t> beyond;
         beyond.alloc(1);
         HIP_CHECK(hipMemsetAsync(beyond.p, 0, sizeof(uint32_t), stream));
@@ -151,6 +147,65 @@ void update_from_device_arrays(gs_scene* s, const gs_device_arrays& a, uint64_t 
     }
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(stream));
+}
+
+// gs_scene_update_from_device_arrays: the ingest over the range, then whatever is derived from the members that changed.
+void update_from_device_arrays(gs_scene* s, const gs_device_arrays& a, uint64_t first, uint64_t count, hipStream_t stream) {
+    HIP_CHECK(hipSetDevice(s->device));
+    const uint32_t st = static_cast<uint32_t>(gs::blob_stride(s->n));
+    gs_device_arrays in = a;
+    if (!in.sh_rest) in.sh_rest_coeffs = 0;
+    gs::launch_ingest_arrays(in, s->blob, st, static_cast<uint32_t>(first), static_cast<uint32_t>(count), in.sh_rest != nullptr, stream);
+    redo_derived(s, a.log_scales || a.quats, a.sh_dc || a.sh_rest, a.opacity_logits != nullptr, stream);
+}
+
+// What gs_scene_adam_step refuses before any device is touched; returns whether any group is given.
+bool check_adam_step(const gs_adam_step* a) {
+    if (!a) throw Error(GS_ERR_INVALID, "null argument");
+    const uint32_t k = a->sh_rest_coeffs;
+    if (k != 0 && k != 3 && k != 8 && k != 15) throw Error(GS_ERR_INVALID, "sh_rest_coeffs must be 0, 3, 8 or 15 (SH degree 0..3)");
+    const struct {
+        const gs_adam_group* g;
+        const char* name;
+    } groups[6] = {{&a->means, "means"}, {&a->log_scales, "log_scales"}, {&a->quats, "quats"}, {&a->opacity_logits, "opacity_logits"},
+                   {&a->sh_dc, "sh_dc"}, {&a->sh_rest, "sh_rest"}};
+    bool any = false;
+    for (const auto& m : groups) {
+        const gs_adam_group& g = *m.g;
+        const int given = (g.param != nullptr) + (g.grad != nullptr) + (g.exp_avg != nullptr) + (g.exp_avg_sq != nullptr);
+        if (given == 0) continue;
+        const std::string name = std::string("group `") + m.name + "`";
+        if (given != 4) throw Error(GS_ERR_INVALID, name + " has some but not all of param, grad, exp_avg, exp_avg_sq");
+        for (const float* p : {g.param, g.exp_avg, g.exp_avg_sq})
+            if (reinterpret_cast<uintptr_t>(p) % 4 != 0) throw Error(GS_ERR_INVALID, name + ": param, exp_avg and exp_avg_sq must be 4-byte aligned");
+        if (reinterpret_cast<uintptr_t>(g.grad) % 8 != 0) throw Error(GS_ERR_INVALID, name + ": grad must be 8-byte aligned");
+        if (!(std::isfinite(g.lr) && g.lr >= 0.0)) throw Error(GS_ERR_INVALID, name + ": lr must be finite and >= 0");
+        any = true;
+    }
+    if (a->sh_rest.param && k == 0) throw Error(GS_ERR_INVALID, "group `sh_rest` is given with sh_rest_coeffs == 0");
+    if (!(a->beta1 >= 0.0 && a->beta1 < 1.0) || !(a->beta2 >= 0.0 && a->beta2 < 1.0)) throw Error(GS_ERR_INVALID, "beta1 and beta2 must lie in [0, 1)");
+    if (!(std::isfinite(a->eps) && a->eps >= 0.0)) throw Error(GS_ERR_INVALID, "eps must be finite and >= 0");
+    if (!(a->bias_correction1 > 0.0 && a->bias_correction1 <= 1.0) || !(a->bias_correction2 > 0.0 && a->bias_correction2 <= 1.0))
+        throw Error(GS_ERR_INVALID, "the bias corrections must lie in (0, 1]");
+    return any;
+}
+
+// gs_scene_adam_step: the step over the whole scene (k_adam_step leaves the workgroups of unmasked Gaussians at once), then
+// whatever is derived from the groups that were stepped, as an update of those members would redo it.
+void adam_step(gs_scene* s, const gs_adam_step& a, hipStream_t stream) {
+    HIP_CHECK(hipSetDevice(s->device));
+    gs::AdamStep k{};
+    const gs_adam_group* from[6] = {&a.means, &a.log_scales, &a.quats, &a.opacity_logits, &a.sh_dc, &a.sh_rest};
+    gs::AdamGroup* to[6] = {&k.means, &k.log_scales, &k.quats, &k.opacity_logits, &k.sh_dc, &k.sh_rest};
+    for (int i = 0; i < 6; ++i) *to[i] = gs::AdamGroup{from[i]->param, from[i]->grad, from[i]->exp_avg, from[i]->exp_avg_sq, from[i]->lr / a.bias_correction1};
+    k.sh_rest_coeffs = a.sh_rest_coeffs;
+    k.mask = a.mask;
+    k.beta1 = a.beta1, k.beta2 = a.beta2, k.one_minus_beta1 = 1.0 - a.beta1, k.one_minus_beta2 = 1.0 - a.beta2;
+    k.sqrt_bc2 = std::sqrt(a.bias_correction2);
+    k.eps = a.eps;
+    k.zero_grads = a.zero_grads != 0;
+    gs::launch_adam_step(k, s->blob, static_cast<uint32_t>(gs::blob_stride(s->n)), static_cast<uint32_t>(s->n), stream);
+    redo_derived(s, a.log_scales.param || a.quats.param, a.sh_dc.param || a.sh_rest.param, a.opacity_logits.param != nullptr, stream);
 }
 
 // gs_scene_transform: the kernel over the range, then what is derived from scales, rotations and SH -- over the range alone
@@ -341,6 +396,15 @@ int gs_scene_update_from_device_arrays(gs_scene* s, const gs_device_arrays* a, u
         if (first > s->n || count > s->n - first) throw Error(GS_ERR_INVALID, "Gaussian range out of bounds");
         if (count == 0 || !(a->means || a->log_scales || a->quats || a->opacity_logits || a->sh_dc || a->sh_rest)) return;
         update_from_device_arrays(s, *a, first, count, static_cast<hipStream_t>(stream));
+    });
+}
+
+int gs_scene_adam_step(gs_scene* s, const gs_adam_step* a, void* stream) {
+    return guarded([&] {
+        const bool any = check_adam_step(a);
+        if (!s) throw Error(GS_ERR_INVALID, "null argument");
+        if (!any || s->n == 0) return;
+        adam_step(s, *a, static_cast<hipStream_t>(stream));
     });
 }
 

@@ -868,6 +868,74 @@ typedef struct {
                               exactly what gs_blend_backward takes */
 } gs_photo_loss;
 int gs_photometric_loss(gs_renderer* r, const gs_photo_loss* l);
+/* The LAST frame's visibility as the mask gs_scene_adam_step takes: mask[id] = (the frame's GS_STAGE_TILES value of Gaussian id
+ * != 0) ? 1 : 0, by SCENE id (also on a scene that keeps a copy in spatial order), N = gs_scene_num_vertices bytes of device
+ * memory on the scene's device.  accumulate != 0: the byte is ORed into what mask[id] holds -- the union over a camera set; zero
+ * the mask once.  One kernel (gs_optim.hip).  No reference counterpart.  Ordinary device allocations, the mask's contents
+ * COMPLETE before an accumulating call, the renderer's own NON-BLOCKING stream, the synchronisation (queued frames retire, an
+ * overflowed frame is re-run, the call returns when the mask is written), "no frame rendered yet" and the behaviour after a
+ * refused or failed gs_render: all as gs_project_backward states them.
+ * GS_ERR_INVALID, checked before any device is touched: r or mask NULL. */
+int gs_visible_mask(gs_renderer* r, uint8_t* mask, int accumulate);
+
+/* ---- the optimiser's step: a sparse Adam on the trainer's tensors that leaves the scene ready for the next frame -----------
+ * One Adam step of the Gaussians of a mask ("SelectiveAdam" / "SparseGaussianAdam": a Gaussian the frames did not see is not
+ * stepped and its moments do not decay), in the caller's tensors AND in the scene: the parameters, gradients and moments are
+ * the six PLY-domain arrays of gs_device_arrays and their companions; the scene receives the activated values of the new
+ * parameters.  No reference counterpart.  One kernel (gs_optim.hip: k_adam_step), then the load-time passes over what changed.
+ *
+ * THE UPDATE, for every masked Gaussian and every element of every given group, with p, m, v the stored binary32 parameter and
+ * moments converted exactly and g the binary64 gradient.  All arithmetic is binary64, every operation is rounded on its own
+ * (the unit is built with -ffp-contract=off), in exactly this order:
+ *     m' = (beta1 * m) + ((1 - beta1) * g)              (1 - beta1) and (1 - beta2) formed once, in binary64
+ *     v' = (beta2 * v) + (((1 - beta2) * g) * g)
+ *     d  = (sqrt(v') / sqrt(bias_correction2)) + eps    sqrt and / are IEEE; sqrt(bias_correction2) formed once on the host
+ *     p' = p - ((lr / bias_correction1) * (m' / d))     lr / bias_correction1 formed once on the host, per group
+ *     exp_avg <- fl32(m')    exp_avg_sq <- fl32(v')    param <- fl32(p')        one rounding each, at the store
+ * This is torch.optim.Adam's update (amsgrad = False, no weight decay, not maximize) with the moments kept in binary32; the
+ * update uses the unrounded m' and v'.  The order is fixed and every operation is IEEE: THE CONTRACT IS A BIT PATTERN, not a
+ * bound (tests/adam_step_reference.py restates it in numpy).
+ *   * An UNMASKED Gaussian: nothing is read and nothing is written -- not its parameters, moments or gradients, not the scene's
+ *     rows.  Its moments do not decay (a dense Adam would go on moving it by its old momentum).
+ *   * A NaN or infinite gradient reaches the masked Gaussian's own elements only.
+ *   * zero_grads != 0: exactly the elements that were read as g are set to +0.0, so that gs_project_backward, which ADDS, can
+ *     go on using tensors that were zeroed once.
+ * THE SCENE.  For each masked Gaussian the planes of every STEPPED group are written from the new binary32 parameters with the
+ * arithmetic of gs_scene_from_device_arrays (exp: libm's expf restated, for the scales; q * (1 / sqrtf(dot)) for the rotation;
+ * 1 / (1 + expf(-l)) for the opacity; SH copied): afterwards the scene's blob is BIT FOR BIT what
+ * gs_scene_update_from_device_arrays of the new parameters over those rows would have made -- with one difference: the SH
+ * bands beyond sh_rest_coeffs KEEP what the scene holds (the update zeroes them when it is given sh_rest).  A group that is
+ * not stepped keeps its planes.  What is derived from what changed is redone on `stream` with the same passes and under the
+ * same conditions as gs_scene_update_from_device_arrays: the copy in spatial order (its order stays), cov3D after log_scales
+ * or quats, the binary16 SH block of a quantised scene after sh_dc or sh_rest, the alpha cuts and the opacity flag behind exp
+ * mode 3 after opacity_logits.  No device pointer a renderer holds changes, so the scene's renderers -- captured graphs included
+ * -- go on working.
+ * stream: a hipStream_t (NULL: the default stream).  The step is enqueued on it, behind what the caller has enqueued there;
+ * the call returns after synchronising it.  Tensors written on OTHER streams (gs_project_backward's gradients are written on
+ * the renderer's stream, but that call returns synchronised) must be complete before the call.  Frames in flight read the scene
+ * while they run: call gs_synchronize on EVERY renderer of the scene first, as gs_scene_update_from_device_arrays states.
+ * All pointers are device pointers on the scene's device; N = gs_scene_num_vertices rows each.
+ * GS_ERR_INVALID, checked before any device is touched: s or a NULL; a group with some but not all of its four pointers; a
+ * param, exp_avg or exp_avg_sq pointer that is not 4-byte aligned, a grad pointer that is not 8-byte aligned (judged by their
+ * values alone); sh_rest_coeffs not in {0, 3, 8, 15}, or sh_rest given with 0; an lr that is not finite or < 0 (of a given
+ * group); beta1 or beta2 outside [0, 1); eps not finite or < 0; a bias correction outside (0, 1].  A call with no group at
+ * all, or on a scene of no Gaussians, succeeds and does nothing.  Cost: INTEGRATION.md, 3k. */
+typedef struct {
+    float*  param;       /* [N][...] binary32, the trainer's tensor, updated in place; 4-byte aligned            */
+    double* grad;        /* same shape, binary64: what gs_project_backward added to; 8-byte aligned                */
+    float*  exp_avg;     /* same shape, binary32, updated in place                                               */
+    float*  exp_avg_sq;  /* same shape, binary32, updated in place                                               */
+    double  lr;
+} gs_adam_group;         /* all four pointers NULL: the group is not stepped and the scene keeps what it holds   */
+typedef struct {
+    gs_adam_group means, log_scales, quats, opacity_logits, sh_dc, sh_rest;   /* row shapes as gs_device_arrays */
+    uint32_t sh_rest_coeffs;        /* 0, 3, 8 or 15: sh_rest is [N][sh_rest_coeffs][3]; higher bands keep their bits */
+    const uint8_t* mask;            /* [N] by scene id, nonzero = step this Gaussian; NULL = every Gaussian */
+    double beta1, beta2, eps;
+    double bias_correction1, bias_correction2;   /* 1 - beta^t, computed by the caller */
+    int zero_grads;                 /* nonzero: the gradient rows that were consumed are set to +0.0 */
+} gs_adam_step;
+int gs_scene_adam_step(gs_scene* s, const gs_adam_step* a, void* stream);
 /* Test hook (tests/test_gpu_expf.py): evaluate the blend's exp() implementations ON THE DEVICE over the binary32 values with
  * bit patterns [first_bits, first_bits + count) (the negative floats run from 0x80000000 = -0 to 0xFF800000 = -inf).
  * block_sums[j] = sum over block j of 2^20 consecutive patterns of  bits(expf(x)) * ((bits(x) * 0x9E3779B1) | 1)  mod 2^64,
