@@ -109,7 +109,10 @@ def evaluate(x, y, lam, dtype=np.float64, mutate=None, parts=False):
             sign = np.where(d == 0, one, sign)
         l1, mse = np.abs(d).sum() / n, (d * d).sum() / n
         if lam == 0:
-            return dict(terms=np.array([l1, l1, dtype(np.nan), mse], dtype), grad=(one - lam) * sign / n)
+            out = dict(terms=np.array([l1, l1, dtype(np.nan), mse], dtype), grad=(one - lam) * sign / n)
+            if parts:
+                out.update(x=x, y=y, n=n)
+            return out
         c1, c2 = dtype(1) / dtype(10000), dtype(9) / dtype(10000)
         if dtype == np.float64:
             c1, c2 = np.float64(C1), np.float64(C2)

@@ -3,7 +3,11 @@ pinned to torch.autograd and to binary80 by tests/test_photometric_loss_api.py):
 module derives, on the images of tests/photometric_loss_images.py -- sizes below the window's radius, the kernel's tile exactly and
 one more in either axis, 5 x 6 workgroups -- both pixel strides, lambda 0 and 1, badly conditioned images, a NaN pixel; that two
 calls give the same bits; that the call stands beside a frame without touching it; and the autograd function down to forty Adam
-steps of a small scene.  Images are at most 70 x 90, the frame 200 x 120."""
+steps of a small scene.  Then the sizes at which the SUMS change regime (pli.REDUCTION_SIZES): a lane of k_loss_finish takes a
+second row, exactly the unrolled eight, a ninth, twelve; k_loss_l1 fills its capped grid, then strides; the extent of 16384 in
+either axis; on uniform images within the same bound and on dyadic images, whose l1 and mse are one correctly rounded division,
+bit for bit; the renderer's scratch carried across sizes, before any gradient call, and at pixel stride 4.  Images of the first
+seven sections are at most 70 x 90, the frame 200 x 120; the reduction sizes reach 33 x 16384 (1.6 M values, 3072 rows)."""
 import numpy as np
 import pytest
 import torch  # at collection, before the package loads its library: both must bind the same HIP runtime
@@ -258,3 +262,145 @@ def test_forty_adam_steps_lower_the_photometric_loss(pkg, gpu):
     finally:
         r.close()
         gs.close()
+
+
+# ------------------------------------------------------------------------------------------------ 8. where the sums change regime
+# pli.REDUCTION_SIZES, each on the path it was chosen for.  tests/test_photometric_loss_api.py shows on a model of the partition
+# that one dropped, doubled or stale row of partial sums at any of these sizes misses a term's bound by more than ten times.
+LAM = pli.REDUCTION_LAMBDA
+SSIM_SIZES = [(h, w) for h, w, lam in pli.REDUCTION_SIZES if lam != 0]
+L1_SIZES = [(h, w) for h, w, lam in pli.REDUCTION_SIZES if lam == 0]
+SENTINEL = 7.0     # what the outputs hold before a call: an element the call does not write is far outside any bound
+
+
+def _ids(sizes):
+    return [f"{h}x{w}" for h, w in sizes]
+
+
+def _rows(h, w, lam):
+    gy, gx = pli.ssim_rows(h, w)
+    return gy * gx if lam != 0 else pli.l1_rows(h, w)
+
+
+def _call_prefilled(rend, x, y, lam):
+    h, w = x.shape[:2]
+    grad = torch.full((h, w, 3), SENTINEL, dtype=torch.float32, device="cuda")
+    terms = torch.full((4,), SENTINEL, dtype=torch.float64, device="cuda")
+    return _call(rend, x, y, lam, grad=grad, terms=terms)
+
+
+def _same_bits(a, b):
+    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a.view(np.uint8), b.view(np.uint8))
+
+
+def _sign_over_n(x, y):
+    """lambda = 0: grad_rgb is fl32(sign(x - y) / n), one correctly rounded division and one rounding to binary32."""
+    n = 3 * x.shape[0] * x.shape[1]
+    return (np.sign(x[..., :3].astype(np.float64) - y[..., :3].astype(np.float64)) / n).astype(np.float32)
+
+
+def _assert_exact_l1_and_mse(terms, x, y, label):
+    l1, mse = pli.dyadic_exact(x, y)
+    assert float(terms[1]).hex() == l1.hex() and float(terms[3]).hex() == mse.hex(), \
+        f"{label}: l1 {float(terms[1]).hex()} against {l1.hex()}, mse {float(terms[3]).hex()} against {mse.hex()}"
+
+
+@pytest.mark.parametrize("h,w", SSIM_SIZES, ids=_ids(SSIM_SIZES))
+def test_the_finish_adds_every_row_of_the_window_path(rend, h, w):
+    name = f"uniform_{h}x{w}"
+    x, y = pli.images(name)
+    want, lim = _reference(name, x, y, LAM)
+    grad, terms = _call_prefilled(rend, x, y, LAM)
+    _assert_within_bound(grad, terms, want, lim, f"{name}, {_rows(h, w, LAM)} rows")
+    none, alone = _call(rend, x, y, LAM, grad=None)      # k_loss_ssim<false>: the same finish, no maps
+    assert none is None and _same_bits(alone, terms), "the forward alone gives other terms"
+
+
+@pytest.mark.parametrize("h,w", L1_SIZES, ids=_ids(L1_SIZES))
+def test_the_one_pass_of_lambda_zero_up_to_its_cap_and_striding_beyond(rend, h, w):
+    name = f"uniform_{h}x{w}"
+    x, y = pli.images(name)
+    want, lim = _reference(name, x, y, 0.0)
+    grad, terms = _call_prefilled(rend, x, y, 0.0)
+    _assert_within_bound(grad, terms, want, lim, f"{name}, lambda 0, {_rows(h, w, 0.0)} rows")
+    assert np.isnan(terms[2]) and terms[0] == terms[1]
+    assert _same_bits(grad, _sign_over_n(x, y)), "lambda = 0: the gradient is fl32(sign(x - y) / n)"
+    none, alone = _call(rend, x, y, 0.0, grad=None)      # k_loss_l1<false>
+    assert none is None and _same_bits(alone, terms), "the forward alone gives other terms"
+
+
+@pytest.mark.parametrize("lam", [LAM, 0.0], ids=["window", "lambda0"])
+@pytest.mark.parametrize("h,w", SSIM_SIZES + L1_SIZES, ids=_ids(SSIM_SIZES + L1_SIZES))
+def test_dyadic_images_give_l1_and_mse_bit_for_bit(rend, h, w, lam):
+    """Every size on both paths.  The sums of |x - y| and (x - y)^2 are exact in binary64 in ANY order (pli.dyadic), so l1 and mse are
+    one correctly rounded division by n whatever the device's association: unlike the bound, no slack for a row's arithmetic."""
+    name = f"dyadic_{h}x{w}"
+    x, y = pli.images(name)
+    grad, terms = _call_prefilled(rend, x, y, lam)
+    label = f"{name}, lambda {lam}, {_rows(h, w, lam)} rows"
+    _assert_exact_l1_and_mse(terms, x, y, label)
+    if lam == 0:
+        assert float(terms[0]).hex() == float(terms[1]).hex() and np.isnan(terms[2]), label
+        assert _same_bits(grad, _sign_over_n(x, y)), label
+    else:
+        want, lim = _reference(name, x, y, lam)
+        _assert_within_bound(grad, terms, want, lim, label)
+
+
+def test_the_scratch_of_one_size_does_not_reach_the_sums_of_the_next(rend):
+    """One renderer, one scratch: 3072 rows, then 257, then k_loss_l1's 2048 (of which 257 .. 2047 would still hold the first call's
+    sums had nothing rewritten them), 302, and the first size again.  A finish that reads a row beyond this call's count, or a
+    kernel that leaves one of its rows unwritten, adds a stale row: l1 and mse of a dyadic pair then miss their bit pattern."""
+    order = [(33, 16384, LAM), (16, 4112, LAM), (350, 1249, 0.0), (161, 160, 0.0), (33, 16384, LAM)]
+    assert [_rows(*o) for o in order] == [3072, 257, 2048, 302, 3072]
+    got = []
+    for k, (h, w, lam) in enumerate(order):
+        x, y = pli.images(f"dyadic_{h}x{w}")
+        got.append(_call_prefilled(rend, x, y, lam))
+        _assert_exact_l1_and_mse(got[-1][1], x, y, f"call {k + 1}, {h} x {w}, lambda {lam}")
+        if lam == 0:
+            assert _same_bits(got[-1][0], _sign_over_n(x, y))
+    assert _same_bits(got[4][1], got[0][1]) and _same_bits(got[4][0], got[0][0]), "the first size again gives other bits"
+    x, y = pli.images("dyadic_33x16384")
+    want, lim = _reference("dyadic_33x16384", x, y, LAM)
+    _assert_within_bound(*got[4], want, lim, "33 x 16384 after three other sizes")
+
+
+def test_the_forward_alone_on_a_renderer_that_never_formed_a_gradient(pkg, gpu):
+    """The map scratch has never been allocated when k_loss_ssim<false> runs; the later call with the gradient allocates it."""
+    h, w = 17, 16384
+    name = f"uniform_{h}x{w}"
+    x, y = pli.images(name)
+    want, lim = _reference(name, x, y, LAM)
+    scene = pkg.Scene.from_records(pkg.synth.synth_records(64, seed=3, kind="A"), device=0)
+    r = pkg.Renderer(scene)
+    try:
+        none, alone = _call(r, x, y, LAM, grad=None)
+        grad, terms = _call_prefilled(r, x, y, LAM)
+    finally:
+        r.close()
+        scene.close()
+    assert none is None and _same_bits(alone, terms), "the forward alone gives other terms"
+    _assert_within_bound(grad, terms, want, lim, f"{name} on a fresh renderer")
+
+
+@pytest.mark.parametrize("h,w,lam", [(33, 16384, LAM), (350, 1249, 0.0)], ids=["33x16384", "350x1249-lambda0"])
+def test_two_calls_give_the_same_bits_where_lanes_take_many_rows(rend, h, w, lam):
+    name = f"uniform_{h}x{w}"
+    x, y = pli.images(name)
+    want, lim = _reference(name, x, y, lam)
+    first, second = _call_prefilled(rend, x, y, lam), _call_prefilled(rend, x, y, lam)
+    assert _same_bits(first[0], second[0]) and _same_bits(first[1], second[1])
+    _assert_within_bound(*second, want, lim, f"{name}, lambda {lam}, the second call")
+
+
+def test_pixel_stride_four_at_the_extent(rend):
+    """17 x 16384 at strides (4, 4): p * stride there is the largest index any test forms.  Bit-equal to strides (3, 3)."""
+    h, w = 17, 16384
+    name = f"uniform_{h}x{w}"
+    x, y = pli.images(name)
+    want, lim = _reference(name, x, y, LAM)
+    plain = _call_prefilled(rend, x, y, LAM)
+    grad, terms = _call_prefilled(rend, pli.widen(x, 0.75), pli.widen(y, -3.0), LAM)
+    _assert_within_bound(grad, terms, want, lim, f"{name}, strides 4 and 4")
+    assert _same_bits(grad, plain[0]) and _same_bits(terms, plain[1])

@@ -3,15 +3,21 @@
 float64 restatement written the way the trainers write it (tests/photometric_loss_torch.py), within the bound the module derives,
 on every image of tests/photometric_loss_images.py and lambda in 0, 0.2, 1; it lies within a QUARTER of that bound of the same
 formulas in binary80, so the yardstick itself is inside the contract; and each single-term mutation of it misses the bound by
-more than ten times on some listed image.  Then the entry point's refusals, the structure's layout and the wrapper's checks."""
+more than ten times on some listed image.  Then the sizes at which the device's SUMS change regime (pli.REDUCTION_SIZES): that
+they reach the regimes they were chosen for, recomputed from the kernels' constants; that the dyadic images' l1 and mse are what
+integer arithmetic gives; and, on a model of the device's partition into partial-sum rows (tests/photometric_loss_rows.py), that
+one dropped, doubled or stale row anywhere misses a term's bound by more than ten times, so the GPU tests at those sizes have
+teeth.  Then the entry point's refusals, the structure's layout and the wrapper's checks."""
 import ctypes as C
 import os
+from fractions import Fraction
 
 import numpy as np
 import pytest
 
 import photometric_loss_images as pli
 import photometric_loss_reference as plr
+import photometric_loss_rows as plrows
 import photometric_loss_torch as plt_
 
 INVALID = -1
@@ -66,6 +72,17 @@ def test_the_reference_is_what_autograd_finds_for_the_trainers_own_formulation(n
 @pytest.mark.parametrize("lam", LAMBDAS)
 @pytest.mark.parametrize("name", pli.NAMES)
 def test_the_reference_lies_within_a_quarter_of_the_bound_of_binary80(name, lam):
+    _assert_within_a_quarter_of_binary80(name, lam)
+
+
+@pytest.mark.parametrize("h,w", [(1, pli.MAX_EXTENT), (pli.MAX_EXTENT, 1)])
+def test_the_reference_lies_within_a_quarter_of_the_bound_of_binary80_on_the_thin_images_at_the_extent(h, w):
+    """One pixel across: every window is mostly padding, and the sums have 3 x 16384 addends.  New geometry for the yardstick."""
+    assert (h, w, pli.REDUCTION_LAMBDA) in pli.REDUCTION_SIZES
+    _assert_within_a_quarter_of_binary80(f"uniform_{h}x{w}", pli.REDUCTION_LAMBDA)
+
+
+def _assert_within_a_quarter_of_binary80(name, lam):
     assert np.finfo(np.longdouble).nmant >= 63, "this host's long double is no wider than binary64"
     exact = reference(name, lam, dtype=np.longdouble)
     want, lim = reference(name, lam), limit(name, lam)
@@ -106,7 +123,137 @@ def test_the_mutations_are_the_eight_the_contract_names():
                                         "0x1.b43c3f52b19f2p-3", "0x1.106560aa892c0p-2"]       # gs_loss.hip's constants
 
 
-# ------------------------------------------------------------------------------------------------ 4. the C entry point
+# ------------------------------------------------------------------------------------------------ 4. where the sums change regime
+SSIM_SIZES = tuple((h, w) for h, w, lam in pli.REDUCTION_SIZES if lam != 0)
+L1_SIZES = tuple((h, w) for h, w, lam in pli.REDUCTION_SIZES if lam == 0)
+_IDS = [f"{h}x{w}-lambda{lam}" for h, w, lam in pli.REDUCTION_SIZES]
+
+
+def test_the_reduction_sizes_stay_out_of_the_per_name_tests():
+    assert not set(SSIM_SIZES + L1_SIZES) & set(pli.SIZES)
+    assert len(pli.NAMES) == len(pli.SIZES) + len(pli.CONDITIONING) == 16, "the NAMES product (torch and binary80 per entry) has grown"
+    assert not any(f"{h}x{w}" in name for h, w, _ in pli.REDUCTION_SIZES for name in pli.NAMES)
+    assert len(set(pli.REDUCTION_SIZES)) == len(pli.REDUCTION_SIZES) == 13 and len(SSIM_SIZES) == 8 and len(L1_SIZES) == 5
+    assert all(lam in (0.0, pli.REDUCTION_LAMBDA) for _, _, lam in pli.REDUCTION_SIZES)
+
+
+def test_the_constants_are_the_kernels(pkg):
+    src = open(os.path.join(os.path.dirname(pkg.binding.__file__), "csrc", "gs_loss.hip")).read()
+    for text in (f"constexpr int kLossTile = {pli.TILE};", f"constexpr int kLossThreads = {pli.THREADS};",
+                 f"constexpr uint32_t kLossL1Groups = {pli.L1_GROUPS};", f"#pragma unroll {pli.FINISH_UNROLL}\n    for (uint32_t r = threadIdx.x; r < rows;"):
+        assert text in src, text
+    assert pkg.binding.PHOTO_LOSS_MAX_EXTENT == pli.MAX_EXTENT
+
+
+def test_the_ssim_path_sizes_reach_the_regimes_their_comments_claim():
+    T, U8, tiles = pli.THREADS, pli.FINISH_UNROLL, {hw: pli.ssim_rows(*hw) for hw in SSIM_SIZES}
+    rows = {hw: gy * gx for hw, (gy, gx) in tiles.items()}
+    assert all(1 <= v <= pli.MAX_EXTENT for hw in SSIM_SIZES for v in hw)
+    assert tiles[16, 4112] == (1, 257) and rows[16, 4112] == T + 1                 # lane 0 of the finish, and no other, takes a second row
+    assert tiles[272, 272] == (17, 17) and rows[272, 272] > T                      # many tiles in both axes, and a second row for some lanes
+    assert tiles[1, 16384] == (1, pli.MAX_EXTENT // pli.TILE) == (1, 1024)         # the extent across: 1024 tiles in a row ...
+    assert 1 + plr.RADIUS < pli.TILE                                               # ... whose tile rows above and below row 0 are all padding
+    assert tiles[16384, 1] == (1024, 1)                                            # the extent down: gridDim.y = 1024
+    assert tiles[368, 1424] == (23, 89) and rows[368, 1424] == U8 * T - 1          # lanes take 7 or 8 rows: lane 255 stops one short of the body
+    assert tiles[17, 16384] == (2, 1024) and rows[17, 16384] == U8 * T             # 8 rows for every lane: the unrolled body alone
+    assert tiles[48, 10928] == (3, 683) and rows[48, 10928] == U8 * T + 1          # lane 0 takes a 9th row: the body, then a remainder of one
+    assert tiles[33, 16384] == (3, 1024) and rows[33, 16384] == 12 * T == 3072     # 12 rows per lane:
+    assert 12 > U8 and 12 % U8 != 0 and 33 % pli.TILE == 1                         # body plus remainder; the last tile row holds ONE image row
+    assert max(rows.values()) == 3072 and sorted(rows.values()) == [257, 289, 1024, 1024, 2047, 2048, 2049, 3072]
+    # every SSIM-path row count fits the scratch k_loss_l1 may have sized (photo_loss_partials: max(rows, L1_GROUPS)) or exceeds it
+    assert sum(r > pli.L1_GROUPS for r in rows.values()) == 2
+
+
+def test_the_l1_path_sizes_reach_the_regimes_their_comments_claim():
+    T, cap = pli.THREADS, pli.L1_GROUPS * pli.THREADS
+    E = {hw: 3 * hw[0] * hw[1] for hw in L1_SIZES}
+    rows = {hw: pli.l1_rows(*hw) for hw in L1_SIZES}
+    assert cap == 524288
+    assert E[160, 160] == 76800 == 300 * T and rows[160, 160] == 300 < pli.L1_GROUPS             # every workgroup full, no stride
+    assert E[161, 160] == 77280 and rows[161, 160] == 302 and 0 < E[161, 160] % T < T            # the last workgroup partly idle
+    assert E[126, 1387] == cap - 2 and rows[126, 1387] == pli.L1_GROUPS                          # the cap's grid, no lane strides, two idle
+    assert -(-E[126, 1387] // T) == pli.L1_GROUPS                                                # ... reached, not exceeded
+    assert E[183, 955] == cap + 7 and rows[183, 955] == pli.L1_GROUPS                            # seven lanes take a second element
+    assert -(-E[183, 955] // T) > pli.L1_GROUPS                                                  # ... only because of the cap
+    assert E[350, 1249] == 1311450 and 2 * cap < E[350, 1249] < 3 * cap and rows[350, 1249] == pli.L1_GROUPS   # lanes take 2 or 3
+
+
+@pytest.mark.parametrize("h,w,lam", pli.REDUCTION_SIZES, ids=_IDS)
+def test_the_dyadic_images_terms_are_what_integer_arithmetic_gives(h, w, lam):
+    x, y = pli.images(f"dyadic_{h}x{w}")
+    n = 3 * h * w
+    assert 256 * n < 2 ** 53 and 65536 * n < 2 ** 53, "the scaled sums could leave binary64's integers"
+    for a in (x, y):
+        k = a.astype(np.float64) * 256
+        assert a.dtype == np.float32 and a.shape == (h, w, 3) and np.array_equal(k, np.rint(k)) and k.min() >= 0 and k.max() <= 256
+    assert not np.array_equal(x, y)
+    l1, mse = pli.dyadic_exact(x, y)
+    terms = plr.evaluate(x, y, 0.0)["terms"]          # (l1 and mse do not depend on lambda)
+    assert terms[1] == l1 and terms[3] == mse and terms[0] == l1 and l1 > 0 and mse > 0
+    if n <= 3 * 161 * 160:      # the same from rationals, where that is quick
+        fx, fy = ([Fraction(float(v)) for v in a.ravel()] for a in (x, y))
+        assert l1 == float(sum(abs(p - q) for p, q in zip(fx, fy)) / n) and mse == float(sum((p - q) ** 2 for p, q in zip(fx, fy)) / n)
+
+
+def _partition(h, w, lam):
+    """(the model's [rows][3] partial sums, the reference's l1, ssim, mse, their bounds, n) on the uniform images."""
+    key = ("rows", h, w, lam)
+    if key not in _cache:
+        x, y = pli.images(f"uniform_{h}x{w}")
+        q = plr.evaluate(x, y, lam, parts=True)
+        _cache[key] = (plrows.partial_rows(x, y, lam, q), q["terms"][1:].copy(), plr.bound(x, y, lam)["terms"][1:].copy(), float(q["n"]))
+    return _cache[key]
+
+
+def _escapes(delta, n, lim):
+    """delta: [k][3], what a fault adds to the three sums.  (rows of delta that move NO term by more than ten bounds, the weakest
+    row's best ratio.)  ssim at lambda = 0 is not evaluated (a NaN bound): it cannot witness."""
+    with np.errstate(invalid="ignore"):
+        ratio = np.where(np.isnan(lim), 0.0, np.abs(delta) / n / lim)
+    best = ratio.max(axis=1)
+    return np.flatnonzero(~(best > 10.0)), float(best.min())
+
+
+def test_the_partition_model_has_the_row_counts_of_the_launch():
+    for h, w, lam in pli.REDUCTION_SIZES:
+        gy, gx = pli.ssim_rows(h, w)
+        assert len(_partition(h, w, lam)[0]) == (gy * gx if lam != 0 else pli.l1_rows(h, w))
+    # ... and its order: tile (by, bx) of the SSIM path is row by * gx + bx, element e of the L1 path is in row (e / THREADS) mod rows
+    x, y = pli.images("uniform_272x272")
+    d = np.abs(x.astype(np.float64) - y.astype(np.float64))
+    rows = _partition(272, 272, pli.REDUCTION_LAMBDA)[0]
+    assert rows[3 * 17 + 5, 0] == pytest.approx(d[48:64, 80:96].sum(), rel=1e-13) and rows[16 * 17 + 16, 0] == pytest.approx(d[256:, 256:].sum(), rel=1e-13)
+    x, y = pli.images("uniform_183x955")
+    d = np.abs(x.astype(np.float64) - y.astype(np.float64)).ravel()
+    rows = _partition(183, 955, 0.0)[0]
+    assert rows[0, 0] == pytest.approx(d[:256].sum() + d[524288:].sum(), rel=1e-13) and rows[1, 0] == pytest.approx(d[256:512].sum(), rel=1e-13)
+    assert (rows[:, 1] == 0).all()
+
+
+@pytest.mark.parametrize("h,w,lam", pli.REDUCTION_SIZES, ids=_IDS)
+def test_one_dropped_doubled_or_stale_partial_row_misses_the_bound_by_ten_times(h, w, lam):
+    """The GPU tests hold the terms to plr.bound at these sizes; that is only a test of the finish if ONE wrong row shows.  Every row
+    of every size, three faults each; no row may escape.  (Had one escaped, the remedy is another seed or image for that size, never
+    another factor: none was needed, every size is on the uniform images of seeds 1 and 2 like the sizes of pli.SIZES.)"""
+    rows, terms, lim, n = _partition(h, w, lam)
+    witness = ~np.isnan(lim)
+    assert (np.abs(rows.sum(axis=0) / n - terms)[witness] <= lim[witness]).all(), "the model's rows do not sum to the reference's terms"
+    assert witness.sum() == (3 if lam != 0 else 2) and (lim[witness] > 0).all()
+    escaped, weakest = _escapes(rows, n, lim)          # dropped: the sums lose the row; doubled: they gain it once more
+    print(f"{h} x {w}, lambda {lam}: {len(rows)} rows; a dropped or doubled row moves a term by at least {weakest:.3g} bounds", end="")
+    assert len(escaped) == 0, f"dropping or doubling row {escaped[0]} of {len(rows)} moves no term by ten bounds ({weakest:.3g})"
+    for oh, ow, olam in pli.REDUCTION_SIZES:           # stale: the row still holds what another size's call left at its index
+        if (oh, ow, olam) == (h, w, lam):
+            continue
+        other = _partition(oh, ow, olam)[0]
+        k = min(len(rows), len(other))
+        escaped, ratio = _escapes(other[:k] - rows[:k], n, lim)
+        weakest = min(weakest, ratio)
+        assert len(escaped) == 0, f"row {escaped[0]} left by {oh} x {ow}, lambda {olam}, moves no term by ten bounds ({ratio:.3g})"
+    print(f"; any fault, a stale row included, by at least {weakest:.3g}")
+
+
+# ------------------------------------------------------------------------------------------------ 5. the C entry point
 MEMBERS = ("image", "target", "width", "height", "image_stride", "target_stride", "lambda_dssim", "terms", "grad_rgb")
 
 
