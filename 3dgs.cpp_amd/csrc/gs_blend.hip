@@ -213,6 +213,28 @@ struct PairLoopEvent {
         "v_mul_f32 v55, v55, v59\n\t"             /* c01' dx dy */                                                            \
         "v_add_f32 v54, v55, v54\n\t"             /* pn = -power                          (render.comp:66) */                 \
         "v_cmpx_le_u32 vcc, v54, v63\n\t"         /* +0 <= pn <= ncut: power <= 0 and power >= the alpha cut (render.comp:68,78) */
+// Round 26: two paths per pair.  A pixel breaks at most once, so the break's bookkeeping (mk, exec &= ~mk, alive &= ~mk, "the last
+// pixel died") serves 13 % of config B's pairs.  ONE compare on the new T decides: T (1 - alpha) < slice_hi, the first binary32 above
+// the guard's slice (0x38D20000, 1.00434e-4 > 1e-4).  No lane below it: nobody breaks and nobody is in the slice -- accumulate
+// under exec = m2 as it is, restore exec, next pair (FAST path).  Some lane below it: the out-of-line stub GS_PAIR_SLOW takes the
+// break compare, the slice compare and the bookkeeping as before, and returns to the copy's `s_mov exec, alive`.
+// And the count goes per group of four: alive changes on the slow path alone, so the fast path need not ask after every pair whether
+// the chunk has ended.  The kept entries are staged RIGHT-ALIGNED to a multiple of four (blend_walk: `pad` empty slots ahead of them), the
+// loop is entered at the copy 3 - (rem & 3), and `rem` counts groups of four inside the string (one s_add beside the address's v_add).
+// The stubs leave directly when alive becomes 0, and the event exits rebuild the pair count from the group count and their own J.
+// Per pair on the fast path: 22.25 vector + 3.5 scalar instructions (s_nop, s_cbranch_vccnz, s_mov exec; s_add and the back edge per
+// four) where round 6 had 23.25 + 8; a pair that takes the stub: 24.25 + 7.5, two taken branches more.  Same arithmetic, frames
+// bit-identical; measured in profiles/r26_pair_loop_paths.txt, the loop shapes alone in tools/ubench/pair_loop_model.hip (modes 11-15).
+static_assert(kGuardSlice == 0x38D1u, "slice_hi below is (kGuardSlice + 1) << 16");
+// the quadrant's last pixel broke (scc of alive &= ~mk): the loop is over
+#define GS_PAIR_LAST_PIXEL(J)                                                                                                 \
+        "s_cbranch_scc1 .Lgs_next" GS_STR(J) "_%=\n\t"                                                                        \
+        "s_branch .Lgs_done_%=\n"
+// leave with the pending pair: rem = the pairs behind it (4 groups + 3 - J), the address at the group the next pair is in
+#define GS_PAIR_EVENT_OUT(J)                                                                                                  \
+        "s_lshl_b32 %[rem], %[rem], 2\n\t"                                                                                    \
+        "s_add_u32 %[rem], %[rem], 3-" GS_STR(J) "\n\t"                                                                       \
+        "v_add_u32 %[addr], (" GS_STR(J) "/3)*64, %[addr]\n\t"
 #define GS_PAIR_GUARDED(J)                                                                                                    \
         GS_PAIR_HEAD(J)                                                                                                       \
         "v_mul_f32 v56, 0xbfb8aa3b, v54\n\t"      /* power log2 e */                                                          \
@@ -223,22 +245,29 @@ struct PairLoopEvent {
         "v_sub_f32 v55, 1.0, v56\n\t"             /* 1 - alpha */                                                             \
         "v_mul_f32 %[w], v56, %[T]\n\t"           /* alpha T: the weight of this entry (the T of before) */                   \
         "v_mul_f32 %[T], %[T], v55\n\t"           /* test_T = T (1 - alpha), in place */                                      \
+        "v_cmp_gt_f32 vcc, 0x38d20000, %[T]\n\t"  /* test_T < slice_hi: can a lane break, or lie in the guard's slice? */     \
+        "s_cbranch_vccnz .Lgs_slow" GS_STR(J) "_%=\n\t"                                                                       \
+        "v_fmac_f32 %[c0], v60, %[w]\n\t"         /* render.comp:87 (the guarded mode's fused form) */                        \
+        "v_fmac_f32 %[c1], v61, %[w]\n\t"                                                                                     \
+        "v_fmac_f32 %[c2], v62, %[w]\n"                                                                                       \
+        ".Lgs_next" GS_STR(J) "_%=:\n\t"                                                                                      \
+        "s_mov_b64 exec, %[alive]\n\t"
+// a lane of m2 below slice_hi: render.comp:83's compare and the slice's, then the bookkeeping of a break (mk may still be 0).
+// A lane of m2 inside the slice: inside the guard's COARSE window as well?  (under exec = m2: bits of m2's lanes only.)  No: every
+// decision of this pair is the fast arithmetic's, carry on (T(6e6): most slice hits end here).  Yes: leave with the pending pair --
+// exec restored FIRST (the address register belongs to every lane), then the address moved.
+#define GS_PAIR_SLOW(J)                                                                                                       \
+        ".Lgs_slow" GS_STR(J) "_%=:\n\t"                                                                                      \
         "v_cmp_gt_f32 %[mk], %[k1e4], %[T]\n\t"   /* test_T < 1e-4                     (render.comp:83) */                    \
         "v_cmp_eq_u32_sdwa vcc, %[T], %[slice] src0_sel:WORD_1 src1_sel:DWORD\n\t"  /* ... any of them inside the guard's slice? */ \
         "s_cbranch_vccnz .Lgs_slice" GS_STR(J) "_%=\n"                                                                        \
         ".Lgs_cont" GS_STR(J) "_%=:\n\t"                                                                                      \
         "s_andn2_b64 exec, exec, %[mk]\n\t"                                                                                   \
-        "v_fmac_f32 %[c0], v60, %[w]\n\t"         /* render.comp:87 (the guarded mode's fused form) */                        \
+        "v_fmac_f32 %[c0], v60, %[w]\n\t"                                                                                     \
         "v_fmac_f32 %[c1], v61, %[w]\n\t"                                                                                     \
         "v_fmac_f32 %[c2], v62, %[w]\n\t"                                                                                     \
         "s_andn2_b64 %[alive], %[alive], %[mk]\n\t"                                                                           \
-        "s_cselect_b32 %[rem], %[rem], 0\n\t"     /* the quadrant's last pixel has saturated: this was the last pair */       \
-        "s_mov_b64 exec, %[alive]\n\t"                                                                                        \
-        "s_add_u32 %[rem], %[rem], -1\n\t"        /* carry = there was another pair */
-// a lane of m2 inside the slice: inside the guard's COARSE window as well?  (under exec = m2: bits of m2's lanes only.)  No: every
-// decision of this pair is the fast arithmetic's, carry on (T(6e6): most slice hits end here).  Yes: leave with the pending pair --
-// exec restored FIRST (the address register belongs to every lane), then the address put past the pair.
-#define GS_PAIR_SLICE(J)                                                                                                      \
+        GS_PAIR_LAST_PIXEL(J)                                                                                                 \
         ".Lgs_slice" GS_STR(J) "_%=:\n\t"                                                                                     \
         "v_cmp_le_f32 %[sl], %[klo], %[T]\n\t"                                                                                \
         "v_cmp_gt_f32 %[m2], %[khi], %[T]\n\t"                                                                                \
@@ -246,11 +275,12 @@ struct PairLoopEvent {
         "s_cbranch_scc0 .Lgs_cont" GS_STR(J) "_%=\n\t"                                                                        \
         "s_mov_b64 %[m2], exec\n\t"                                                                                           \
         "s_mov_b64 exec, %[sv]\n\t"                                                                                           \
-        "v_add_u32 %[addr], 16+" GS_STR(J) "*16, %[addr]\n\t"                                                                 \
+        GS_PAIR_EVENT_OUT(J)                                                                                                  \
         "s_branch .Lgs_event_%=\n"
-// slab_addr: LDS byte address of the next entry's {c00' c01' c11' o} (the other two planes 1024 and 2048 bytes behind it);
+// slab_addr: LDS byte address of the group of four slots the next entry is in (its {c00' c01' c11' o}; the other two planes 1024 and
+// 2048 bytes behind), the entry itself in slot 3 - (rem & 3) of the group;
 // rem: pairs left in the chunk MINUS ONE.  Returns 0 when the chunk is exhausted or alive == 0, 1 with `ev` filled (rem then
-// still counts the pending pair, slab_addr is already past it).
+// still counts the pending pair, slab_addr is that of the pair behind it).
 __device__ __forceinline__ uint32_t blend_pair_loop(uint32_t& slab_addr, uint32_t& rem, uint64_t& alive, const float fx, const float fy, float& T,
                                                     float& c0, float& c1, float& c2, PairLoopEvent& ev) {
     uint32_t event;
@@ -261,24 +291,32 @@ __device__ __forceinline__ uint32_t blend_pair_loop(uint32_t& slab_addr, uint32_
     uint32_t left = (uint32_t)__builtin_amdgcn_readfirstlane((int)rem);
     asm volatile(
         "s_mov_b64 %[sv], exec\n\t"
-        "s_mov_b64 exec, %[alive]\n"
+        "s_mov_b64 exec, %[alive]\n\t"
+        "s_and_b32 %[ev], %[rem], 3\n\t"          /* enter at copy 3 - (rem & 3); rem <- groups of four behind this one */
+        "s_lshr_b32 %[rem], %[rem], 2\n\t"
+        "s_cmp_lt_u32 %[ev], 2\n\t"
+        "s_cbranch_scc1 .Lgs_enter23_%=\n\t"
+        "s_cmp_eq_u32 %[ev], 2\n\t"
+        "s_cbranch_scc1 .Lgs_pair1_%=\n"
         GS_PAIR_GUARDED(0)
-        "s_cbranch_scc0 .Lgs_done_%=\n"
         GS_PAIR_GUARDED(1)
-        "s_cbranch_scc0 .Lgs_done_%=\n"
         GS_PAIR_GUARDED(2)
-        "s_cbranch_scc0 .Lgs_done_%=\n"
         GS_PAIR_GUARDED(3)
         "v_add_u32 %[addr], 64, %[addr]\n\t"
+        "s_add_u32 %[rem], %[rem], -1\n\t"        /* carry = there was another group of four */
         "s_cbranch_scc1 .Lgs_pair0_%=\n"
         ".Lgs_done_%=:\n\t"
         "s_mov_b32 %[ev], 0\n\t"
         "s_mov_b64 exec, %[sv]\n\t"
         "s_branch .Lgs_exit_%=\n"
-        GS_PAIR_SLICE(0)
-        GS_PAIR_SLICE(1)
-        GS_PAIR_SLICE(2)
-        GS_PAIR_SLICE(3)
+        ".Lgs_enter23_%=:\n\t"
+        "s_cmp_eq_u32 %[ev], 1\n\t"
+        "s_cbranch_scc1 .Lgs_pair2_%=\n\t"
+        "s_branch .Lgs_pair3_%=\n"
+        GS_PAIR_SLOW(0)
+        GS_PAIR_SLOW(1)
+        GS_PAIR_SLOW(2)
+        GS_PAIR_SLOW(3)
         ".Lgs_event_%=:\n\t"
         "s_mov_b32 %[ev], 1\n"
         ".Lgs_exit_%=:"
@@ -295,10 +333,12 @@ __device__ __forceinline__ uint32_t blend_pair_loop(uint32_t& slab_addr, uint32_
 // every product of color * alpha * T and every sum rounded on its own).  No events: the loop ends with the chunk or with the quadrant's last
 // pixel.  Operation for operation the arithmetic of the compiler's form (the exact mode's frames are the reference's bit for bit either
 // way: the parity tests run in this mode); what goes is its mask traffic -- 17 scalar instructions and three taken branches per pair down to
-// 7 and one.  Registers: v[52:63] clobbered -- the record in v[54:63]; binary64 temporaries in the even-aligned pairs v[52:53] (the table
+// 7 and one (round 26: 3.5 on the fast path, below).  Registers: v[52:63] clobbered -- the record in v[54:63]; binary64 temporaries in the even-aligned pairs v[52:53] (the table
 // entry, then y), v[54:55] (kd, then the cubic), v[58:59] (x, r, r s) as the record's fields retire.
 // Round 6: the single unsigned compare on pn = -power and the unroll by four of the guarded loop (see there); gs_expf_libm takes
 // power = -pn through the conversion's sign modifier.  The exp section is thirty issue slots here: pairs no pixel keeps branch over it.
+// Round 26: the guarded loop's two paths and its count per group of four (see there), with vcc = test_T < 1e-4 deciding: there is no
+// slice here, a pair takes the stub exactly when a pixel breaks at it.
 #define GS_PAIR_EXACT(J)                                                                                                      \
         GS_PAIR_HEAD(J)                                                                                                       \
         "s_cbranch_execz .Lgs_xskip" GS_STR(J) "_%=\n\t"                                                                      \
@@ -321,8 +361,12 @@ __device__ __forceinline__ uint32_t blend_pair_loop(uint32_t& slab_addr, uint32_
         "v_min_f32 v54, 0x3f7d70a4, v54\n\t"      /* alpha = min(0.99, .)             (render.comp:77) */                     \
         "v_sub_f32 v55, 1.0, v54\n\t"             /* 1 - alpha */                                                             \
         "v_mul_f32 v55, %[T], v55\n\t"            /* test_T = T (1 - alpha) */                                                \
-        "v_cmp_gt_f32 %[mk], %[k1e4], v55\n\t"    /* test_T < 1e-4: the pixel is done   (render.comp:83; under exec = m2) */  \
-        "s_andn2_b64 exec, exec, %[mk]\n\t"                                                                                   \
+        "v_cmp_gt_f32 vcc, %[k1e4], v55\n\t"      /* test_T < 1e-4: the pixel is done   (render.comp:83; under exec = m2) */  \
+        "s_cbranch_vccnz .Lgs_xslow" GS_STR(J) "_%=\n\t"                                                                       \
+        GS_EXACT_ACCUMULATE                                                                                                   \
+        ".Lgs_xskip" GS_STR(J) "_%=:\n\t"                                                                                     \
+        "s_mov_b64 exec, %[alive]\n\t"
+#define GS_EXACT_ACCUMULATE                                                                                                   \
         "v_mul_f32 v60, v60, v54\n\t"             /* color * alpha * T, left to right    (render.comp:87) */                  \
         "v_mul_f32 v61, v61, v54\n\t"                                                                                         \
         "v_mul_f32 v62, v62, v54\n\t"                                                                                         \
@@ -332,36 +376,55 @@ __device__ __forceinline__ uint32_t blend_pair_loop(uint32_t& slab_addr, uint32_
         "v_add_f32 %[c0], %[c0], v60\n\t"                                                                                     \
         "v_add_f32 %[c1], %[c1], v61\n\t"                                                                                     \
         "v_add_f32 %[c2], %[c2], v62\n\t"                                                                                     \
-        "v_mov_b32 %[T], v55\n\t"                                                                                             \
-        "s_andn2_b64 %[alive], %[alive], %[mk]\n\t"                                                                           \
-        "s_cselect_b32 %[rem], %[rem], 0\n"       /* the quadrant's last pixel is done: this was the last pair */             \
-        ".Lgs_xskip" GS_STR(J) "_%=:\n\t"                                                                                     \
-        "s_mov_b64 exec, %[alive]\n\t"                                                                                        \
-        "s_add_u32 %[rem], %[rem], -1\n\t"        /* carry = there was another pair */
+        "v_mov_b32 %[T], v55\n"
+// a lane of m2 breaks here (vcc, which none of the accumulate's instructions writes): the others accumulate, the pixel leaves alive;
+// the quadrant's last pixel: the loop is over
+#define GS_PAIR_EXACT_SLOW(J)                                                                                                 \
+        ".Lgs_xslow" GS_STR(J) "_%=:\n\t"                                                                                     \
+        "s_andn2_b64 exec, exec, vcc\n\t"                                                                                     \
+        GS_EXACT_ACCUMULATE                                                                                                   \
+        "\ts_andn2_b64 %[alive], %[alive], vcc\n\t"                                                                           \
+        "s_cbranch_scc1 .Lgs_xskip" GS_STR(J) "_%=\n\t"                                                                       \
+        "s_branch .Lgs_xdone_%=\n"
 __device__ __forceinline__ void blend_pair_loop_exact(uint32_t slab_addr, const uint32_t rem, uint64_t& alive, const float fx, const float fy,
                                                       float& T, float& c0, float& c1, float& c2, const uint2* __restrict__ tab) {
     const double InvLn2N = 0x1.71547652b82fep+0 * 32.0, SHIFT = 0x1.8p+52;  // gs_expf_libm's constants
     const double C0 = 0x1.c6af84b912394p-5 / 32.0 / 32.0 / 32.0, C1 = 0x1.ebfce50fac4f3p-3 / 32.0 / 32.0, C2 = 0x1.62e42ff0c52d6p-1 / 32.0;
     const float k1e4 = 0.0001f;
-    uint64_t saved, mk;
+    uint64_t saved;
+    uint32_t enter;
     uint32_t left = (uint32_t)__builtin_amdgcn_readfirstlane((int)rem);
     const uint32_t tab_addr = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uintptr_t)tab);  // (wave-uniform: the wave's copy in LDS)
     asm volatile(
         "s_mov_b64 %[sv], exec\n\t"
-        "s_mov_b64 exec, %[alive]\n"
+        "s_mov_b64 exec, %[alive]\n\t"
+        "s_and_b32 %[en], %[rem], 3\n\t"          /* enter at copy 3 - (rem & 3); rem <- groups of four behind this one */
+        "s_lshr_b32 %[rem], %[rem], 2\n\t"
+        "s_cmp_lt_u32 %[en], 2\n\t"
+        "s_cbranch_scc1 .Lgs_xenter23_%=\n\t"
+        "s_cmp_eq_u32 %[en], 2\n\t"
+        "s_cbranch_scc1 .Lgs_pair1_%=\n"
         GS_PAIR_EXACT(0)
-        "s_cbranch_scc0 .Lgs_xdone_%=\n"
         GS_PAIR_EXACT(1)
-        "s_cbranch_scc0 .Lgs_xdone_%=\n"
         GS_PAIR_EXACT(2)
-        "s_cbranch_scc0 .Lgs_xdone_%=\n"
         GS_PAIR_EXACT(3)
         "v_add_u32 %[addr], 64, %[addr]\n\t"
+        "s_add_u32 %[rem], %[rem], -1\n\t"        /* carry = there was another group of four */
         "s_cbranch_scc1 .Lgs_pair0_%=\n"
         ".Lgs_xdone_%=:\n\t"
-        "s_mov_b64 exec, %[sv]"
+        "s_mov_b64 exec, %[sv]\n\t"
+        "s_branch .Lgs_xexit_%=\n"
+        ".Lgs_xenter23_%=:\n\t"
+        "s_cmp_eq_u32 %[en], 1\n\t"
+        "s_cbranch_scc1 .Lgs_pair2_%=\n\t"
+        "s_branch .Lgs_pair3_%=\n"
+        GS_PAIR_EXACT_SLOW(0)
+        GS_PAIR_EXACT_SLOW(1)
+        GS_PAIR_EXACT_SLOW(2)
+        GS_PAIR_EXACT_SLOW(3)
+        ".Lgs_xexit_%=:"
         : [c0] "+v"(c0), [c1] "+v"(c1), [c2] "+v"(c2), [T] "+v"(T), [addr] "+v"(slab_addr), [alive] "+s"(alive), [rem] "+s"(left),
-          [mk] "=&s"(mk), [sv] "=&s"(saved)
+          [en] "=&s"(enter), [sv] "=&s"(saved)
         : [fx] "v"(fx), [fy] "v"(fy), [k1e4] "s"(k1e4), [tab] "s"(tab_addr), [iln] "s"(InvLn2N), [shift] "v"(SHIFT), [C0] "s"(C0), [C1] "v"(C1),
           [C2] "v"(C2)
         : "vcc", "scc", "memory", "v52", "v53", "v54", "v55", "v56", "v57", "v58", "v59", "v60", "v61", "v62", "v63");
@@ -440,6 +503,7 @@ __device__ __forceinline__ bool blend_walk(const uint2 range, const uint32_t* __
         const uint32_t kbase = npairs;  // GUARD: how many entries the list of kept entries held before this chunk
         // the hand-written loops walk an address and a count: this lane's entry is the chunk's rank-th kept one
         const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(bm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bm, 0u));
+        const uint32_t pad = kAsmLoop || kAsmLoopExact ? (0u - (uint32_t)__popcll(bm)) & 3u : 0u;  // (the hand-written loops: empty slots ahead of the kept entries)
         if (GUARD) {
             // abandon: set where a break decision had to be resolved (see there); more pairs than the coarse window allows for
             npairs += (uint32_t)__popcll(bm);
@@ -453,11 +517,13 @@ __device__ __forceinline__ bool blend_walk(const uint2 range, const uint32_t* __
             __builtin_amdgcn_wave_barrier();
         }
         if constexpr (kAsmLoop || kAsmLoopExact) {
-            // the kept entries staged in rank order
+            // the kept entries staged in rank order -- for the guarded loop behind `pad` empty slots, so that the last entry is
+            // the fourth of a group of four (pad + kept <= 64: the next multiple of four)
+            const uint32_t slot = rank + pad;
             if (keep) {  // (the conic scaled by a power of two, signs as they are: the loops compute pn = -power; ncut = -cut)
-                slab[0][rank] = make_float4(h00, cur.co.y, h11, cur.co.w);
-                slab[1][rank] = cur.uv;
-                *reinterpret_cast<float2*>(&slab[2][rank]) = make_float2(cur.bc.x, -cut);  // (the loops read these two alone)
+                slab[0][slot] = make_float4(h00, cur.co.y, h11, cur.co.w);
+                slab[1][slot] = cur.uv;
+                *reinterpret_cast<float2*>(&slab[2][slot]) = make_float2(cur.bc.x, -cut);  // (the loops read these two alone)
             }
             __builtin_amdgcn_wave_barrier();
         } else {
@@ -515,7 +581,7 @@ __device__ __forceinline__ bool blend_walk(const uint2 range, const uint32_t* __
                     uint64_t updm = ev.m2 & ~mk;
                     updm = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(updm >> 32)) << 32) |
                            (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)updm);
-                    const uint32_t at = n_kept - 1u - rem;  // the pending pair's slot in the slab
+                    const uint32_t at = pad + (n_kept - 1u - rem);  // the pending pair's slot in the slab
                     const float er = slab[1][at].z, eg = slab[1][at].w, eb = slab[2][at].x;
                     uint64_t saved;
                     asm volatile("s_and_saveexec_b64 %[sv], %[um]\n\t"

@@ -4,6 +4,7 @@
 //   0  23 VALU, no LDS                                     3  23 VALU + the three reads under exec = lanes 0-15 (one lane group)
 //   1  23 VALU + the three broadcast reads (the shipped)   4  33 VALU (10 v_readfirstlane) + one-lane-group reads: the entry in SGPRs
 //   2  the three reads alone                               5  23 VALU + s_load_dwordx8 + s_load_dwordx2 of the NEXT entry (scalar cache)
+//   6-10  the shipped body and its ablations (real_pair)   11-15  the path split of round 26 (kpaths, below)
 // hipcc --offload-arch=gfx950 -O3 pair_loop_model.hip -o pair_loop_model && ./pair_loop_model
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -120,6 +121,69 @@ __global__ __launch_bounds__(256) void k(float* out, const float* entries, int i
     out[blockIdx.x * 256 + threadIdx.x] = c0 + c1 + c2 + T;
 }
 
+// ---- round 26: the path split (gs_blend.hip: GS_PAIR_GUARDED / GS_PAIR_SLOW) ---------------------------------------------------
+// The whole timed loop in one string, as the kernel has it: eight copies of the pair (two groups of four; the branch between the
+// groups is a taken one, as the kernel's back edge every four pairs), the count in an SGPR, stubs out of line.  SHAPE:
+//   0  the shipped tail: break compare, slice compare, s_andn2 exec, s_andn2 alive, s_cselect, s_mov exec, s_add + branch per pair
+//   1  step 1: ONE compare T < slice_hi and a branch; fast path = accumulate, s_mov exec, s_add + branch per pair
+//   2  step 2: as 1, the count once per four pairs
+// SLOW: the first of the eight copies compares against 2.0 instead of slice_hi, so its stub (the shipped bookkeeping, mk = 0) runs
+// on one pair in eight.  T is kept away from the thresholds by one more VALU per pair (v_fma), in every shape alike.
+#define P_BODY(OFF)                                                                                                                \
+    "ds_read_b128 v[54:57], %[a] offset:" #OFF "\n ds_read_b128 v[58:61], %[a] offset:1024+" #OFF "\n ds_read_b64 v[62:63], %[a] offset:2048+" #OFF "\n" \
+    "s_waitcnt lgkmcnt(0)\n"                                                                                                       \
+    "v_sub_f32 v58, v58, %[fx]\n v_sub_f32 v59, v59, %[fy]\n v_mul_f32 v54, v54, v58\n v_mul_f32 v56, v56, v59\n"                  \
+    "v_mul_f32 v54, v58, v54\n v_mul_f32 v56, v59, v56\n v_mul_f32 v55, v55, v58\n v_add_f32 v54, v54, v56\n"                       \
+    "v_mul_f32 v55, v55, v59\n v_add_f32 v54, v55, v54\n v_cmpx_le_u32 vcc, v54, v63\n"                                            \
+    "v_mul_f32 v56, 0xbfb8aa3b, v54\n v_exp_f32 v56, v56\n s_nop 0\n v_mul_f32 v56, v57, v56\n v_min_f32 v56, 0x3f7d70a4, v56\n"   \
+    "v_sub_f32 v55, 1.0, v56\n v_mul_f32 %[w], v56, %[T]\n v_mul_f32 %[T], %[T], v55\n"
+#define P_FMAC "v_fmac_f32 %[c0], v60, %[w]\n v_fmac_f32 %[c1], v61, %[w]\n v_fmac_f32 %[c2], v62, %[w]\n"
+#define P_KEEP_T "v_fma_f32 %[T], %[T], 0.5, 0.5\n"
+#define P_BOOK                                                                                                                     \
+    "v_cmp_gt_f32 %[mk], %[k1e4], %[T]\n v_cmp_eq_u32_sdwa vcc, %[T], %[slice] src0_sel:WORD_1 src1_sel:DWORD\n s_cbranch_vccnz .Ldone_%=\n" \
+    "s_andn2_b64 exec, exec, %[mk]\n" P_FMAC "s_andn2_b64 %[alive], %[alive], %[mk]\n"
+#define P_COUNT "s_add_u32 %[rem], %[rem], -1\n"
+#define P_SHIPPED(OFF) P_BODY(OFF) P_BOOK "s_cselect_b32 %[rem], %[rem], 0\n s_mov_b64 exec, %[alive]\n" P_KEEP_T P_COUNT
+#define P_SPLIT(J, OFF, THR, COUNT)                                                                                                \
+    P_BODY(OFF) "v_cmp_gt_f32 vcc, " THR ", %[T]\n s_cbranch_vccnz .Lslow" #J "_%=\n" P_FMAC ".Lnext" #J "_%=:\n s_mov_b64 exec, %[alive]\n" P_KEEP_T COUNT
+#define P_STUB1(J) ".Lslow" #J "_%=:\n" P_BOOK "s_cselect_b32 %[rem], %[rem], 0\n s_branch .Lnext" #J "_%=\n"
+#define P_STUB2(J) ".Lslow" #J "_%=:\n" P_BOOK "s_cbranch_scc1 .Lnext" #J "_%=\n s_branch .Ldone_%=\n"
+#define P_OUT ".Ldone_%=:\n s_mov_b64 exec, %[alive]\n s_branch .Lend_%=\n"
+#define P_BETWEEN "s_cbranch_scc0 .Ldone_%=\n"
+#define P_MID "s_cbranch_scc1 .Lmid_%=\n s_nop 0\n .Lmid_%=:\n"   /* (a taken branch: the kernel's back edge after four pairs) */
+#define P_HI "0x38d20000"
+template <int SHAPE, bool SLOW>
+__global__ __launch_bounds__(256) void kpaths(float* out, int iters) {
+    __shared__ float4 slab[4][3][64];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    for (int p = 0; p < 3; ++p) slab[w][p][lane] = p == 0 ? make_float4(0.001f, 0.0f, 0.001f, 0.3f) : p == 1 ? make_float4(3.5f, 3.5f, 0.5f, 0.5f) : make_float4(0.5f, 100.0f, 0.f, 0.f);
+    __syncthreads();
+    float c0 = 0, c1 = 0, c2 = 0, T = 1.0f, ww;
+    const float fx = (float)(lane & 7), fy = (float)(lane >> 3), k1e4 = 1e-4f;
+    const uint32_t addr = (uint32_t)(uintptr_t)&slab[w][0][0], slice = 0x38D1u;
+    const float thr0 = SLOW ? 2.0f : __uint_as_float(0x38D20000u);  // the first copy's threshold: slice_hi, or one every T is below
+    uint64_t alive = ~0ull, mk;
+    // pairs (shapes 0, 1) or groups of four (shape 2) left MINUS ONE: `iters` pairs in all, a multiple of eight
+    uint32_t rem = (uint32_t)__builtin_amdgcn_readfirstlane(SHAPE == 2 ? iters / 4 - 1 : iters - 1);
+#define P_OPERANDS                                                                                                                 \
+    : [c0] "+v"(c0), [c1] "+v"(c1), [c2] "+v"(c2), [T] "+v"(T), [w] "=&v"(ww), [alive] "+s"(alive), [rem] "+s"(rem), [mk] "=&s"(mk) \
+    : [fx] "v"(fx), [fy] "v"(fy), [a] "v"(addr), [k1e4] "s"(k1e4), [slice] "s"(slice), [thr0] "s"(thr0)                                            \
+    : "vcc", "scc", "memory", "v54", "v55", "v56", "v57", "v58", "v59", "v60", "v61", "v62", "v63"
+    if (SHAPE == 0) {
+        asm volatile(".Ltop_%=:\n" P_SHIPPED(0) P_BETWEEN P_SHIPPED(16) P_BETWEEN P_SHIPPED(32) P_BETWEEN P_SHIPPED(48) P_MID
+                     P_SHIPPED(0) P_BETWEEN P_SHIPPED(16) P_BETWEEN P_SHIPPED(32) P_BETWEEN P_SHIPPED(48) "s_cbranch_scc1 .Ltop_%=\n" P_OUT ".Lend_%=:" P_OPERANDS);
+    } else if (SHAPE == 1) {
+        asm volatile(".Ltop_%=:\n" P_SPLIT(0, 0, "%[thr0]", P_COUNT) P_BETWEEN P_SPLIT(1, 16, P_HI, P_COUNT) P_BETWEEN P_SPLIT(2, 32, P_HI, P_COUNT) P_BETWEEN P_SPLIT(3, 48, P_HI, P_COUNT) P_MID
+                     P_SPLIT(4, 0, P_HI, P_COUNT) P_BETWEEN P_SPLIT(5, 16, P_HI, P_COUNT) P_BETWEEN P_SPLIT(6, 32, P_HI, P_COUNT) P_BETWEEN P_SPLIT(7, 48, P_HI, P_COUNT) "s_cbranch_scc1 .Ltop_%=\n" P_OUT
+                     P_STUB1(0) P_STUB1(1) P_STUB1(2) P_STUB1(3) P_STUB1(4) P_STUB1(5) P_STUB1(6) P_STUB1(7) ".Lend_%=:" P_OPERANDS);
+    } else {
+        asm volatile(".Ltop_%=:\n" P_SPLIT(0, 0, "%[thr0]", "") P_SPLIT(1, 16, P_HI, "") P_SPLIT(2, 32, P_HI, "") P_SPLIT(3, 48, P_HI, P_COUNT) P_MID
+                     P_SPLIT(4, 0, P_HI, "") P_SPLIT(5, 16, P_HI, "") P_SPLIT(6, 32, P_HI, "") P_SPLIT(7, 48, P_HI, P_COUNT) "s_cbranch_scc1 .Ltop_%=\n" P_OUT
+                     P_STUB2(0) P_STUB2(1) P_STUB2(2) P_STUB2(3) P_STUB2(4) P_STUB2(5) P_STUB2(6) P_STUB2(7) ".Lend_%=:" P_OPERANDS);
+    }
+    out[blockIdx.x * 256 + threadIdx.x] = c0 + c1 + c2 + T + (float)(uint32_t)alive;
+}
+
 int main() {
     float *out, *ent;
     const int blocks = 256 * 8, iters = 4096;
@@ -132,8 +196,10 @@ int main() {
     const char* names[] = {"23 VALU, no LDS", "23 VALU + 3 broadcast reads (shipped shape)", "3 broadcast reads alone (+1 VALU)", "23 VALU + 3 reads under exec = 16 lanes",
                            "33 VALU (10 readfirstlane) + 16-lane reads, entry in SGPRs", "23 VALU + s_load x8 + x2 of the next entry",
                            "the shipped body (+1 VALU to keep T in range)", "  ... v_exp_f32 -> v_mul_f32", "  ... v_cmpx (writes exec) -> v_cmp", "  ... without the scalar tail (exec / alive / rem)",
-                           "  ... the s_nop behind v_exp replaced by a v_mov"};
-    for (int mode = 0; mode < 11; ++mode) {
+                           "  ... the s_nop behind v_exp replaced by a v_mov",
+                           "path split harness: the shipped tail", "path split, step 1 (one compare, count per pair): fast path only", "  ... its stub on one pair in eight",
+                           "path split, step 2 (count per four pairs): fast path only", "  ... its stub on one pair in eight"};
+    for (int mode = 0; mode < 16; ++mode) {
         float best = 1e9f;
         for (int rep = 0; rep < 4; ++rep) {
             hipEventRecord(e0);
@@ -149,6 +215,11 @@ int main() {
                 case 8: hipLaunchKernelGGL(k<8>, dim3(blocks), dim3(256), 0, 0, out, ent, iters); break;
                 case 9: hipLaunchKernelGGL(k<9>, dim3(blocks), dim3(256), 0, 0, out, ent, iters); break;
                 case 10: hipLaunchKernelGGL(k<10>, dim3(blocks), dim3(256), 0, 0, out, ent, iters); break;
+                case 11: hipLaunchKernelGGL((kpaths<0, false>), dim3(blocks), dim3(256), 0, 0, out, iters); break;
+                case 12: hipLaunchKernelGGL((kpaths<1, false>), dim3(blocks), dim3(256), 0, 0, out, iters); break;
+                case 13: hipLaunchKernelGGL((kpaths<1, true>), dim3(blocks), dim3(256), 0, 0, out, iters); break;
+                case 14: hipLaunchKernelGGL((kpaths<2, false>), dim3(blocks), dim3(256), 0, 0, out, iters); break;
+                case 15: hipLaunchKernelGGL((kpaths<2, true>), dim3(blocks), dim3(256), 0, 0, out, iters); break;
             }
             hipEventRecord(e1);
             hipEventSynchronize(e1);
