@@ -125,15 +125,44 @@ def _transform(rotation, translation, scale):
     return t
 
 
+PARAMETER_NAMES = ("means", "log_scales", "quats", "opacity_logits", "sh_dc", "sh_rest")  # Scene.from_tensors' keywords
+
+
+def _parameter_shapes(rows, k):
+    """The shapes of the six parameter tensors of `rows` Gaussians under PARAMETER_NAMES, sh_rest with k coefficients above the DC
+    term (None: an extent _tensor_exact does not check)."""
+    return dict(means=(rows, 3), log_scales=(rows, 3), quats=(rows, 4), opacity_logits=(rows,), sh_dc=(rows, 3), sh_rest=(rows, k, 3))
+
+
+def _torch_device(dev):
+    """The torch device of a scene on GPU `dev`: where the wrappers allocate what they are asked to."""
+    return f"cuda:{int(dev)}"
+
+
+def _tensor_shape(name, t, dtypes):
+    """The first checks of a device tensor `t`: it has a tensor's attributes and one of `dtypes`.  Returns its shape."""
+    if not all(hasattr(t, a) for a in ("data_ptr", "shape", "dtype", "is_contiguous", "device")):
+        raise TypeError(f"{name}: a device tensor is needed (data_ptr, shape, dtype, is_contiguous, device), got {type(t).__name__}")
+    if str(t.dtype).rsplit(".", 1)[-1] not in dtypes:
+        raise TypeError(f"{name}: dtype must be {' or '.join(dtypes)}, not {t.dtype}")
+    return tuple(int(d) for d in t.shape)
+
+
+def _tensor_on_device(name, t, device, instead, holder):
+    """The last checks of a device tensor `t`: it is on GPU `device`, where `holder` is; `instead` says what a CPU tensor misses."""
+    dev = t.device
+    kind, index = getattr(dev, "type", str(dev).split(":")[0]), getattr(dev, "index", None)
+    if kind == "cpu":
+        raise ValueError(f"{name}: the tensor is on the CPU; {instead}")
+    if (0 if index is None else int(index)) != int(device):
+        raise ValueError(f"{name}: the tensor is on device {index}, the {holder} on device {device}")
+
+
 def _tensor_rows(name, t, trailing, device):
     """Rows of device tensor `t` after checking it is what gs_device_arrays takes: float32, contiguous, on GPU `device`, of
     shape (rows, *trailing) up to singleton axes (the Inria trainer keeps _features_dc as (N, 1, 3), _opacity as (N, 1)).
     `trailing` None: (rows, k, 3) with k in {0, 3, 8, 15}; returns (rows, k) then."""
-    if not all(hasattr(t, a) for a in ("data_ptr", "shape", "dtype", "is_contiguous", "device")):
-        raise TypeError(f"{name}: a device tensor is needed (data_ptr, shape, dtype, is_contiguous, device), got {type(t).__name__}")
-    if str(t.dtype).rsplit(".", 1)[-1] != "float32":
-        raise TypeError(f"{name}: dtype must be float32, not {t.dtype}")
-    shape = tuple(int(d) for d in t.shape)
+    shape = _tensor_shape(name, t, ("float32",))
     if len(shape) < 1:
         raise ValueError(f"{name}: shape {shape} has no row axis")
     if not t.is_contiguous():
@@ -145,25 +174,32 @@ def _tensor_rows(name, t, trailing, device):
         rows = (rows, rest[0])
     elif rest != tuple(d for d in trailing if d != 1):
         raise ValueError(f"{name}: shape {shape} is not (rows, {', '.join(map(str, trailing))})")
-    dev = t.device
-    kind, index = getattr(dev, "type", str(dev).split(":")[0]), getattr(dev, "index", None)
-    if kind == "cpu":
-        raise ValueError(f"{name}: the tensor is on the CPU; Scene.from_records takes host data")
-    if (0 if index is None else int(index)) != int(device):
-        raise ValueError(f"{name}: the tensor is on device {index}, the scene on device {device}")
+    _tensor_on_device(name, t, device, "Scene.from_records takes host data", "scene")
     return rows
+
+
+def _tensor_exact(name, t, dtypes, shape, device, owner="Renderer.contributions"):
+    """data_ptr of device tensor `t` after checking it is what gs_contributions / gs_feature_maps take: one of `dtypes`,
+    contiguous, on GPU `device`, of exactly `shape` (a None extent is not checked)."""
+    got = _tensor_shape(name, t, dtypes)
+    if len(got) != len(shape) or any(w is not None and g != w for g, w in zip(got, shape)):
+        raise ValueError(f"{name}: shape {got} is not ({', '.join('?' if w is None else str(w) for w in shape)})")
+    if not t.is_contiguous():
+        raise ValueError(f"{name}: the tensor must be contiguous; call .contiguous()")
+    _tensor_on_device(name, t, device, f"the arrays of {owner} live on the renderer's device", "renderer")
+    return t.data_ptr() if all(got) else None
 
 
 def _device_arrays(tensors, device, require):
     """(DeviceArrays, rows) from {member: tensor or None}; every check of the tensors happens here, before C is called."""
-    trailing = dict(means=(3,), log_scales=(3,), quats=(4,), opacity_logits=(1,), sh_dc=(3,), sh_rest=None)
+    shapes = _parameter_shapes(None, None)
     a, rows = DeviceArrays(), None
     for name, t in tensors.items():
         if t is None:
             if require and name != "sh_rest":
                 raise TypeError(f"{name} is required")
             continue
-        r = _tensor_rows(name, t, trailing[name], device)
+        r = _tensor_rows(name, t, None if name == "sh_rest" else shapes[name][1:] or (1,), device)
         if name == "sh_rest":
             r, a.sh_rest_coeffs = r
             if a.sh_rest_coeffs == 0:
@@ -241,15 +277,10 @@ class AdamStep(C.Structure):
                 ("bias_correction1", C.c_double), ("bias_correction2", C.c_double), ("zero_grads", C.c_int)]
 
 
-PARAMETER_NAMES = ("means", "log_scales", "quats", "opacity_logits", "sh_dc", "sh_rest")  # Scene.from_tensors' keywords
-
 PHOTO_LOSS_MAX_EXTENT = 16384   # GS_PHOTO_LOSS_MAX_EXTENT: width and height of gs_photometric_loss
 CAMERA_BACKWARD_LANES = 131072  # GS_CAMERA_BACKWARD_LANES: a scene with more Gaussians is strided over by gs_camera_backward's lanes
 
-_FEATURE_MAPS_FN = None  # the torch.autograd.Function of Renderer.differentiable_feature_maps, defined when first asked for
-_RENDER_FN = None        # ... and of Renderer.differentiable_render
-_RENDER_POSED_FN = None  # ... and of Renderer.differentiable_render_posed
-_PHOTO_LOSS_FN = None    # ... and of Renderer.differentiable_photometric_loss
+_AUTOGRAD = None  # the torch.autograd.Functions of Renderer.differentiable_*, defined when first asked for (_autograd)
 
 
 def _complete_callers_work(*tensors):
@@ -268,183 +299,181 @@ def _complete_callers_work(*tensors):
             return
 
 
-def _feature_maps_function():
-    """The autograd function behind Renderer.differentiable_feature_maps; torch is imported here, not with the module."""
-    global _FEATURE_MAPS_FN
-    if _FEATURE_MAPS_FN is None:
-        import torch
-
-        class FeatureMapsFunction(torch.autograd.Function):
-            """out = feature_maps(features) of the renderer's last frame; d/dfeatures only -- the frame is a constant."""
-
-            @staticmethod
-            def forward(ctx, renderer, features):
-                ctx.renderer, ctx.frame = renderer, renderer._frames
-                _complete_callers_work(features)  # (an optimizer step on the features may still be queued on torch's stream)
-                return renderer.feature_maps(features=features.detach().contiguous(), out=True)["out"]
-
-            @staticmethod
-            def backward(ctx, grad):
-                rend = ctx.renderer
-                if rend._frames != ctx.frame:
-                    raise RuntimeError(f"differentiable_feature_maps: the forward blended frame {ctx.frame} of this renderer, which has "
-                                       f"rendered frame {rend._frames} since; the gradient of another frame is not returned")
-                lifted = rend.lift_pixels(grad.contiguous().float(), out=True)["out"]
-                return None, lifted.to(torch.float32)
-
-        _FEATURE_MAPS_FN = FeatureMapsFunction
-    return _FEATURE_MAPS_FN
+def _record_shapes(n):
+    """The shapes of the four float64 gradients per Gaussian with respect to a frame's records: what blend_backward sums and
+    project_backward and camera_backward take."""
+    return dict(colour=(n, 3), opacity=(n,), conic=(n, 3), uv=(n, 2))
 
 
-def _render_function():
-    """The autograd function behind Renderer.differentiable_render; torch is imported here, not with the module."""
-    global _RENDER_FN
-    if _RENDER_FN is None:
-        import torch
-
-        class RenderFunction(torch.autograd.Function):
-            """rgb (and alpha) of one frame of the renderer's scene, refreshed from the six parameter tensors; the backward is
-            blend_backward then project_backward, at the frame's values, rounded to float32."""
-
-            @staticmethod
-            def forward(ctx, renderer, uniforms, want_alpha, means, log_scales, quats, opacity_logits, sh_dc, sh_rest):
-                params = dict(means=means, log_scales=log_scales, quats=quats, opacity_logits=opacity_logits, sh_dc=sh_dc, sh_rest=sh_rest)
-                renderer.synchronize()  # (no frame of this renderer may straddle the update)
-                renderer.scene.update_from_tensors(0, **{k: (None if v is None else v.detach().contiguous()) for k, v in params.items()})
-                h, w = int(uniforms["height"][0]), int(uniforms["width"][0])
-                rgba = torch.empty((h, w, 4), dtype=torch.float32, device=f"cuda:{int(renderer.scene.device)}")
-                renderer.render(uniforms, rgba.data_ptr())
-                renderer.synchronize()
-                ctx.renderer, ctx.frame, ctx.want_alpha = renderer, renderer._frames, bool(want_alpha)
-                ctx.shapes = {k: (None if v is None else tuple(v.shape)) for k, v in params.items()}
-                rgb = rgba[..., :3].contiguous()
-                if not want_alpha:
-                    return rgb
-                return rgb, renderer.feature_maps(alpha=True)["alpha"]
-
-            @staticmethod
-            def backward(ctx, grad_rgb, grad_alpha=None):
-                rend = ctx.renderer
-                if rend._frames != ctx.frame:
-                    raise RuntimeError(f"differentiable_render: the forward rendered frame {ctx.frame} of this renderer, which has "
-                                       f"rendered frame {rend._frames} since; the gradient of another frame is not returned")
-                if grad_rgb is None:
-                    grad_rgb = torch.zeros(rend._frame_hw + (3,), dtype=torch.float32, device=f"cuda:{int(rend.scene.device)}")
-                d = rend.blend_backward(grad_rgb.contiguous().float(), None if grad_alpha is None else grad_alpha.contiguous().float(),
-                                        colour=True, opacity=True, conic=True, uv=True)
-                rest = ctx.shapes["sh_rest"]
-                k = 0 if rest is None else int(rest[-2])
-                n = int(rend.scene.num_vertices)
-                names = ("means", "log_scales", "quats", "opacity_logits", "sh_dc") + (("sh_rest",) if k else ())
-                shapes = dict(means=(n, 3), log_scales=(n, 3), quats=(n, 4), opacity_logits=(n,), sh_dc=(n, 3), sh_rest=(n, k, 3))
-                out = {name: torch.zeros(shapes[name], dtype=torch.float64, device=grad_rgb.device) for name in names}
-                rend.project_backward(out=out, **d)
-                grads = [None if ctx.shapes[name] is None or name not in out else out[name].to(torch.float32).reshape(ctx.shapes[name])
-                         for name in ("means", "log_scales", "quats", "opacity_logits", "sh_dc", "sh_rest")]
-                if ctx.shapes["sh_rest"] is not None and not k:
-                    grads[5] = torch.zeros(ctx.shapes["sh_rest"], dtype=torch.float32, device=grad_rgb.device)
-                return (None, None, None, *grads)
-
-        _RENDER_FN = RenderFunction
-    return _RENDER_FN
+def _record_gradients(struct, owner, n, device, **given):
+    """Set the d_colour / d_opacity / d_conic / d_uv inputs of `struct` from the tensors `given` under those names; None = zeros."""
+    for name, shape in _record_shapes(n).items():
+        if given[name] is not None:
+            setattr(struct, "d_" + name, _tensor_exact(name, given[name], ("float64",), shape, device, owner))
 
 
-def _render_posed_function():
-    """The autograd function behind Renderer.differentiable_render_posed; torch is imported here, not with the module."""
-    global _RENDER_POSED_FN
-    if _RENDER_POSED_FN is None:
-        import torch
-
-        class RenderPosedFunction(torch.autograd.Function):
-            """rgb (and alpha) of one frame seen from the pose (position, rotation); the backward is blend_backward, then
-            camera_backward and camera_pose_gradient for the pose, and project_backward only for scene tensors that ask."""
-
-            @staticmethod
-            def forward(ctx, renderer, width, height, fov, near, far, want_alpha, position, rotation, means, log_scales, quats,
-                        opacity_logits, sh_dc, sh_rest):
-                params = dict(means=means, log_scales=log_scales, quats=quats, opacity_logits=opacity_logits, sh_dc=sh_dc, sh_rest=sh_rest)
-                pose = [np.ascontiguousarray(t.detach().to("cpu", torch.float32).numpy().reshape(-1)) for t in (position, rotation)]
-                if pose[0].shape != (3,) or pose[1].shape != (4,):
-                    raise ValueError(f"position must hold 3 values and rotation 4 (w x y z), not {pose[0].shape[0]} and {pose[1].shape[0]}")
-                cam = make_camera(position=pose[0], rotation=pose[1], fov=fov, near=near, far=far)
-                uniforms = camera_uniforms(cam, int(width), int(height))
-                renderer.synchronize()  # (no frame of this renderer may straddle the update)
-                if any(v is not None for v in params.values()):
-                    renderer.scene.update_from_tensors(0, **{k: (None if v is None else v.detach().contiguous()) for k, v in params.items()})
-                rgba = torch.empty((int(height), int(width), 4), dtype=torch.float32, device=f"cuda:{int(renderer.scene.device)}")
-                renderer.render(uniforms, rgba.data_ptr())
-                renderer.synchronize()
-                ctx.renderer, ctx.frame, ctx.cam, ctx.size = renderer, renderer._frames, cam, (int(width), int(height))
-                ctx.pose = [(t.dtype, t.device, tuple(t.shape)) for t in (position, rotation)]
-                ctx.shapes = {k: (None if v is None else tuple(v.shape)) for k, v in params.items()}
-                rgb = rgba[..., :3].contiguous()
-                if not want_alpha:
-                    return rgb
-                return rgb, renderer.feature_maps(alpha=True)["alpha"]
-
-            @staticmethod
-            def backward(ctx, grad_rgb, grad_alpha=None):
-                rend = ctx.renderer
-                if rend._frames != ctx.frame:
-                    raise RuntimeError(f"differentiable_render_posed: the forward rendered frame {ctx.frame} of this renderer, which has "
-                                       f"rendered frame {rend._frames} since; the gradient of another frame is not returned")
-                dev = f"cuda:{int(rend.scene.device)}"
-                if grad_rgb is None:
-                    grad_rgb = torch.zeros(rend._frame_hw + (3,), dtype=torch.float32, device=dev)
-                d = rend.blend_backward(grad_rgb.contiguous().float(), None if grad_alpha is None else grad_alpha.contiguous().float(),
-                                        colour=True, opacity=True, conic=True, uv=True)
-                pose = [None, None]
-                if ctx.needs_input_grad[7] or ctx.needs_input_grad[8]:
-                    found = camera_pose_gradient(ctx.cam, ctx.size[0], ctx.size[1], rend.camera_backward(**d))
-                    pose = [torch.as_tensor(g).to(device=device, dtype=dtype).reshape(shape) if need else None
-                            for g, (dtype, device, shape), need in zip(found, ctx.pose, ctx.needs_input_grad[7:9])]
-                names = ("means", "log_scales", "quats", "opacity_logits", "sh_dc", "sh_rest")
-                grads = [None] * 6
-                if any(ctx.needs_input_grad[9:]):
-                    rest = ctx.shapes["sh_rest"]
-                    k = 0 if rest is None else int(rest[-2])
-                    n = int(rend.scene.num_vertices)
-                    shapes = dict(means=(n, 3), log_scales=(n, 3), quats=(n, 4), opacity_logits=(n,), sh_dc=(n, 3), sh_rest=(n, k, 3))
-                    out = {name: torch.zeros(shapes[name], dtype=torch.float64, device=dev)
-                           for name, need in zip(names, ctx.needs_input_grad[9:]) if need and (name != "sh_rest" or k)}
-                    rend.project_backward(out=out, **d)
-                    grads = [out[name].to(torch.float32).reshape(ctx.shapes[name]) if name in out else None for name in names]
-                    if ctx.needs_input_grad[14] and not k:
-                        grads[5] = torch.zeros(ctx.shapes["sh_rest"], dtype=torch.float32, device=dev)
-                return (None, None, None, None, None, None, None, *pose, *grads)
-
-        _RENDER_POSED_FN = RenderPosedFunction
-    return _RENDER_POSED_FN
+def _output(value, member, dtype, shape, zeros=False, key=None):
+    """One output of a pass, for _outputs: `value` is a tensor to fill, True to have one allocated, or None to skip; `member` of the
+    C struct takes its pointer; it has `dtype` and exactly `shape`, and holds zeros, or nothing yet, when it is allocated here; the
+    result holds it under `key` (None: under the name it is checked by)."""
+    return value, member, dtype, shape, zeros, key
 
 
-def _photo_loss_function():
-    """The autograd function behind Renderer.differentiable_photometric_loss; torch is imported here, not with the module."""
-    global _PHOTO_LOSS_FN
-    if _PHOTO_LOSS_FN is None:
-        import torch
+def _outputs(struct, owner, device, outputs):
+    """The passes' output protocol over {name: _output(...)}: an output that is None is skipped, one that is True is allocated on
+    the scene's device, each is checked as `owner`'s tensor `name` (_tensor_exact) and its pointer set in `struct`.  Returns
+    {key: tensor} of the outputs that were asked for."""
+    result = {}
+    for name, (t, member, dtype, shape, zeros, key) in outputs.items():
+        if t is None:
+            continue
+        if t is True:
+            import torch
+            t = (torch.zeros if zeros else torch.empty)(shape, dtype=getattr(torch, dtype), device=_torch_device(device))
+        setattr(struct, member, _tensor_exact(name, t, (dtype,), shape, device, owner))
+        result[name if key is None else key] = t
+    return result
 
-        class PhotoLossFunction(torch.autograd.Function):
-            """loss(image, target) as a 0-dim float64 tensor; the forward's one call also finds d loss / d image, which the
-            backward scales.  The target carries no gradient.  Nothing of the renderer's last frame is involved."""
 
-            @staticmethod
-            def forward(ctx, renderer, lambda_dssim, image, target):
-                got = renderer.photometric_loss(image.detach().contiguous(), target.detach().contiguous(), lambda_dssim, grad=True, terms=True)
-                ctx.save_for_backward(got["grad_rgb"])
-                ctx.image = (tuple(image.shape), image.dtype)
-                return got["loss"].clone()
+def _autograd():
+    """The torch.autograd.Functions behind Renderer.differentiable_feature_maps, _render, _render_posed and _photometric_loss, as
+    the attributes feature_maps, render, render_posed and photometric_loss; torch is imported here, not with the module."""
+    global _AUTOGRAD
+    if _AUTOGRAD is not None:
+        return _AUTOGRAD
+    import types
 
-            @staticmethod
-            def backward(ctx, grad_output):
-                (saved,) = ctx.saved_tensors
-                shape, dtype = ctx.image
-                g = grad_output.float() * saved
-                if shape[-1] == 4:   # (an RGBA image: the fourth float is not read, its gradient is zero)
-                    g = torch.cat([g, torch.zeros(shape[:2] + (1,), dtype=g.dtype, device=g.device)], dim=2)
-                return None, None, g.to(dtype), None
+    import torch
 
-        _PHOTO_LOSS_FN = PhotoLossFunction
-    return _PHOTO_LOSS_FN
+    def render_frame(ctx, renderer, uniforms, want_alpha, params, refresh):
+        """The forward of both render functions from the uniforms on: the scene refreshed from `params` if `refresh`, the frame
+        rendered into a fresh tensor and synchronised, what the backward needs kept in ctx; rgb, and alpha if wanted."""
+        renderer.synchronize()  # (no frame of this renderer may straddle the update)
+        if refresh:
+            renderer.scene.update_from_tensors(0, **{k: (None if v is None else v.detach().contiguous()) for k, v in params.items()})
+        h, w = int(uniforms["height"][0]), int(uniforms["width"][0])
+        rgba = torch.empty((h, w, 4), dtype=torch.float32, device=_torch_device(renderer.scene.device))
+        renderer.render(uniforms, rgba.data_ptr())
+        renderer.synchronize()
+        ctx.renderer, ctx.frame = renderer, renderer._frames
+        ctx.shapes = {k: (None if v is None else tuple(v.shape)) for k, v in params.items()}
+        rgb = rgba[..., :3].contiguous()
+        if not want_alpha:
+            return rgb
+        return rgb, renderer.feature_maps(alpha=True)["alpha"]
+
+    def record_gradients(ctx, method, grad_rgb, grad_alpha):
+        """The backward of both render functions as far as the records: blend_backward of the frame the forward rendered."""
+        rend = ctx.renderer
+        if rend._frames != ctx.frame:
+            raise RuntimeError(f"{method}: the forward rendered frame {ctx.frame} of this renderer, which has "
+                               f"rendered frame {rend._frames} since; the gradient of another frame is not returned")
+        if grad_rgb is None:
+            grad_rgb = torch.zeros(rend._frame_hw + (3,), dtype=torch.float32, device=_torch_device(rend.scene.device))
+        return rend.blend_backward(grad_rgb.contiguous().float(), None if grad_alpha is None else grad_alpha.contiguous().float(),
+                                   colour=True, opacity=True, conic=True, uv=True)
+
+    def parameter_gradients(ctx, d, want):
+        """project_backward of the record gradients `d` into float64 zeros for the names that `want` marks (PARAMETER_NAMES' order),
+        rounded to float32 in the shapes the forward was given; None for a name not wanted or not given.  sh_rest of k = 0 has no
+        array in C: its gradient is float32 zeros."""
+        rend, dev = ctx.renderer, _torch_device(ctx.renderer.scene.device)
+        rest = ctx.shapes["sh_rest"]
+        k = 0 if rest is None else int(rest[-2])
+        shapes = _parameter_shapes(int(rend.scene.num_vertices), k)
+        out = {name: torch.zeros(shapes[name], dtype=torch.float64, device=dev)
+               for name, need in zip(PARAMETER_NAMES, want) if need and (name != "sh_rest" or k)}
+        rend.project_backward(out=out, **d)
+        grads = [out[name].to(torch.float32).reshape(ctx.shapes[name]) if name in out and ctx.shapes[name] is not None else None
+                 for name in PARAMETER_NAMES]
+        if want[5] and rest is not None and not k:
+            grads[5] = torch.zeros(rest, dtype=torch.float32, device=dev)
+        return grads
+
+    class FeatureMapsFunction(torch.autograd.Function):
+        """out = feature_maps(features) of the renderer's last frame; d/dfeatures only -- the frame is a constant."""
+
+        @staticmethod
+        def forward(ctx, renderer, features):
+            ctx.renderer, ctx.frame = renderer, renderer._frames
+            _complete_callers_work(features)  # (an optimizer step on the features may still be queued on torch's stream)
+            return renderer.feature_maps(features=features.detach().contiguous(), out=True)["out"]
+
+        @staticmethod
+        def backward(ctx, grad):
+            rend = ctx.renderer
+            if rend._frames != ctx.frame:
+                raise RuntimeError(f"differentiable_feature_maps: the forward blended frame {ctx.frame} of this renderer, which has "
+                                   f"rendered frame {rend._frames} since; the gradient of another frame is not returned")
+            lifted = rend.lift_pixels(grad.contiguous().float(), out=True)["out"]
+            return None, lifted.to(torch.float32)
+
+    class RenderFunction(torch.autograd.Function):
+        """rgb (and alpha) of one frame of the renderer's scene, refreshed from the six parameter tensors; the backward is
+        blend_backward then project_backward, at the frame's values, rounded to float32."""
+
+        @staticmethod
+        def forward(ctx, renderer, uniforms, want_alpha, means, log_scales, quats, opacity_logits, sh_dc, sh_rest):
+            params = dict(zip(PARAMETER_NAMES, (means, log_scales, quats, opacity_logits, sh_dc, sh_rest)))
+            return render_frame(ctx, renderer, uniforms, want_alpha, params, refresh=True)
+
+        @staticmethod
+        def backward(ctx, grad_rgb, grad_alpha=None):
+            d = record_gradients(ctx, "differentiable_render", grad_rgb, grad_alpha)
+            return (None, None, None, *parameter_gradients(ctx, d, want=(True,) * 6))
+
+    class RenderPosedFunction(torch.autograd.Function):
+        """rgb (and alpha) of one frame seen from the pose (position, rotation); the backward is blend_backward, then
+        camera_backward and camera_pose_gradient for the pose, and project_backward only for scene tensors that ask."""
+
+        @staticmethod
+        def forward(ctx, renderer, width, height, fov, near, far, want_alpha, position, rotation, means, log_scales, quats,
+                    opacity_logits, sh_dc, sh_rest):
+            params = dict(zip(PARAMETER_NAMES, (means, log_scales, quats, opacity_logits, sh_dc, sh_rest)))
+            pose = [np.ascontiguousarray(t.detach().to("cpu", torch.float32).numpy().reshape(-1)) for t in (position, rotation)]
+            if pose[0].shape != (3,) or pose[1].shape != (4,):
+                raise ValueError(f"position must hold 3 values and rotation 4 (w x y z), not {pose[0].shape[0]} and {pose[1].shape[0]}")
+            cam = make_camera(position=pose[0], rotation=pose[1], fov=fov, near=near, far=far)
+            ctx.cam, ctx.size = cam, (int(width), int(height))
+            ctx.pose = [(t.dtype, t.device, tuple(t.shape)) for t in (position, rotation)]
+            return render_frame(ctx, renderer, camera_uniforms(cam, int(width), int(height)), want_alpha, params,
+                                refresh=any(v is not None for v in params.values()))
+
+        @staticmethod
+        def backward(ctx, grad_rgb, grad_alpha=None):
+            d = record_gradients(ctx, "differentiable_render_posed", grad_rgb, grad_alpha)
+            pose, grads = [None, None], [None] * 6
+            if ctx.needs_input_grad[7] or ctx.needs_input_grad[8]:
+                found = camera_pose_gradient(ctx.cam, ctx.size[0], ctx.size[1], ctx.renderer.camera_backward(**d))
+                pose = [torch.as_tensor(g).to(device=device, dtype=dtype).reshape(shape) if need else None
+                        for g, (dtype, device, shape), need in zip(found, ctx.pose, ctx.needs_input_grad[7:9])]
+            if any(ctx.needs_input_grad[9:]):
+                grads = parameter_gradients(ctx, d, want=ctx.needs_input_grad[9:])
+            return (None, None, None, None, None, None, None, *pose, *grads)
+
+    class PhotoLossFunction(torch.autograd.Function):
+        """loss(image, target) as a 0-dim float64 tensor; the forward's one call also finds d loss / d image, which the
+        backward scales.  The target carries no gradient.  Nothing of the renderer's last frame is involved."""
+
+        @staticmethod
+        def forward(ctx, renderer, lambda_dssim, image, target):
+            got = renderer.photometric_loss(image.detach().contiguous(), target.detach().contiguous(), lambda_dssim, grad=True, terms=True)
+            ctx.save_for_backward(got["grad_rgb"])
+            ctx.image = (tuple(image.shape), image.dtype)
+            return got["loss"].clone()
+
+        @staticmethod
+        def backward(ctx, grad_output):
+            (saved,) = ctx.saved_tensors
+            shape, dtype = ctx.image
+            g = grad_output.float() * saved
+            if shape[-1] == 4:   # (an RGBA image: the fourth float is not read, its gradient is zero)
+                g = torch.cat([g, torch.zeros(shape[:2] + (1,), dtype=g.dtype, device=g.device)], dim=2)
+            return None, None, g.to(dtype), None
+
+    _AUTOGRAD = types.SimpleNamespace(feature_maps=FeatureMapsFunction, render=RenderFunction, render_posed=RenderPosedFunction,
+                                      photometric_loss=PhotoLossFunction)
+    return _AUTOGRAD
 
 
 def camera_pose_gradient(cam, width, height, d):
@@ -469,27 +498,6 @@ def camera_pose_gradient(cam, width, height, d):
     _check(lib().gs_camera_uniforms_backward(_p(cam), C.c_uint32(int(width)), C.c_uint32(int(height)), _p(gv), _p(gp), _p(gc),
                                              _p(d_position), _p(d_rotation)))
     return d_position, d_rotation
-
-
-def _tensor_exact(name, t, dtypes, shape, device, owner="Renderer.contributions"):
-    """data_ptr of device tensor `t` after checking it is what gs_contributions / gs_feature_maps take: one of `dtypes`,
-    contiguous, on GPU `device`, of exactly `shape` (a None extent is not checked)."""
-    if not all(hasattr(t, a) for a in ("data_ptr", "shape", "dtype", "is_contiguous", "device")):
-        raise TypeError(f"{name}: a device tensor is needed (data_ptr, shape, dtype, is_contiguous, device), got {type(t).__name__}")
-    if str(t.dtype).rsplit(".", 1)[-1] not in dtypes:
-        raise TypeError(f"{name}: dtype must be {' or '.join(dtypes)}, not {t.dtype}")
-    got = tuple(int(d) for d in t.shape)
-    if len(got) != len(shape) or any(w is not None and g != w for g, w in zip(got, shape)):
-        raise ValueError(f"{name}: shape {got} is not ({', '.join('?' if w is None else str(w) for w in shape)})")
-    if not t.is_contiguous():
-        raise ValueError(f"{name}: the tensor must be contiguous; call .contiguous()")
-    dev = t.device
-    kind, index = getattr(dev, "type", str(dev).split(":")[0]), getattr(dev, "index", None)
-    if kind == "cpu":
-        raise ValueError(f"{name}: the tensor is on the CPU; the arrays of {owner} live on the renderer's device")
-    if (0 if index is None else int(index)) != int(device):
-        raise ValueError(f"{name}: the tensor is on device {index}, the renderer on device {device}")
-    return t.data_ptr() if all(got) else None
 
 
 def _stream_handle(stream):
@@ -706,7 +714,7 @@ class Scene:
         if int(step) != step or step < 1:
             raise ValueError(f"step must be an integer >= 1, not {step!r}")
         a = AdamStep()
-        shapes = dict(means=(n, 3), log_scales=(n, 3), quats=(n, 4), opacity_logits=(n,), sh_dc=(n, 3), sh_rest=(n, None, 3))
+        shapes = _parameter_shapes(n, None)
         members = dict(params=("param", "float32"), grads=("grad", "float64"), exp_avg=("exp_avg", "float32"), exp_avg_sq=("exp_avg_sq", "float32"))
         used = []
         for name in PARAMETER_NAMES:
@@ -763,15 +771,13 @@ class Scene:
             if sh_degree not in SH_REST_COEFFS:
                 raise ValueError(f"sh_degree must be 0, 1, 2 or 3, not {sh_degree!r}")
             import torch
-            shapes = dict(means=(count, 3), log_scales=(count, 3), quats=(count, 4), opacity_logits=(count,), sh_dc=(count, 3),
-                          sh_rest=(count, SH_REST_COEFFS[sh_degree], 3))
-            out = {k: torch.empty(shape, dtype=torch.float32, device=f"cuda:{self.device}") for k, shape in shapes.items()}
-        names = ("means", "log_scales", "quats", "opacity_logits", "sh_dc", "sh_rest")
-        unknown = sorted(set(out) - set(names))
+            out = {k: torch.empty(shape, dtype=torch.float32, device=_torch_device(self.device))
+                   for k, shape in _parameter_shapes(count, SH_REST_COEFFS[sh_degree]).items()}
+        unknown = sorted(set(out) - set(PARAMETER_NAMES))
         if unknown:
             raise TypeError(f"out: unknown member(s) {unknown}")
-        a, rows = _device_arrays({k: out.get(k) for k in names}, self.device, require=False)
-        given = [k for k in names if out.get(k) is not None and not (k == "sh_rest" and a.sh_rest_coeffs == 0)]
+        a, rows = _device_arrays({k: out.get(k) for k in PARAMETER_NAMES}, self.device, require=False)
+        given = [k for k in PARAMETER_NAMES if out.get(k) is not None and not (k == "sh_rest" and a.sh_rest_coeffs == 0)]
         if given and rows != count:
             raise ValueError(f"out: the tensors have {rows} rows, the range {count}")
         _check(lib().gs_scene_to_device_arrays(self._h, C.byref(a), C.c_uint64(first), C.c_uint64(count), _stream_handle(stream)))
@@ -852,6 +858,16 @@ class Renderer:
         self._frame_hw = (int(uniforms["height"][0]), int(uniforms["width"][0]))
         self._frames += 1
 
+    def _frame_extent(self, entry, struct, asked=()):
+        """(height, width) of the last frame for the checks of a pass over it; before any frame (None, None), extents that are not
+        checked -- C refuses the call.  If one of `asked` is True then, there is no frame to size the allocation by: the refusal
+        is obtained at once, from the pass's C entry point `entry` with an empty `struct`."""
+        if self._frame_hw is not None:
+            return self._frame_hw
+        if any(v is True for v in asked):
+            _check(getattr(lib(), entry)(self._h, C.byref(struct())))
+        return None, None
+
     def contributions(self, weight=None, pixels=None, top_id=None, mask=None):
         """What every Gaussian contributed to the last frame (gs_accumulate_contributions), into torch tensors on the renderer's
         device, contiguous: weight int64 (N,) and pixels int32 (N,) are ADDED to -- the sum over the counted pixels that blend a
@@ -860,7 +876,7 @@ class Renderer:
         (H, W): only pixels where it is not 0 are counted.  N = the scene's Gaussians, (H, W) = the last frame.  The arithmetic
         is the reference's (exp mode 2) whatever mode the frame was blended in.  Returns synchronised."""
         n = int(self.scene.num_vertices)
-        h, w = self._frame_hw if self._frame_hw is not None else (None, None)
+        h, w = self._frame_extent("gs_accumulate_contributions", Contributions)
         dev = self.scene.device
         c = Contributions()
         if weight is not None:
@@ -884,10 +900,7 @@ class Renderer:
         owner = "Renderer.feature_maps"
         n = int(self.scene.num_vertices)
         dev = self.scene.device
-        asked = dict(out=out, alpha=alpha, depth=depth, median_depth=median_depth)
-        if self._frame_hw is None and any(v is True for v in asked.values()):
-            _check(lib().gs_blend_features(self._h, C.byref(FeatureMaps())))  # (refuses: there is no frame to size an output by)
-        h, w = self._frame_hw if self._frame_hw is not None else (None, None)
+        h, w = self._frame_extent("gs_blend_features", FeatureMaps, (out, alpha, depth, median_depth))
         m = FeatureMaps()
         channels = 0
         if features is not None:
@@ -900,17 +913,10 @@ class Renderer:
         elif out is not None:
             raise ValueError("out: an output for blended features needs features")
         m.channels = channels
-        shapes = dict(out=(h, w, channels), alpha=(h, w), depth=(h, w), median_depth=(h, w))
-        members = dict(out="out_features", alpha="out_alpha", depth="out_depth", median_depth="out_depth_median")
-        result = {}
-        for name, t in asked.items():
-            if t is None:
-                continue
-            if t is True:
-                import torch
-                t = torch.empty(shapes[name], dtype=torch.float32, device=f"cuda:{int(dev)}")
-            setattr(m, members[name], _tensor_exact(name, t, ("float32",), shapes[name], dev, owner))
-            result[name] = t
+        result = _outputs(m, owner, dev, dict(out=_output(out, "out_features", "float32", (h, w, channels)),
+                                              alpha=_output(alpha, "out_alpha", "float32", (h, w)),
+                                              depth=_output(depth, "out_depth", "float32", (h, w)),
+                                              median_depth=_output(median_depth, "out_depth_median", "float32", (h, w))))
         _check(lib().gs_blend_features(self._h, C.byref(m)))
         return result
 
@@ -929,10 +935,7 @@ class Renderer:
         owner = "Renderer.lift_pixels"
         n = int(self.scene.num_vertices)
         dev = self.scene.device
-        asked = dict(out=out, weight=weight)
-        if self._frame_hw is None and any(v is True for v in asked.values()):
-            _check(lib().gs_lift_pixels(self._h, C.byref(PixelLift())))  # (refuses: there is no frame to size an input by)
-        h, w = self._frame_hw if self._frame_hw is not None else (None, None)
+        h, w = self._frame_extent("gs_lift_pixels", PixelLift, (out, weight))
         l = PixelLift()
         channels = 0
         if values is not None:
@@ -947,17 +950,8 @@ class Renderer:
         l.channels = channels
         if mask is not None:
             l.mask = _tensor_exact("mask", mask, ("uint8", "bool"), (h, w), dev, owner)
-        shapes = dict(out=(n, channels), weight=(n,))
-        members = dict(out="out", weight="out_weight")
-        result = {}
-        for name, t in asked.items():
-            if t is None:
-                continue
-            if t is True:
-                import torch
-                t = torch.zeros(shapes[name], dtype=torch.float64, device=f"cuda:{int(dev)}")
-            setattr(l, members[name], _tensor_exact(name, t, ("float64",), shapes[name], dev, owner))
-            result[name] = t
+        result = _outputs(l, owner, dev, dict(out=_output(out, "out", "float64", (n, channels), zeros=True),
+                                              weight=_output(weight, "out_weight", "float64", (n,), zeros=True)))
         _complete_callers_work(values, mask, *result.values())  # (the zeros allocated above among them: their fill is queued too)
         _check(lib().gs_lift_pixels(self._h, C.byref(l)))
         return result
@@ -976,9 +970,7 @@ class Renderer:
         n = int(self.scene.num_vertices)
         dev = self.scene.device
         asked = dict(colour=colour, opacity=opacity, conic=conic, uv=uv)
-        if self._frame_hw is None and any(v is True for v in asked.values()):
-            _check(lib().gs_blend_backward(self._h, C.byref(BlendGrads())))  # (refuses: there is no frame to size an input by)
-        h, w = self._frame_hw if self._frame_hw is not None else (None, None)
+        h, w = self._frame_extent("gs_blend_backward", BlendGrads, asked.values())
         g = BlendGrads()
         if grad_rgb is not None:
             g.grad_rgb = _tensor_exact("grad_rgb", grad_rgb, ("float32",), (h, w, 3), dev, owner)
@@ -986,16 +978,8 @@ class Renderer:
             raise ValueError("grad_rgb: an output is asked for but there is no grad_rgb")
         if grad_alpha is not None:
             g.grad_alpha = _tensor_exact("grad_alpha", grad_alpha, ("float32",), (h, w), dev, owner)
-        shapes = dict(colour=(n, 3), opacity=(n,), conic=(n, 3), uv=(n, 2))
-        result = {}
-        for name, t in asked.items():
-            if t is None:
-                continue
-            if t is True:
-                import torch
-                t = torch.zeros(shapes[name], dtype=torch.float64, device=f"cuda:{int(dev)}")
-            setattr(g, "d_" + name, _tensor_exact(name, t, ("float64",), shapes[name], dev, owner))
-            result[name] = t
+        result = _outputs(g, owner, dev, {name: _output(asked[name], "d_" + name, "float64", shape, zeros=True)
+                                          for name, shape in _record_shapes(n).items()})
         _complete_callers_work(grad_rgb, grad_alpha, *result.values())  # (the zeros allocated above among them)
         _check(lib().gs_blend_backward(self._h, C.byref(g)))
         return result
@@ -1013,26 +997,21 @@ class Renderer:
         owner = "Renderer.project_backward"
         n = int(self.scene.num_vertices)
         dev = self.scene.device
-        names = ("means", "log_scales", "quats", "opacity_logits", "sh_dc", "sh_rest")
         g = ProjectGrads()
         if out is None:
             if sh_degree not in SH_REST_COEFFS:
                 raise ValueError(f"sh_degree must be 0, 1, 2 or 3, not {sh_degree!r}")
         else:
-            unknown = sorted(set(out) - set(names))
+            unknown = sorted(set(out) - set(PARAMETER_NAMES))
             if unknown:
                 raise TypeError(f"out: unknown member(s) {unknown}")
-        ins = dict(colour=(colour, (n, 3)), opacity=(opacity, (n,)), conic=(conic, (n, 3)), uv=(uv, (n, 2)))
-        for name, (t, shape) in ins.items():
-            if t is not None:
-                setattr(g, "d_" + name, _tensor_exact(name, t, ("float64",), shape, dev, owner))
+        _record_gradients(g, owner, n, dev, colour=colour, opacity=opacity, conic=conic, uv=uv)
         if out is None:
             import torch
-            k = SH_REST_COEFFS[sh_degree]
-            shapes = dict(means=(n, 3), log_scales=(n, 3), quats=(n, 4), opacity_logits=(n,), sh_dc=(n, 3), sh_rest=(n, k, 3))
-            out = {name: torch.zeros(shapes[name], dtype=torch.float64, device=f"cuda:{int(dev)}") for name in names}
-        shapes = dict(means=(n, 3), log_scales=(n, 3), quats=(n, 4), opacity_logits=(n,), sh_dc=(n, 3), sh_rest=(n, None, 3))
-        for name in names:
+            out = {name: torch.zeros(shape, dtype=torch.float64, device=_torch_device(dev))
+                   for name, shape in _parameter_shapes(n, SH_REST_COEFFS[sh_degree]).items()}
+        shapes = _parameter_shapes(n, None)
+        for name in PARAMETER_NAMES:
             t = out.get(name)
             if t is None:
                 continue
@@ -1053,14 +1032,12 @@ class Renderer:
         -- the union over a camera set (zero it once).  The stream and the wait for torch's current stream are lift_pixels's;
         raises GsError before any frame was rendered.  Returns synchronised, with the tensor."""
         n, dev = int(self.scene.num_vertices), self.scene.device
-        if out is None:
-            import torch
-            out = torch.zeros(n, dtype=torch.uint8, device=f"cuda:{int(dev)}")
-        ptr = _tensor_exact("out", out, ("uint8",), (n,), dev, "Renderer.visible_mask")
-        if ptr is None:  # a scene of no Gaussians has no mask to write
+        mask = C.c_void_p()  # (its .value is the one member of this call's "struct")
+        out = _outputs(mask, "Renderer.visible_mask", dev, dict(out=_output(True if out is None else out, "value", "uint8", (n,), zeros=True)))["out"]
+        if mask.value is None:  # a scene of no Gaussians has no mask to write
             return out
         _complete_callers_work(out)
-        _check(lib().gs_visible_mask(self._h, C.c_void_p(ptr), C.c_int(1 if accumulate else 0)))
+        _check(lib().gs_visible_mask(self._h, mask, C.c_int(1 if accumulate else 0)))
         return out
 
     def differentiable_render(self, uniforms, means, log_scales, quats, opacity_logits, sh_dc, sh_rest=None, want_alpha=False):
@@ -1073,7 +1050,7 @@ class Renderer:
         lists, the 1/255 and 1e-4 cuts, the 0.99 clamp, the Jacobian clamp's branch, red's max(0, .)).  The camera carries no
         gradient.  A backward after this renderer has been handed another frame raises RuntimeError instead of returning the
         gradient of a different frame; so one backward per forward, before the next forward."""
-        return _render_function().apply(self, uniforms, bool(want_alpha), means, log_scales, quats, opacity_logits, sh_dc, sh_rest)
+        return _autograd().render.apply(self, uniforms, bool(want_alpha), means, log_scales, quats, opacity_logits, sh_dc, sh_rest)
 
     def camera_backward(self, colour=None, opacity=None, conic=None, uv=None, view_mat=True, proj_mat=True, camera_position=True):
         """The camera half of the last frame's backward (gs_camera_backward): from the same four float64 per-Gaussian gradients
@@ -1089,20 +1066,10 @@ class Renderer:
         n = int(self.scene.num_vertices)
         dev = self.scene.device
         g = CameraGrads()
-        ins = dict(colour=(colour, (n, 3)), opacity=(opacity, (n,)), conic=(conic, (n, 3)), uv=(uv, (n, 2)))
-        for name, (t, shape) in ins.items():
-            if t is not None:
-                setattr(g, "d_" + name, _tensor_exact(name, t, ("float64",), shape, dev, owner))
-        shapes = dict(view_mat=(16,), proj_mat=(16,), camera_position=(3,))
-        result = {}
-        for name, t in dict(view_mat=view_mat, proj_mat=proj_mat, camera_position=camera_position).items():
-            if t is None:
-                continue
-            if t is True:
-                import torch
-                t = torch.zeros(shapes[name], dtype=torch.float64, device=f"cuda:{int(dev)}")
-            setattr(g, "d_" + name, _tensor_exact(name, t, ("float64",), shapes[name], dev, owner))
-            result[name] = t
+        _record_gradients(g, owner, n, dev, colour=colour, opacity=opacity, conic=conic, uv=uv)
+        result = _outputs(g, owner, dev, dict(view_mat=_output(view_mat, "d_view_mat", "float64", (16,), zeros=True),
+                                              proj_mat=_output(proj_mat, "d_proj_mat", "float64", (16,), zeros=True),
+                                              camera_position=_output(camera_position, "d_camera_position", "float64", (3,), zeros=True)))
         _complete_callers_work(colour, opacity, conic, uv, *result.values())  # (the zeros allocated above among them)
         _check(lib().gs_camera_backward(self._h, C.byref(g)))
         return result
@@ -1139,22 +1106,12 @@ class Renderer:
         l.target = _tensor_exact("target", target, ("float32",), (h, w, tshape[2]), dev, owner)
         l.width, l.height, l.image_stride, l.target_stride = w, h, shape[2], tshape[2]
         result = dict(loss=None, terms=None, grad_rgb=None)
-        if grad is not None:
-            if grad is True:
-                import torch
-                grad = torch.empty((h, w, 3), dtype=torch.float32, device=f"cuda:{int(dev)}")
-            l.grad_rgb = _tensor_exact("grad", grad, ("float32",), (h, w, 3), dev, owner)
-            result["grad_rgb"] = grad
-        if terms is not None:
-            if terms is True:
-                import torch
-                terms = torch.empty((4,), dtype=torch.float64, device=f"cuda:{int(dev)}")
-            l.terms = _tensor_exact("terms", terms, ("float64",), (4,), dev, owner)
-            result["terms"] = terms
-        _complete_callers_work(image, target, grad, terms)
+        result.update(_outputs(l, owner, dev, dict(grad=_output(grad, "grad_rgb", "float32", (h, w, 3), key="grad_rgb"),
+                                                   terms=_output(terms, "terms", "float64", (4,)))))
+        _complete_callers_work(image, target, result["grad_rgb"], result["terms"])
         _check(lib().gs_photometric_loss(self._h, C.byref(l)))
         if terms is not None:
-            result["loss"] = terms[0]
+            result["loss"] = result["terms"][0]
         return result
 
     def differentiable_photometric_loss(self, image, target, lambda_dssim=0.2):
@@ -1165,7 +1122,7 @@ class Renderer:
         bind it.  A trainer's step:
             rgb = rend.differentiable_render(u, **params)
             rend.differentiable_photometric_loss(rgb, photo).backward()"""
-        return _photo_loss_function().apply(self, float(lambda_dssim), image, target)
+        return _autograd().photometric_loss.apply(self, float(lambda_dssim), image, target)
 
     def differentiable_render_posed(self, width, height, position, rotation, means=None, log_scales=None, quats=None, opacity_logits=None,
                                     sh_dc=None, sh_rest=None, fov=45.0, near=0.1, far=1000.0, want_alpha=False):
@@ -1179,7 +1136,7 @@ class Renderer:
         decisions as constants, as differentiable_render states it; rotation's is that of the RAW quaternion (an optimiser that
         normalises after each step needs no more; fov, near and far carry none).  One backward per forward, before the next
         forward: a backward after this renderer has been handed another frame raises RuntimeError."""
-        return _render_posed_function().apply(self, int(width), int(height), float(fov), float(near), float(far), bool(want_alpha),
+        return _autograd().render_posed.apply(self, int(width), int(height), float(fov), float(near), float(far), bool(want_alpha),
                                               position, rotation, means, log_scales, quats, opacity_logits, sh_dc, sh_rest)
 
     def differentiable_feature_maps(self, features):
@@ -1188,7 +1145,7 @@ class Renderer:
         opacities, covariances, the camera -- is a constant: the map is linear in features, and the backward is its transpose,
         lift_pixels of the incoming gradient, rounded to float32.  A backward after this renderer has been handed another frame
         raises RuntimeError instead of returning the gradient of a different frame."""
-        return _feature_maps_function().apply(self, features)
+        return _autograd().feature_maps.apply(self, features)
 
     def render_host(self, uniforms, want_rgba=True, want_bgra=False):
         h, w = int(uniforms["height"][0]), int(uniforms["width"][0])

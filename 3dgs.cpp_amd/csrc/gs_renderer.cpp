@@ -12,6 +12,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <limits>
 #include <memory>
 #include <utility>
@@ -523,6 +524,13 @@ struct gs_renderer {
         return k;
     }
 
+    // The scene as the kernels that read Gaussians take it: the frame's preprocess and the two backward passes to the parameters.
+    gs::SceneView scene_view() const {
+        const uint32_t n = static_cast<uint32_t>(scene->n);
+        return {scene->render_blob(), scene->cov3d.p, n, static_cast<uint32_t>(gs::blob_stride(n)),
+                scene->sh_half ? scene->sh16.p : nullptr, scene->acut.p, scene->perm.p};
+    }
+
     // Part (3) of enqueue.  Nothing that is queued needs to retire in here (ensure_tile_order's own drain finds nothing queued).
     void issue(const gs_uniforms& u, float* d_rgba, uint8_t* d_bgra) {
         FrameSlot& sl = slots[frames_enqueued % kSlots];
@@ -532,8 +540,7 @@ struct gs_renderer {
         const FramePlan plan = plan_frame(u, fb);
         lap(2);
 
-        gs::SceneView sv{scene->render_blob(), scene->cov3d.p, n, static_cast<uint32_t>(gs::blob_stride(n)),
-                          scene->sh_half ? scene->sh16.p : nullptr, scene->acut.p, scene->perm.p};
+        const gs::SceneView sv = scene_view();
         gs::Counters* cnt = fb.counters.p;
         gs::AttrView av{fb.tiles.p, fb.depth.p, fb.aabb.p, fb.rec.p, plan.dense_list ? fb.vis.p : nullptr, plan.dense_list ? fb.vis_count.p : nullptr,
                         fb.vis_region_slots};
@@ -960,6 +967,18 @@ struct gs_renderer {
     }
 };
 
+// What the passes refuse of their pointers before anything else looks at them: each of `members` {pointer, name}, in order, must
+// be k-byte aligned (by the pointer's value alone: nothing is dereferenced, and a null pointer passes).
+struct NamedPointer {
+    const void* p;
+    const char* name;
+};
+static void require_aligned(unsigned k, std::initializer_list<NamedPointer> members) {
+    for (const NamedPointer& m : members)
+        if (reinterpret_cast<uintptr_t>(m.p) % k != 0)
+            throw Error(GS_ERR_INVALID, std::string(m.name) + " must be " + std::to_string(k) + "-byte aligned");
+}
+
 // ------------------------------------------------------------------------------------------
 // C ABI
 // ------------------------------------------------------------------------------------------
@@ -1269,10 +1288,8 @@ int gs_debug_download(gs_renderer* r, int stage, void* dst, uint64_t bytes) {
 int gs_accumulate_contributions(gs_renderer* r, const gs_contributions* c) {
     return guarded([&] {
         if (!r || !c) throw Error(GS_ERR_INVALID, "null argument");
-        // (by the pointer's value alone: nothing is dereferenced here)
-        if (reinterpret_cast<uintptr_t>(c->weight) % 8 != 0) throw Error(GS_ERR_INVALID, "weight must be 8-byte aligned");
-        if (reinterpret_cast<uintptr_t>(c->pixels) % 4 != 0) throw Error(GS_ERR_INVALID, "pixels must be 4-byte aligned");
-        if (reinterpret_cast<uintptr_t>(c->top_id) % 4 != 0) throw Error(GS_ERR_INVALID, "top_id must be 4-byte aligned");
+        require_aligned(8, {{c->weight, "weight"}});
+        require_aligned(4, {{c->pixels, "pixels"}, {c->top_id, "top_id"}});
         r->over_last_frame(!c->weight && !c->pixels && !c->top_id, [&](const gs::TileLists& lists, hipStream_t s) {
             gs::launch_contributions(lists, c->mask, c->weight, c->pixels, c->top_id, s);
         });
@@ -1286,12 +1303,8 @@ int gs_blend_features(gs_renderer* r, const gs_feature_maps* m) {
         if (m->channels > GS_FEATURE_CHANNELS_MAX) throw Error(GS_ERR_INVALID, "channels exceeds GS_FEATURE_CHANNELS_MAX (256)");
         if (m->channels > 0 && !m->features) throw Error(GS_ERR_INVALID, "channels > 0 needs features");
         if (m->channels > 0 && !m->out_features) throw Error(GS_ERR_INVALID, "features given without out_features");
-        const struct { const void* p; const char* what; } ptrs[] = {
-            {m->features, "features must be 4-byte aligned"},         {m->out_features, "out_features must be 4-byte aligned"},
-            {m->out_alpha, "out_alpha must be 4-byte aligned"},       {m->out_depth, "out_depth must be 4-byte aligned"},
-            {m->out_depth_median, "out_depth_median must be 4-byte aligned"}};
-        for (const auto& q : ptrs)
-            if (reinterpret_cast<uintptr_t>(q.p) % 4 != 0) throw Error(GS_ERR_INVALID, q.what);
+        require_aligned(4, {{m->features, "features"}, {m->out_features, "out_features"}, {m->out_alpha, "out_alpha"},
+                            {m->out_depth, "out_depth"}, {m->out_depth_median, "out_depth_median"}});
         float* out_features = m->channels > 0 ? m->out_features : nullptr;  // channels == 0: that output is not touched
         r->over_last_frame(!out_features && !m->out_alpha && !m->out_depth && !m->out_depth_median, [&](const gs::TileLists& lists, hipStream_t s) {
             gs::launch_features(lists, m->features, m->channels, out_features, m->out_alpha, m->out_depth, m->out_depth_median, s);
@@ -1306,9 +1319,8 @@ int gs_lift_pixels(gs_renderer* r, const gs_pixel_lift* l) {
         if (l->channels > GS_LIFT_CHANNELS_MAX) throw Error(GS_ERR_INVALID, "channels exceeds GS_LIFT_CHANNELS_MAX (256)");
         if (l->channels > 0 && !l->values) throw Error(GS_ERR_INVALID, "channels > 0 needs values");
         if (l->channels > 0 && !l->out) throw Error(GS_ERR_INVALID, "values given without out");
-        if (reinterpret_cast<uintptr_t>(l->values) % 4 != 0) throw Error(GS_ERR_INVALID, "values must be 4-byte aligned");
-        if (reinterpret_cast<uintptr_t>(l->out) % 8 != 0) throw Error(GS_ERR_INVALID, "out must be 8-byte aligned");
-        if (reinterpret_cast<uintptr_t>(l->out_weight) % 8 != 0) throw Error(GS_ERR_INVALID, "out_weight must be 8-byte aligned");
+        require_aligned(4, {{l->values, "values"}});
+        require_aligned(8, {{l->out, "out"}, {l->out_weight, "out_weight"}});
         double* out = l->channels > 0 ? l->out : nullptr;  // channels == 0: that output is not touched
         r->over_last_frame(!out && !l->out_weight, [&](const gs::TileLists& lists, hipStream_t s) {
             gs::launch_lift(lists, l->mask, l->values, l->channels, out, l->out_weight, s);
@@ -1322,13 +1334,8 @@ int gs_blend_backward(gs_renderer* r, const gs_blend_grads* g) {
         // (all by the members' values alone: nothing is dereferenced and no device is touched before they pass)
         const bool asked = g->d_colour || g->d_opacity || g->d_conic || g->d_uv;
         if (asked && !g->grad_rgb) throw Error(GS_ERR_INVALID, "an output is given without grad_rgb");
-        if (reinterpret_cast<uintptr_t>(g->grad_rgb) % 4 != 0) throw Error(GS_ERR_INVALID, "grad_rgb must be 4-byte aligned");
-        if (reinterpret_cast<uintptr_t>(g->grad_alpha) % 4 != 0) throw Error(GS_ERR_INVALID, "grad_alpha must be 4-byte aligned");
-        const struct { const void* p; const char* what; } outs[] = {
-            {g->d_colour, "d_colour must be 8-byte aligned"}, {g->d_opacity, "d_opacity must be 8-byte aligned"},
-            {g->d_conic, "d_conic must be 8-byte aligned"},   {g->d_uv, "d_uv must be 8-byte aligned"}};
-        for (const auto& q : outs)
-            if (reinterpret_cast<uintptr_t>(q.p) % 8 != 0) throw Error(GS_ERR_INVALID, q.what);
+        require_aligned(4, {{g->grad_rgb, "grad_rgb"}, {g->grad_alpha, "grad_alpha"}});
+        require_aligned(8, {{g->d_colour, "d_colour"}, {g->d_opacity, "d_opacity"}, {g->d_conic, "d_conic"}, {g->d_uv, "d_uv"}});
         r->over_last_frame(!asked, [&](const gs::TileLists& lists, hipStream_t s) {
             gs::launch_blend_backward(lists, g->grad_rgb, g->grad_alpha, g->d_colour, g->d_opacity, g->d_conic, g->d_uv, s);
         });
@@ -1339,25 +1346,16 @@ int gs_project_backward(gs_renderer* r, const gs_project_grads* g) {
     return guarded([&] {
         if (!r || !g) throw Error(GS_ERR_INVALID, "null argument");
         // (all by the members' values alone: nothing is dereferenced and no device is touched before they pass)
-        const struct { const void* p; const char* what; } ptrs[] = {
-            {g->d_colour, "d_colour must be 8-byte aligned"},   {g->d_opacity, "d_opacity must be 8-byte aligned"},
-            {g->d_conic, "d_conic must be 8-byte aligned"},     {g->d_uv, "d_uv must be 8-byte aligned"},
-            {g->d_means, "d_means must be 8-byte aligned"},     {g->d_log_scales, "d_log_scales must be 8-byte aligned"},
-            {g->d_quats, "d_quats must be 8-byte aligned"},     {g->d_opacity_logits, "d_opacity_logits must be 8-byte aligned"},
-            {g->d_sh_dc, "d_sh_dc must be 8-byte aligned"},     {g->d_sh_rest, "d_sh_rest must be 8-byte aligned"}};
-        for (const auto& q : ptrs)
-            if (reinterpret_cast<uintptr_t>(q.p) % 8 != 0) throw Error(GS_ERR_INVALID, q.what);
+        require_aligned(8, {{g->d_colour, "d_colour"}, {g->d_opacity, "d_opacity"}, {g->d_conic, "d_conic"}, {g->d_uv, "d_uv"},
+                            {g->d_means, "d_means"}, {g->d_log_scales, "d_log_scales"}, {g->d_quats, "d_quats"},
+                            {g->d_opacity_logits, "d_opacity_logits"}, {g->d_sh_dc, "d_sh_dc"}, {g->d_sh_rest, "d_sh_rest"}});
         const uint32_t k = g->sh_rest_coeffs;
         if (k != 0 && k != 3 && k != 8 && k != 15) throw Error(GS_ERR_INVALID, "sh_rest_coeffs must be 0, 3, 8 or 15");
         if (k != 0 && !g->d_sh_rest) throw Error(GS_ERR_INVALID, "sh_rest_coeffs > 0 needs d_sh_rest");
         const bool asked = g->d_means || g->d_log_scales || g->d_quats || g->d_opacity_logits || g->d_sh_dc || (g->d_sh_rest && k != 0);
         r->over_last_frame(!asked, [&](const gs::TileLists& lists, hipStream_t s) {
             r->rebuild_planes();  // visibility is the tiles tap's answer (a frame of the dense lists or the one-pass level 1 wrote no planes)
-            const gs_scene* sc = r->scene;
-            const uint32_t n = static_cast<uint32_t>(sc->n);
-            const gs::SceneView sv{sc->render_blob(), sc->cov3d.p, n, static_cast<uint32_t>(gs::blob_stride(n)),
-                                   sc->sh_half ? sc->sh16.p : nullptr, sc->acut.p, sc->perm.p};
-            gs::launch_project_backward(sv, r->last_frame.set->tiles.p, lists.rec, r->last_frame.u, r->last_frame.antialiased, *g, s);
+            gs::launch_project_backward(r->scene_view(), r->last_frame.set->tiles.p, lists.rec, r->last_frame.u, r->last_frame.antialiased, *g, s);
         });
     });
 }
@@ -1366,22 +1364,13 @@ int gs_camera_backward(gs_renderer* r, const gs_camera_grads* g) {
     return guarded([&] {
         if (!r || !g) throw Error(GS_ERR_INVALID, "null argument");
         // (all by the members' values alone: nothing is dereferenced and no device is touched before they pass)
-        const struct { const void* p; const char* what; } ptrs[] = {
-            {g->d_colour, "d_colour must be 8-byte aligned"},     {g->d_opacity, "d_opacity must be 8-byte aligned"},
-            {g->d_conic, "d_conic must be 8-byte aligned"},       {g->d_uv, "d_uv must be 8-byte aligned"},
-            {g->d_view_mat, "d_view_mat must be 8-byte aligned"}, {g->d_proj_mat, "d_proj_mat must be 8-byte aligned"},
-            {g->d_camera_position, "d_camera_position must be 8-byte aligned"}};
-        for (const auto& q : ptrs)
-            if (reinterpret_cast<uintptr_t>(q.p) % 8 != 0) throw Error(GS_ERR_INVALID, q.what);
+        require_aligned(8, {{g->d_colour, "d_colour"}, {g->d_opacity, "d_opacity"}, {g->d_conic, "d_conic"}, {g->d_uv, "d_uv"},
+                            {g->d_view_mat, "d_view_mat"}, {g->d_proj_mat, "d_proj_mat"}, {g->d_camera_position, "d_camera_position"}});
         const bool asked = g->d_view_mat || g->d_proj_mat || g->d_camera_position;
         r->over_last_frame(!asked, [&](const gs::TileLists& lists, hipStream_t s) {
             r->rebuild_planes();  // visibility is the tiles tap's answer, as in gs_project_backward
             r->camera_partials.ensure(gs::camera_backward_partials());
-            const gs_scene* sc = r->scene;
-            const uint32_t n = static_cast<uint32_t>(sc->n);
-            const gs::SceneView sv{sc->render_blob(), sc->cov3d.p, n, static_cast<uint32_t>(gs::blob_stride(n)),
-                                   sc->sh_half ? sc->sh16.p : nullptr, sc->acut.p, sc->perm.p};
-            gs::launch_camera_backward(sv, r->last_frame.set->tiles.p, lists.rec, r->last_frame.u, r->last_frame.antialiased, *g,
+            gs::launch_camera_backward(r->scene_view(), r->last_frame.set->tiles.p, lists.rec, r->last_frame.u, r->last_frame.antialiased, *g,
                                        r->camera_partials.p, s);
         });
     });
@@ -1399,10 +1388,8 @@ int gs_photometric_loss(gs_renderer* r, const gs_photo_loss* l) {
         if (l->image_stride != 3 && l->image_stride != 4) throw Error(GS_ERR_INVALID, "image_stride must be 3 or 4");
         if (l->target_stride != 3 && l->target_stride != 4) throw Error(GS_ERR_INVALID, "target_stride must be 3 or 4");
         if (!(l->lambda_dssim >= 0.0 && l->lambda_dssim <= 1.0)) throw Error(GS_ERR_INVALID, "lambda_dssim must lie in [0, 1]");
-        if (reinterpret_cast<uintptr_t>(l->image) % 4 != 0) throw Error(GS_ERR_INVALID, "image must be 4-byte aligned");
-        if (reinterpret_cast<uintptr_t>(l->target) % 4 != 0) throw Error(GS_ERR_INVALID, "target must be 4-byte aligned");
-        if (reinterpret_cast<uintptr_t>(l->grad_rgb) % 4 != 0) throw Error(GS_ERR_INVALID, "grad_rgb must be 4-byte aligned");
-        if (reinterpret_cast<uintptr_t>(l->terms) % 8 != 0) throw Error(GS_ERR_INVALID, "terms must be 8-byte aligned");
+        require_aligned(4, {{l->image, "image"}, {l->target, "target"}, {l->grad_rgb, "grad_rgb"}});
+        require_aligned(8, {{l->terms, "terms"}});
         if (!asked) return;
         // Behind queued frames: they retire first, as for the passes over the last frame (an overflowed one is re-run, so `image`
         // may be the target of a gs_render that has not retired).  Nothing of the last frame is read or written from here on.

@@ -184,3 +184,47 @@ def compare_images(img, ref_img, ref, width, label="", max_flips=None):
     rest = d.copy()
     rest[ys, xs] = 0
     return float(rest.max()), flips
+
+
+# ---------------------------------------------------------------- the Python wrappers without a device
+class FakeTensor:
+    """The attributes the wrappers of binding.py read of a tensor, without torch or a device: what a device tensor of
+    another framework would offer."""
+
+    def __init__(self, shape, dtype="torch.float32", device="cuda:0", contiguous=True):
+        self.shape, self.dtype, self._c = shape, dtype, contiguous
+
+        class D:
+            type, index = device.split(":")[0], (int(device.split(":")[1]) if ":" in device else None)
+        self.device = D
+
+    def data_ptr(self):
+        return 4096
+
+    def is_contiguous(self):
+        return self._c
+
+
+class NoC:
+    """In place of the C library: a wrapper that has checked its arguments and goes on to C raises this AssertionError."""
+
+    def __getattr__(self, name):
+        raise AssertionError("the C library was reached")
+
+
+def forbid_c(pkg, monkeypatch):
+    monkeypatch.setattr(pkg.binding, "lib", lambda: NoC())
+
+
+def hand_made_scene(pkg, n=100):
+    """A Scene of `n` Gaussians on device 0 that holds no handle: num_vertices does not ask C."""
+    class SceneStub(pkg.Scene):
+        num_vertices = n
+    return SceneStub(None)
+
+
+def hand_made_renderer(pkg, n=100, frame_hw=(40, 72), frames=1):
+    """A Renderer that was never created in C: a scene of `n` Gaussians on device 0, `frame_hw` the last of `frames` frames."""
+    rend = object.__new__(pkg.Renderer)
+    rend.scene, rend._h, rend._frame_hw, rend._frames = hand_made_scene(pkg, n), None, frame_hw, frames
+    return rend

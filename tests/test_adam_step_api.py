@@ -11,6 +11,7 @@ import pytest
 
 import adam_step_reference as ar
 import composed_reference as comp
+from helpers import FakeTensor as _Fake, forbid_c, hand_made_renderer, hand_made_scene
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GS_ERR_INVALID = -1
@@ -176,35 +177,9 @@ def test_a_mask_of_ones_is_no_mask_and_a_mask_of_zeros_is_no_step(pkg):
 
 
 # ------------------------------------------------------------------------------------------------ the Python layer
-class _Fake:
-    """The attributes Scene.adam_step reads of a tensor, without torch or a device."""
-
-    def __init__(self, shape, dtype="torch.float32", device="cuda:0", contiguous=True):
-        self.shape, self.dtype, self._c = shape, dtype, contiguous
-
-        class D:
-            type, index = device.split(":")[0], (int(device.split(":")[1]) if ":" in device else None)
-        self.device = D
-
-    def data_ptr(self):
-        return 4096
-
-    def is_contiguous(self):
-        return self._c
-
-
 def test_the_wrapper_checks_its_tensors_before_it_reaches_c(pkg, monkeypatch):
-    class NoC:
-        def __getattr__(self, name):
-            raise AssertionError("the C library was reached")
-
-    class SceneStub(pkg.Scene):
-        num_vertices = 100
-
-        def __del__(self):
-            pass
-    monkeypatch.setattr(pkg.binding, "lib", lambda: NoC())
-    scene = SceneStub(None)
+    forbid_c(pkg, monkeypatch)
+    scene = hand_made_scene(pkg)
     f64 = "torch.float64"
     shapes = dict(means=(100, 3), log_scales=(100, 3), quats=(100, 4), opacity_logits=(100,), sh_dc=(100, 3), sh_rest=(100, 15, 3))
 
@@ -255,15 +230,8 @@ def test_the_wrapper_checks_its_tensors_before_it_reaches_c(pkg, monkeypatch):
 
 
 def test_visible_mask_checks_its_tensor_before_it_reaches_c(pkg, monkeypatch):
-    class NoC:
-        def __getattr__(self, name):
-            raise AssertionError("the C library was reached")
-    monkeypatch.setattr(pkg.binding, "lib", lambda: NoC())
-
-    class SceneStub:
-        num_vertices, device = 100, 0
-    rend = object.__new__(pkg.Renderer)
-    rend.scene, rend._h = SceneStub(), None
+    forbid_c(pkg, monkeypatch)
+    rend = hand_made_renderer(pkg)
     with pytest.raises(AssertionError, match="C library was reached"):
         rend.visible_mask(out=_Fake((100,), "torch.uint8"), accumulate=True)
     for out, error in ((_Fake((100,), "torch.int8"), TypeError), (_Fake((101,), "torch.uint8"), ValueError),

@@ -11,7 +11,7 @@ import pytest
 
 import backward_reference as bref
 import lift_reference as lref
-from helpers import assert_images_identical, oracle_frame
+from helpers import assert_images_identical, FakeTensor as _Fake, forbid_c, hand_made_renderer, oracle_frame
 
 SCENES = {"A": (600, 72, 40), "T": (1500, 64, 64)}   # synth_records(n, seed=5, kind): n, width, height
 INVALID = -1                                         # GS_ERR_INVALID
@@ -177,33 +177,9 @@ def test_the_structure_has_the_headers_layout(pkg):
 
 
 # ------------------------------------------------------------------------------------------------ the wrapper
-class _Fake:
-    """The attributes Renderer.blend_backward reads of a tensor, without torch or a device."""
-
-    def __init__(self, shape, dtype="torch.float32", device="cuda:0", contiguous=True):
-        self.shape, self.dtype, self._c = shape, dtype, contiguous
-
-        class D:
-            type, index = device.split(":")[0], (int(device.split(":")[1]) if ":" in device else None)
-        self.device = D
-
-    def data_ptr(self):
-        return 4096
-
-    def is_contiguous(self):
-        return self._c
-
-
 def test_the_wrapper_checks_its_tensors_before_it_reaches_c(pkg, monkeypatch):
-    class NoC:
-        def __getattr__(self, name):
-            raise AssertionError("the C library was reached")
-    monkeypatch.setattr(pkg.binding, "lib", lambda: NoC())
-
-    class SceneStub:
-        num_vertices, device = 100, 0
-    rend = object.__new__(pkg.Renderer)
-    rend.scene, rend._h, rend._frame_hw, rend._frames = SceneStub(), None, (40, 72), 1
+    forbid_c(pkg, monkeypatch)
+    rend = hand_made_renderer(pkg, frame_hw=(40, 72))
     f64 = "torch.float64"
     good = dict(grad_rgb=_Fake((40, 72, 3)), grad_alpha=_Fake((40, 72)), colour=_Fake((100, 3), f64), opacity=_Fake((100,), f64),
                 conic=_Fake((100, 3), f64), uv=_Fake((100, 2), f64))

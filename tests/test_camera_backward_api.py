@@ -16,7 +16,7 @@ import camera_backward_reference as cref
 import camera_record_torch as crt
 import project_backward_reference as pref
 import project_backward_scenes as psc
-from helpers import oracle_frame
+from helpers import forbid_c, hand_made_renderer, oracle_frame
 from test_project_backward_api import SCENES
 
 INVALID = -1
@@ -347,15 +347,8 @@ def test_the_structure_has_the_headers_layout(pkg):
 def test_the_wrapper_checks_its_tensors_before_it_reaches_c(pkg, monkeypatch):
     from test_project_backward_api import _Fake
 
-    class NoC:
-        def __getattr__(self, name):
-            raise AssertionError("the C library was reached")
-    monkeypatch.setattr(pkg.binding, "lib", lambda: NoC())
-
-    class SceneStub:
-        num_vertices, device = 100, 0
-    rend = object.__new__(pkg.Renderer)
-    rend.scene, rend._h, rend._frame_hw, rend._frames = SceneStub(), None, (40, 72), 1
+    forbid_c(pkg, monkeypatch)
+    rend = hand_made_renderer(pkg, frame_hw=(40, 72))
     ins = dict(colour=_Fake((100, 3)), opacity=_Fake((100,)), conic=_Fake((100, 3)), uv=_Fake((100, 2)))
     outs = dict(view_mat=_Fake((16,)), proj_mat=_Fake((16,)), camera_position=_Fake((3,)))
     with pytest.raises(AssertionError, match="C library was reached"):   # everything in order: the call goes through to C

@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 import contribution_reference as cref
-from helpers import assert_images_identical, oracle_frame
+from helpers import assert_images_identical, FakeTensor as _Fake, forbid_c, hand_made_renderer, oracle_frame
 
 SCENES = {"A": (600, 80, 48), "T": (1500, 64, 64)}   # synth_records(n, seed=5, kind): n, width, height
 
@@ -75,33 +75,9 @@ def test_null_arguments_are_refused_without_a_device(pkg):
     assert b"null" in L.gs_last_error()
 
 
-class _Fake:
-    """The attributes Renderer.contributions reads of a tensor, without torch or a device."""
-
-    def __init__(self, shape, dtype, device="cuda:0", contiguous=True):
-        self.shape, self.dtype, self._c = shape, dtype, contiguous
-
-        class D:
-            type, index = device.split(":")[0], (int(device.split(":")[1]) if ":" in device else None)
-        self.device = D
-
-    def data_ptr(self):
-        return 4096
-
-    def is_contiguous(self):
-        return self._c
-
-
 def test_the_wrapper_checks_its_tensors_before_it_reaches_c(pkg, monkeypatch):
-    class NoC:
-        def __getattr__(self, name):
-            raise AssertionError("the C library was reached")
-    monkeypatch.setattr(pkg.binding, "lib", lambda: NoC())
-
-    class SceneStub:
-        num_vertices, device = 100, 0
-    rend = object.__new__(pkg.Renderer)
-    rend.scene, rend._h, rend._frame_hw = SceneStub(), None, (48, 80)
+    forbid_c(pkg, monkeypatch)
+    rend = hand_made_renderer(pkg, frame_hw=(48, 80))
     good = dict(weight=_Fake((100,), "torch.int64"), pixels=_Fake((100,), "torch.int32"), top_id=_Fake((48, 80), "torch.int32"),
                 mask=_Fake((48, 80), "torch.uint8"))
     with pytest.raises(AssertionError, match="C library was reached"):   # everything in order: the call goes through to C

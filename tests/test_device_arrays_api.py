@@ -10,6 +10,8 @@ import re
 import numpy as np
 import pytest
 
+from helpers import FakeTensor as _Fake, forbid_c
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("gs_scene_from_device_arrays", "gs_scene_update_from_device_arrays", "gs_debug_activation_expf_scan")
 GS_ERR_INVALID = -1
@@ -87,29 +89,9 @@ def test_update_refuses_bad_arguments_before_it_selects_a_device(pkg):
     del keep, keep_b
 
 
-class _Fake:
-    """The attributes Scene.from_tensors reads, without torch: what a device tensor of another framework would offer."""
-
-    def __init__(self, shape, dtype="float32", device="cuda:0", contiguous=True):
-        self.shape, self.dtype, self._c = shape, dtype, contiguous
-
-        class D:
-            type, index = device.split(":")[0], (int(device.split(":")[1]) if ":" in device else None)
-        self.device = D
-
-    def data_ptr(self):
-        return 4096
-
-    def is_contiguous(self):
-        return self._c
-
-
 def test_from_tensors_rejects_what_the_abi_cannot_take_without_reaching_c(pkg, monkeypatch):
     torch = pytest.importorskip("torch")
-
-    def no_c():
-        raise AssertionError("the C library was reached")
-    monkeypatch.setattr(pkg.binding, "lib", no_c)
+    forbid_c(pkg, monkeypatch)
     n = 8
     good = dict(means=_Fake((n, 3)), log_scales=_Fake((n, 3)), quats=_Fake((n, 4)), opacity_logits=_Fake((n, 1)), sh_dc=_Fake((n, 1, 3)),
                 sh_rest=_Fake((n, 15, 3)))

@@ -15,6 +15,7 @@ from fractions import Fraction
 import numpy as np
 import pytest
 
+from helpers import forbid_c, hand_made_renderer
 import photometric_loss_images as pli
 import photometric_loss_reference as plr
 import photometric_loss_rows as plrows
@@ -315,15 +316,8 @@ def test_the_structure_has_the_headers_layout(pkg):
 def test_the_wrapper_checks_its_tensors_before_it_reaches_c(pkg, monkeypatch):
     from test_project_backward_api import _Fake
 
-    class NoC:
-        def __getattr__(self, name):
-            raise AssertionError("the C library was reached")
-    monkeypatch.setattr(pkg.binding, "lib", lambda: NoC())
-
-    class SceneStub:
-        num_vertices, device = 100, 0
-    rend = object.__new__(pkg.Renderer)
-    rend.scene, rend._h, rend._frame_hw, rend._frames = SceneStub(), None, None, 0      # (no frame rendered: the loss needs none)
+    forbid_c(pkg, monkeypatch)
+    rend = hand_made_renderer(pkg, frame_hw=None, frames=0)      # (no frame rendered: the loss needs none)
     f32 = "torch.float32"
     img, tgt = _Fake((40, 72, 4), f32), _Fake((40, 72, 3), f32)
     grad, terms = _Fake((40, 72, 3), f32), _Fake((4,))

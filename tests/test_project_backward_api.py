@@ -13,7 +13,7 @@ import pytest
 import project_backward_reference as pref
 import project_backward_scenes as psc
 import record_function_torch as rft
-from helpers import oracle_frame
+from helpers import FakeTensor, forbid_c, hand_made_renderer, oracle_frame
 
 SCENES = {"A": (600, 72, 40), "T": (1500, 64, 64)}   # synth_records(n, seed=5, kind): n, width, height; and "branch"
 INVALID = -1                                         # GS_ERR_INVALID
@@ -175,33 +175,14 @@ def test_the_structure_has_the_headers_layout(pkg):
 
 
 # ------------------------------------------------------------------------------------------------ the wrapper
-class _Fake:
-    """The attributes Renderer.project_backward reads of a tensor, without torch or a device."""
-
-    def __init__(self, shape, dtype="torch.float64", device="cuda:0", contiguous=True):
-        self.shape, self.dtype, self._c = shape, dtype, contiguous
-
-        class D:
-            type, index = device.split(":")[0], (int(device.split(":")[1]) if ":" in device else None)
-        self.device = D
-
-    def data_ptr(self):
-        return 4096
-
-    def is_contiguous(self):
-        return self._c
+def _Fake(shape, dtype="torch.float64", **how):
+    """helpers.FakeTensor, float64 unless told: the dtype of what project_backward takes and adds to."""
+    return FakeTensor(shape, dtype, **how)
 
 
 def test_the_wrapper_checks_its_tensors_before_it_reaches_c(pkg, monkeypatch):
-    class NoC:
-        def __getattr__(self, name):
-            raise AssertionError("the C library was reached")
-    monkeypatch.setattr(pkg.binding, "lib", lambda: NoC())
-
-    class SceneStub:
-        num_vertices, device = 100, 0
-    rend = object.__new__(pkg.Renderer)
-    rend.scene, rend._h, rend._frame_hw, rend._frames = SceneStub(), None, (40, 72), 1
+    forbid_c(pkg, monkeypatch)
+    rend = hand_made_renderer(pkg, frame_hw=(40, 72))
     f32 = "torch.float32"
     ins = dict(colour=_Fake((100, 3)), opacity=_Fake((100,)), conic=_Fake((100, 3)), uv=_Fake((100, 2)))
     out = dict(means=_Fake((100, 3)), log_scales=_Fake((100, 3)), quats=_Fake((100, 4)), opacity_logits=_Fake((100,)),

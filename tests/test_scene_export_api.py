@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import export_reference as ref
+from helpers import FakeTensor as _Fake, forbid_c
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("gs_deactivate_vertices", "gs_write_ply", "gs_scene_to_device_arrays", "gs_scene_download_records", "gs_scene_save_ply")
@@ -248,28 +249,8 @@ def test_the_device_entry_points_refuse_bad_arguments_before_they_select_a_devic
     del keep
 
 
-class _Fake:
-    """The attributes to_tensors reads of a member of `out`, without torch or a device."""
-
-    def __init__(self, shape, dtype="float32", device="cuda:0", contiguous=True):
-        self.shape, self.dtype, self._c = shape, dtype, contiguous
-
-        class D:
-            type, index = device.split(":")[0], (int(device.split(":")[1]) if ":" in device else None)
-        self.device = D
-
-    def data_ptr(self):
-        return 4096
-
-    def is_contiguous(self):
-        return self._c
-
-
 def test_to_tensors_checks_out_before_it_reaches_c(pkg, monkeypatch):
-    class NoC:
-        def __getattr__(self, name):
-            raise AssertionError("the C library was reached")
-    monkeypatch.setattr(pkg.binding, "lib", lambda: NoC())
+    forbid_c(pkg, monkeypatch)
     scene = pkg.Scene(None)
     n = 8
     with pytest.raises(TypeError, match="float32"):
