@@ -24,7 +24,7 @@ BLOB_PLANES = 59
 
 # the device code of libgs3d_hip.so: one translation unit per stage + the shared device headers
 KERNEL_SOURCES = ("gs_device.h", "gs_bin.h", "gs_tile_cull.h", "gs_scene.hip", "gs_preprocess.hip", "gs_radix.hip", "gs_bin_l1.hip", "gs_bin_l2.hip",
-                  "gs_blend.hip", "gs_contrib.hip", "gs_features.hip", "gs_lift.hip", "gs_backward.hip", "gs_project_backward.hip", "gs_camera_backward.hip", "gs_loss.hip", "gs_optim.hip", "gs_project_chain.h",
+                  "gs_blend.hip", "gs_contrib.hip", "gs_features.hip", "gs_lift.hip", "gs_backward.hip", "gs_project_backward.hip", "gs_camera_backward.hip", "gs_loss.hip", "gs_optim.hip", "gs_densify.hip", "gs_project_chain.h",
                   "gs_wave_f64.h", "gs_kernels.h")
 
 
@@ -63,7 +63,7 @@ SYMBOLS = ["gs_last_error", "gs_device_count", "gs_read_ply", "gs_activate_recor
            "gs_deactivate_vertices", "gs_write_ply", "gs_scene_to_device_arrays", "gs_scene_download_records", "gs_scene_save_ply",
            "gs_scene_destroy", "gs_renderer_create", "gs_renderer_destroy", "gs_camera_uniforms",
            "gs_render", "gs_render_host", "gs_synchronize", "gs_set_timing", "gs_set_frames_in_flight", "gs_set_sort_path", "gs_set_exp_mode", "gs_set_graph_mode", "gs_set_blend_lockstep", "gs_get_blend_lockstep", "gs_set_level1_fused", "gs_get_level1_fused", "gs_set_tile_cull", "gs_get_tile_cull", "gs_get_listed_instances", "gs_set_blend_contraction", "gs_set_antialiased", "gs_get_antialiased", "gs_get_timing_totals",
-           "gs_get_frame_intervals", "gs_get_stats", "gs_poll_stats", "gs_debug_download", "gs_accumulate_contributions", "gs_blend_features", "gs_lift_pixels", "gs_blend_backward", "gs_project_backward", "gs_camera_backward", "gs_camera_uniforms_backward", "gs_photometric_loss", "gs_visible_mask", "gs_scene_adam_step", "gs_debug_expf_scan", "gs_debug_alpha_cut_scan", "gs_renderer_stream",
+           "gs_get_frame_intervals", "gs_get_stats", "gs_poll_stats", "gs_debug_download", "gs_accumulate_contributions", "gs_blend_features", "gs_lift_pixels", "gs_blend_backward", "gs_project_backward", "gs_camera_backward", "gs_camera_uniforms_backward", "gs_photometric_loss", "gs_visible_mask", "gs_scene_adam_step", "gs_accumulate_densify_stats", "gs_densify_plan", "gs_densify_apply", "gs_debug_expf_scan", "gs_debug_alpha_cut_scan", "gs_renderer_stream",
            "gs_dist_unique_id", "gs_dist_create", "gs_dist_rank", "gs_dist_world", "gs_dist_pose_count",
            "gs_dist_broadcast_scene", "gs_dist_broadcast_scene_ex", "gs_dist_verify", "gs_dist_destroy"]
 
@@ -275,6 +275,35 @@ class AdamStep(C.Structure):
                 ("sh_dc", AdamGroup), ("sh_rest", AdamGroup), ("sh_rest_coeffs", C.c_uint32), ("mask", C.c_void_p),
                 ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double),
                 ("bias_correction1", C.c_double), ("bias_correction2", C.c_double), ("zero_grads", C.c_int)]
+
+
+class DensifyStats(C.Structure):
+    """gs_densify_stats: blend_backward's uv sum and the three statistic arrays of gs_accumulate_densify_stats (include/gs3d_hip.h)."""
+    _fields_ = [("d_uv", C.c_void_p), ("grad_sum", C.c_void_p), ("count", C.c_void_p), ("max_radius", C.c_void_p)]
+
+
+class DensifyRule(C.Structure):
+    """gs_densify_rule: the thresholds of gs_densify_plan (include/gs3d_hip.h); max_screen_radius, max_world_scale <= 0: off."""
+    _fields_ = [("grad_threshold", C.c_double), ("dense_extent", C.c_double), ("min_opacity", C.c_double),
+                ("max_screen_radius", C.c_double), ("max_world_scale", C.c_double)]
+
+
+class DensifyInput(C.Structure):
+    """gs_densify_input: the model, its statistics, the rule and the scratch of gs_densify_plan / gs_densify_apply."""
+    _fields_ = [("params", DeviceArrays), ("grad_sum", C.c_void_p), ("count", C.c_void_p), ("max_radius", C.c_void_p),
+                ("rule", DensifyRule), ("scratch", C.c_void_p)]
+
+
+class DensifyOutput(C.Structure):
+    """gs_densify_output: the moments in, the noise, the plan's two counts and every output array of gs_densify_apply."""
+    _fields_ = [("exp_avg", C.c_void_p * 6), ("exp_avg_sq", C.c_void_p * 6), ("noise", C.c_void_p), ("n_noise", C.c_uint64),
+                ("n_out", C.c_uint64), ("params", DeviceArrays), ("out_exp_avg", C.c_void_p * 6), ("out_exp_avg_sq", C.c_void_p * 6)]
+
+
+DENSIFY_PARTITION = 2048  # GS_DENSIFY_PARTITION: parents per workgroup of the plan's scan
+DENSIFY_BLOCK = 256       # GS_DENSIFY_BLOCK: parents per workgroup of the apply
+DENSIFY_LOG_1_6 = float.fromhex("0x1.e148a1a2726cep-2")  # GS_DENSIFY_LOG_1_6
+DENSIFY_STATS = dict(grad_sum=("float64",), count=("int32", "uint32"), max_radius=("float32",))  # the statistic's tensors and dtypes
 
 
 PHOTO_LOSS_MAX_EXTENT = 16384   # GS_PHOTO_LOSS_MAX_EXTENT: width and height of gs_photometric_loss
@@ -632,6 +661,150 @@ def write_ply(path, records):
 
 
 SH_REST_COEFFS = {0: 0, 1: 3, 2: 8, 3: 15}  # SH degree -> coefficients above the DC term
+
+
+def _densify_stats(struct, stats, n, device, owner):
+    """Set grad_sum / count / max_radius of `struct` from the dict `stats` after checking its three tensors; returns them."""
+    unknown = sorted(set(stats) - set(DENSIFY_STATS))
+    if unknown:
+        raise TypeError(f"stats: unknown member(s) {unknown}")
+    used = []
+    for name, dtypes in DENSIFY_STATS.items():
+        if stats.get(name) is None:
+            raise TypeError(f"stats[{name!r}] is required")
+        setattr(struct, name, _tensor_exact(f"stats[{name!r}]", stats[name], dtypes, (n,), device, owner))
+        used.append(stats[name])
+    return used
+
+
+def densify_stats_zeros(scene):
+    """The three tensors Renderer.densify_stats accumulates into and densify decides by, zeroed, on the scene's device:
+    {grad_sum: float64 (N,), count: int32 (N,), max_radius: float32 (N,)}."""
+    import torch
+    n, dev = int(scene.num_vertices), _torch_device(scene.device)
+    return dict(grad_sum=torch.zeros(n, dtype=torch.float64, device=dev), count=torch.zeros(n, dtype=torch.int32, device=dev),
+                max_radius=torch.zeros(n, dtype=torch.float32, device=dev))
+
+
+def _densify_rule(rule):
+    """DensifyRule from a DensifyRule or a dict of its members (max_screen_radius and max_world_scale default to 0 = off)."""
+    if isinstance(rule, DensifyRule):
+        return rule
+    names = [f[0] for f in DensifyRule._fields_]
+    unknown = sorted(set(rule) - set(names))
+    if unknown:
+        raise TypeError(f"rule: unknown member(s) {unknown}")
+    r = DensifyRule()
+    for name in names:
+        if name not in rule and name not in ("max_screen_radius", "max_world_scale"):
+            raise TypeError(f"rule[{name!r}] is required")
+        v = float(rule.get(name, 0.0))
+        if v != v:
+            raise ValueError(f"rule[{name!r}] is NaN")
+        setattr(r, name, v)
+    return r
+
+
+def densify(scene, params, rule, stats, state=None, noise=None, stream=None):
+    """Adaptive density control of a trainer's model on the device (gs_densify_plan + gs_densify_apply): clone
+    the Gaussians whose average screen-space gradient norm reaches rule['grad_threshold'] and whose largest scale is at most
+    rule['dense_extent'], split the larger ones in two (scales / 1.6, means drawn from the parent), then prune over the extended
+    set -- opacity below rule['min_opacity'], a screen radius above rule['max_screen_radius'], a scale above
+    rule['max_world_scale'] (<= 0 or absent: off).
+    scene: the scene the model belongs to (its device and Gaussian count; it is not changed).  params: the six tensors of
+    Scene.from_tensors under its keyword names (sh_rest may be absent or None).  stats: what Renderer.densify_stats accumulated.
+    state: None, or {'exp_avg': {name: tensor}, 'exp_avg_sq': {name: tensor}} -- Adam's moments, float32, shaped as the
+    parameters; a name absent from BOTH has no moments to carry.  noise: float32 (rows, 2, 3) standard-normal draws with at least
+    as many rows as parents are split (n rows always suffice; rows beyond are not read), None: torch.randn.  The kernels hold no
+    random number generator: with given noise the result is a pure function of the inputs, bit for bit.
+    Returns (new_params, new_state, info): tensors of n_out rows allocated here, ordered by PARENT (a parent's survivors adjacent,
+    the original before its copy); survivors keep parameters and moments bit for bit, new rows have zero moments; new_state is
+    None when state is.  info: n_in, n_out, n_noise (= parents_split) and the parents by outcome -- parents_removed (no row left),
+    parents_single, parents_cloned (two rows, not split), parents_split (two children) -- and the plan's two int32 tensors
+    row_offset and noise_offset (n + 1 each): parent i's rows are [row_offset[i], row_offset[i + 1]) of the outputs, which carries
+    any other per-Gaussian array of the caller's along.  The caller builds
+    Scene.from_tensors(**new_params) and a new Renderer.  Waits for torch's current stream first; runs on `stream` (None:
+    torch's current stream) and returns synchronised."""
+    owner = "densify"
+    dev, n = scene.device, int(scene.num_vertices)
+    unknown = sorted(set(params) - set(PARAMETER_NAMES))
+    if unknown:
+        raise TypeError(f"params: unknown member(s) {unknown}")
+    inp = DensifyInput()
+    inp.params, rows = _device_arrays({name: params.get(name) for name in PARAMETER_NAMES}, dev, require=True)
+    if rows != n:
+        raise ValueError(f"params have {rows} rows, the scene {n} Gaussians")
+    k = int(inp.params.sh_rest_coeffs)
+    given = [name for name in PARAMETER_NAMES if params.get(name) is not None and (name != "sh_rest" or k)]
+    used = [params[name] for name in given] + _densify_stats(inp, stats, n, dev, owner)
+    inp.rule = _densify_rule(rule)
+    out = DensifyOutput()
+    moments = {}
+    if state is not None:
+        unknown = sorted(set(state) - {"exp_avg", "exp_avg_sq"})
+        if unknown or "exp_avg" not in state or "exp_avg_sq" not in state:
+            raise TypeError(f"state: a dict of exp_avg and exp_avg_sq is needed, got {sorted(state)}")
+        for what in ("exp_avg", "exp_avg_sq"):
+            unknown = sorted(set(state[what]) - set(PARAMETER_NAMES))
+            if unknown:
+                raise TypeError(f"state[{what!r}]: unknown member(s) {unknown}")
+        for g, name in enumerate(PARAMETER_NAMES):
+            have = [what for what in ("exp_avg", "exp_avg_sq") if state[what].get(name) is not None]
+            if not have:
+                continue
+            if len(have) != 2:
+                raise ValueError(f"{name}: a partial pair of moments -- given in {have[0]} only")
+            if name not in given:
+                raise ValueError(f"{name}: moments without the parameter")
+            shape = tuple(int(d) for d in params[name].shape)
+            for what in have:
+                t = state[what][name]
+                getattr(out, what)[g] = _tensor_exact(f"state[{what!r}][{name!r}]", t, ("float32",), shape, dev, owner)
+                used.append(t)
+            moments[name] = g
+    if noise is not None:
+        _tensor_exact("noise", noise, ("float32",), (None, 2, 3), dev, owner)
+        used.append(noise)
+    import torch
+    L = lib()
+    plan, apply = L.gs_densify_plan, L.gs_densify_apply   # (every check above comes before C, and before anything is allocated)
+    _complete_callers_work(*used)
+    handle = _stream_handle(stream)
+    tdev = _torch_device(dev)
+    scratch = torch.empty(2 * (n + 1), dtype=torch.int32, device=tdev)
+    inp.scratch = scratch.data_ptr()
+    n_out, n_noise = C.c_uint64(0), C.c_uint64(0)
+    _check(plan(C.byref(inp), C.c_uint64(n), C.c_int(dev), handle, C.byref(n_out), C.byref(n_noise)))
+    n_out, n_noise = int(n_out.value), int(n_noise.value)
+    if noise is None:
+        noise = torch.randn((n_noise, 2, 3), dtype=torch.float32, device=tdev)
+        torch.cuda.current_stream(noise.device).synchronize()
+    elif int(noise.shape[0]) < n_noise:
+        raise ValueError(f"noise has {int(noise.shape[0])} rows, {n_noise} parents are split")
+    out.noise, out.n_noise, out.n_out = (noise.data_ptr() if n_noise else None), n_noise, n_out
+    out.params.sh_rest_coeffs = k
+    new_params, new_state = {}, (None if state is None else dict(exp_avg={}, exp_avg_sq={}))
+    for name in given:
+        shape = (n_out,) + tuple(int(d) for d in params[name].shape[1:])
+        new_params[name] = torch.empty(shape, dtype=torch.float32, device=tdev)
+        setattr(out.params, name, new_params[name].data_ptr() if n_out else None)
+        if name in moments:
+            for what in ("exp_avg", "exp_avg_sq"):
+                t = torch.empty(shape, dtype=torch.float32, device=tdev)
+                new_state[what][name] = t
+                getattr(out, "out_" + what)[moments[name]] = t.data_ptr() if n_out else None
+    if "sh_rest" in params and params["sh_rest"] is not None and not k:
+        new_params["sh_rest"] = torch.empty((n_out, 0, 3), dtype=torch.float32, device=tdev)
+    _check(apply(C.byref(inp), C.c_uint64(n), C.byref(out), C.c_int(dev), handle))
+    info = dict(n_in=n, n_out=n_out, n_noise=n_noise, parents_removed=0, parents_single=0, parents_cloned=0, parents_split=n_noise,
+                row_offset=scratch[:n + 1], noise_offset=scratch[n + 1:])
+    if n:
+        rows_of = scratch[1:n + 1] - scratch[0:n]
+        split = (scratch[n + 2:2 * n + 2] - scratch[n + 1:2 * n + 1]) != 0
+        info["parents_removed"] = int((rows_of == 0).sum())
+        info["parents_single"] = int((rows_of == 1).sum())
+        info["parents_cloned"] = int(((rows_of == 2) & ~split).sum())
+    return new_params, new_state, info
 
 
 class Scene:
@@ -1040,6 +1213,25 @@ class Renderer:
         _check(lib().gs_visible_mask(self._h, mask, C.c_int(1 if accumulate else 0)))
         return out
 
+    def densify_stats(self, uv, stats):
+        """The last frame's share of the statistic densify decides by (gs_accumulate_densify_stats): for every Gaussian the frame
+        saw, grad_sum += the norm of its row of `uv` -- blend_backward's float64 (N, 2) sum for this frame -- scaled by half the
+        frame's width and height (the Inria trainer's viewspace gradient norm), count += 1, max_radius = max(max_radius, its
+        screen radius).  stats: the dict densify_stats_zeros(scene) allocates -- grad_sum float64 (N,), count int32 (N,) (uint32 is
+        taken too: the same bits), max_radius float32 (N,).  An invisible Gaussian's elements are neither read nor written.  The
+        stream and the wait for torch's current stream are lift_pixels's; raises GsError before any frame was rendered.  Returns
+        synchronised, with stats."""
+        owner = "Renderer.densify_stats"
+        n, dev = int(self.scene.num_vertices), self.scene.device
+        st = DensifyStats()
+        st.d_uv = _tensor_exact("uv", uv, ("float64",), (n, 2), dev, owner)
+        used = [uv] + _densify_stats(st, stats, n, dev, owner)
+        if n == 0:  # a scene of no Gaussians has no statistic to keep
+            return stats
+        _complete_callers_work(*used)
+        _check(lib().gs_accumulate_densify_stats(self._h, C.byref(st)))
+        return stats
+
     def differentiable_render(self, uniforms, means, log_scales, quats, opacity_logits, sh_dc, sh_rest=None, want_alpha=False):
         """One frame as a torch.autograd.Function of the trainer's six parameter tensors (float32, on the renderer's device, as
         Scene.from_tensors takes them, one row per Gaussian of the scene): the forward refreshes the scene from them
@@ -1321,6 +1513,29 @@ class Adam:
         except Exception:
             self.t -= 1  # a refused step is no step
             raise
+
+    def densify(self, rule, stats, noise=None):
+        """Adaptive density control of the optimiser's model (densify): the parameters and the moments are
+        replaced by the densified ones, a NEW scene is built from them (Scene.from_tensors) and returned; self.scene, self.params
+        and self.state are replaced, the step count stays.  The old scene and its renderers stay valid until the caller closes
+        them; make a new Renderer and new statistics (densify_stats_zeros) for the new scene.  The optimiser must hold the whole
+        model (every tensor Scene.from_tensors requires), since all of it is compacted.  What happened: self.densify_info."""
+        new_params, new_state, info = densify(self.scene, self.params, rule, stats, self.state, noise)
+        scene = Scene.from_tensors(**new_params, device=self.scene.device)
+        self.scene, self.params, self.state, self.densify_info = scene, new_params, new_state, info
+        return scene
+
+    def reset_opacity(self, ceiling=0.01):
+        """The trainers' opacity reset: opacity_logits <- min(logit, logit(ceiling)), both opacity moments zeroed, the scene's
+        opacity plane refreshed (Scene.update_from_tensors).  Synchronize every renderer of the scene first."""
+        import math
+        if not 0.0 < float(ceiling) < 1.0:
+            raise ValueError(f"ceiling must lie in (0, 1), not {ceiling!r}")
+        logits = self.params["opacity_logits"]
+        logits.clamp_(max=math.log(float(ceiling) / (1.0 - float(ceiling))))
+        self.state["exp_avg"]["opacity_logits"].zero_()
+        self.state["exp_avg_sq"]["opacity_logits"].zero_()
+        self.scene.update_from_tensors(0, opacity_logits=logits, device=self.scene.device)
 
 
 class Dist:

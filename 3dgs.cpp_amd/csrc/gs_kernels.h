@@ -349,4 +349,17 @@ void launch_adam_step(const AdamStep& a, float* blob, uint32_t stride, uint32_t 
 // gs_visible_mask: mask[id] = tiles[id] != 0, or that ORed into mask[id]; tiles: the frame's tiles_overlap plane, by scene id.
 void launch_visible_mask(const uint32_t* tiles, uint8_t* mask, uint32_t n, bool accumulate, hipStream_t s);
 
+// Adaptive density control (gs3d_hip.h; gs_densify.hip).
+// gs_accumulate_densify_stats: the three statistics of the Gaussians with tiles[id] != 0, by scene id; rec: the frame's records
+// (the radius), width, height: the frame's.  One lane per Gaussian, no atomics.
+void launch_densify_stats(const uint32_t* tiles, const AttrRecord* rec, const gs_densify_stats& st, uint32_t n, uint32_t width,
+                          uint32_t height, hipStream_t s);
+// gs_densify_plan: the two offset arrays into in.scratch ([0, n] and [n + 1, 2 n + 1]).  parts: 2 * densify_partitions(n) words of
+// the caller's for the partitions' sums.  Three launches on `s`; nothing is synchronised here.
+size_t densify_partitions(uint32_t n);
+void launch_densify_plan(const gs_densify_input& in, uint32_t n, uint32_t* parts, hipStream_t s);
+// gs_densify_apply: the output arrays from the inputs and the offsets the plan left in in.scratch; a workgroup per
+// GS_DENSIFY_BLOCK parents.  The caller has checked that the offsets end in out.n_out and out.n_noise.
+void launch_densify_apply(const gs_densify_input& in, uint32_t n, const gs_densify_output& out, hipStream_t s);
+
 }  // namespace gs

@@ -844,7 +844,8 @@ struct gs_renderer {
     }
 
     // What the passes over the last frame's tile lists do after their own argument checks (gs_accumulate_contributions,
-    // gs_blend_features, gs_lift_pixels, gs_blend_backward, gs_project_backward, gs_camera_backward, gs_visible_mask), in this order: queued frames retire (an overflowed one is re-run: the lists are the last
+    // gs_blend_features, gs_lift_pixels, gs_blend_backward, gs_project_backward, gs_camera_backward, gs_visible_mask,
+    // gs_accumulate_densify_stats), in this order: queued frames retire (an overflowed one is re-run: the lists are the last
     // frame's, complete); without a frame the call is refused; with nothing asked for it is done; otherwise launch(lists, stream)
     // enqueues the pass over the frame's own lists on the last frame's stream and the call waits for it.
     template <class Launch>
@@ -1410,6 +1411,20 @@ int gs_visible_mask(gs_renderer* r, uint8_t* mask, int accumulate) {
         r->over_last_frame(false, [&](const gs::TileLists&, hipStream_t s) {
             r->rebuild_planes();  // visibility is the tiles tap's answer, as in gs_project_backward
             gs::launch_visible_mask(r->last_frame.set->tiles.p, mask, static_cast<uint32_t>(r->scene->n), accumulate != 0, s);
+        });
+    });
+}
+
+int gs_accumulate_densify_stats(gs_renderer* r, const gs_densify_stats* st) {
+    return guarded([&] {
+        if (!r || !st) throw Error(GS_ERR_INVALID, "null argument");
+        // (all by the members' values alone: nothing is dereferenced and no device is touched before they pass)
+        if (!st->d_uv || !st->grad_sum || !st->count || !st->max_radius) throw Error(GS_ERR_INVALID, "null member: d_uv, grad_sum, count and max_radius are all required");
+        require_aligned(8, {{st->d_uv, "d_uv"}, {st->grad_sum, "grad_sum"}});
+        require_aligned(4, {{st->count, "count"}, {st->max_radius, "max_radius"}});
+        r->over_last_frame(false, [&](const gs::TileLists& lists, hipStream_t s) {
+            r->rebuild_planes();  // visibility is the tiles tap's answer, as in gs_project_backward
+            gs::launch_densify_stats(r->last_frame.set->tiles.p, lists.rec, *st, static_cast<uint32_t>(r->scene->n), lists.width, lists.height, s);
         });
     });
 }

@@ -247,6 +247,51 @@ void check_device_arrays_out(const gs_device_arrays_out* a) {
         if (reinterpret_cast<uintptr_t>(m.p) % 4 != 0) throw Error(GS_ERR_INVALID, std::string("device array `") + m.name + "` is not 4-byte aligned");
 }
 
+// What gs_densify_plan and gs_densify_apply refuse about the model, its statistics and the rule before any device is touched.
+void check_densify_input(const gs_densify_input* in, uint64_t n) {
+    if (!in) throw Error(GS_ERR_INVALID, "null argument");
+    if (n >= kMaxGaussians) throw Error(GS_ERR_INVALID, "too many Gaussians (limit 2^31)");
+    check_device_arrays(&in->params, n, true);
+    if (n && (!in->grad_sum || !in->count || !in->max_radius)) throw Error(GS_ERR_INVALID, "null statistic: grad_sum, count and max_radius are all required");
+    if (n && !in->scratch) throw Error(GS_ERR_INVALID, "null scratch: 2 (n + 1) uint32 are required");
+    if (reinterpret_cast<uintptr_t>(in->grad_sum) % 8 != 0) throw Error(GS_ERR_INVALID, "grad_sum is not 8-byte aligned");
+    if (reinterpret_cast<uintptr_t>(in->count) % 4 != 0) throw Error(GS_ERR_INVALID, "count is not 4-byte aligned");
+    if (reinterpret_cast<uintptr_t>(in->max_radius) % 4 != 0) throw Error(GS_ERR_INVALID, "max_radius is not 4-byte aligned");
+    if (reinterpret_cast<uintptr_t>(in->scratch) % 4 != 0) throw Error(GS_ERR_INVALID, "scratch is not 4-byte aligned");
+    const gs_densify_rule& r = in->rule;
+    const struct {
+        double v;
+        const char* name;
+    } members[5] = {{r.grad_threshold, "grad_threshold"}, {r.dense_extent, "dense_extent"}, {r.min_opacity, "min_opacity"},
+                    {r.max_screen_radius, "max_screen_radius"}, {r.max_world_scale, "max_world_scale"}};
+    for (const auto& m : members)
+        if (std::isnan(m.v)) throw Error(GS_ERR_INVALID, std::string("rule member `") + m.name + "` is NaN");
+}
+
+// What gs_densify_apply refuses about its outputs before any device is touched.
+void check_densify_output(const gs_densify_input* in, uint64_t n, const gs_densify_output* out) {
+    if (!out) throw Error(GS_ERR_INVALID, "null argument");
+    if (out->n_out > 2 * n || out->n_out >= kMaxGaussians) throw Error(GS_ERR_INVALID, "n_out is not a plan's: more than 2 n rows, or 2^31 and beyond");
+    if (out->n_noise > n || 2 * out->n_noise > out->n_out) throw Error(GS_ERR_INVALID, "n_noise is not a plan's: more than n, or more than n_out / 2");
+    if (out->n_noise && !out->noise) throw Error(GS_ERR_INVALID, "noise is null with n_noise != 0");
+    if (reinterpret_cast<uintptr_t>(out->noise) % 4 != 0) throw Error(GS_ERR_INVALID, "noise is not 4-byte aligned");
+    check_device_arrays_out(&out->params);
+    if (out->params.sh_rest_coeffs != in->params.sh_rest_coeffs) throw Error(GS_ERR_INVALID, "the output's sh_rest_coeffs is not the input's");
+    const float* const params[6] = {out->params.means, out->params.log_scales, out->params.quats, out->params.opacity_logits, out->params.sh_dc, out->params.sh_rest};
+    static const char* const names[6] = {"means", "log_scales", "quats", "opacity_logits", "sh_dc", "sh_rest"};
+    for (int g = 0; g < 6; ++g) {
+        const bool needed = g < 5 || in->params.sh_rest_coeffs != 0;
+        if (out->n_out && needed && !params[g]) throw Error(GS_ERR_INVALID, std::string("output array `") + names[g] + "` is null");
+        const int given = (out->exp_avg[g] != nullptr) + (out->exp_avg_sq[g] != nullptr);
+        const int given_out = (out->out_exp_avg[g] != nullptr) + (out->out_exp_avg_sq[g] != nullptr);
+        const std::string name = std::string("group `") + names[g] + "`";
+        if (given == 1 || given_out == 1 || (out->n_out && given != given_out)) throw Error(GS_ERR_INVALID, name + " has some but not all of its four moment pointers");
+        if (given && !needed) throw Error(GS_ERR_INVALID, name + " has moments with sh_rest_coeffs == 0");
+        for (const float* p : {out->exp_avg[g], out->exp_avg_sq[g], static_cast<const float*>(out->out_exp_avg[g]), static_cast<const float*>(out->out_exp_avg_sq[g])})
+            if (reinterpret_cast<uintptr_t>(p) % 4 != 0) throw Error(GS_ERR_INVALID, name + ": a moment pointer is not 4-byte aligned");
+    }
+}
+
 void export_records_streamed(const gs_scene* s, uint64_t first, uint64_t count, const std::function<void(const float*, uint64_t)>& sink) {
     if (count == 0) return;
     HIP_CHECK(hipSetDevice(s->device));
@@ -405,6 +450,47 @@ int gs_scene_adam_step(gs_scene* s, const gs_adam_step* a, void* stream) {
         if (!s) throw Error(GS_ERR_INVALID, "null argument");
         if (!any || s->n == 0) return;
         adam_step(s, *a, static_cast<hipStream_t>(stream));
+    });
+}
+
+int gs_densify_plan(const gs_densify_input* in, uint64_t n, int device, void* stream, uint64_t* n_out, uint64_t* n_noise) {
+    return guarded([&] {
+        check_densify_input(in, n);
+        if (!n_out || !n_noise) throw Error(GS_ERR_INVALID, "null argument");
+        *n_out = *n_noise = 0;
+        if (n == 0) return;
+        select_device(device);
+        const hipStream_t st = static_cast<hipStream_t>(stream);
+        const uint32_t rows = static_cast<uint32_t>(n);
+        DevBuf<uint32_t> parts;  // the partitions' sums: n / 1024 words
+        parts.alloc(2 * gs::densify_partitions(rows));
+        gs::launch_densify_plan(*in, rows, parts.p, st);
+        HIP_CHECK(hipGetLastError());
+        uint32_t totals[2] = {0, 0};
+        HIP_CHECK(hipMemcpyAsync(&totals[0], in->scratch + n, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(&totals[1], in->scratch + 2 * n + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        if (totals[0] >= kMaxGaussians) throw Error(GS_ERR_INVALID, "the densified model would have more than 2^31 - 1 rows");
+        *n_out = totals[0], *n_noise = totals[1];
+    });
+}
+
+int gs_densify_apply(const gs_densify_input* in, uint64_t n, const gs_densify_output* out, int device, void* stream) {
+    return guarded([&] {
+        check_densify_input(in, n);
+        check_densify_output(in, n, out);
+        if (n == 0 || out->n_out == 0) return;
+        select_device(device);
+        const hipStream_t st = static_cast<hipStream_t>(stream);
+        uint32_t totals[2] = {0, 0};
+        HIP_CHECK(hipMemcpyAsync(&totals[0], in->scratch + n, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(&totals[1], in->scratch + 2 * n + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        if (totals[0] != out->n_out || totals[1] != out->n_noise)
+            throw Error(GS_ERR_INVALID, "n_out / n_noise are not what the plan left in scratch: run gs_densify_plan on these inputs first");
+        gs::launch_densify_apply(*in, static_cast<uint32_t>(n), *out, st);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipStreamSynchronize(st));
     });
 }
 

@@ -165,8 +165,8 @@ typedef struct {
  * GS_ERR_INVALID: a null argument, n >= 2^31, sh_rest_coeffs not in {0, 3, 8, 15}, a misaligned pointer. */
 int gs_scene_from_device_arrays(const gs_device_arrays* a, uint64_t n, int device, void* stream, gs_scene** out);
 /* Overwrite Gaussians [first, first + count) of a scene of ANY origin from such arrays (row i = Gaussian first + i), in
- * place: the live view of a training run.  The Gaussian count is fixed (after densification: a new scene and a new
- * renderer).  A NULL member means "keep what the scene holds"; sh_rest == NULL keeps the higher bands whatever
+ * place: the live view of a training run.  The Gaussian count is fixed (a densification changes it: gs_densify_plan and
+ * gs_densify_apply, below, make the new arrays on the device).  A NULL member means "keep what the scene holds"; sh_rest == NULL keeps the higher bands whatever
  * sh_rest_coeffs says, a non-NULL sh_rest replaces all of them (zero beyond sh_rest_coeffs).  count == 0 or no member at
  * all: a successful no-op.  Everything derived from what changed is redone on `stream` before the call returns (it
  * synchronises the stream): cov3D, the alpha cuts and the opacity flag behind exp mode 3, the binary16 SH block of a
@@ -936,6 +936,120 @@ typedef struct {
     int zero_grads;                 /* nonzero: the gradient rows that were consumed are set to +0.0 */
 } gs_adam_step;
 int gs_scene_adam_step(gs_scene* s, const gs_adam_step* a, void* stream);
+
+/* ---- adaptive density control: the statistic, the decision and the compaction of a trainer's model, on the device ----------
+ * What a 3DGS trainer does every hundred iterations -- clone the small Gaussians with a large screen-space gradient, split the
+ * large ones, prune the transparent and the oversized -- over the six PLY-domain arrays of gs_device_arrays and the twelve
+ * moment arrays of gs_scene_adam_step.  Three calls (gs_densify.hip); the new scene is then gs_scene_from_device_arrays of the
+ * new arrays, with a new renderer.  No reference counterpart.  The unit is built with -ffp-contract=off: every operation below
+ * is rounded on its own, in the order written, and THE CONTRACT OF ALL THREE CALLS IS A BIT PATTERN
+ * (tests/densify_reference.py restates them in numpy).  INTEGRATION.md, 3l.
+ *
+ * 1. THE STATISTIC of the LAST frame, for every Gaussian id with stage("tiles")[id] != 0, with (gx, gy) = d_uv[id] -- the row
+ * gs_blend_backward summed -- and W, H the width and height of that frame; binary64:
+ *     grad_sum[id]   += sqrt(((gx * (W / 2)) * (gx * (W / 2))) + ((gy * (H / 2)) * (gy * (H / 2))))      W / 2, H / 2 exact
+ *     count[id]      += 1
+ *     max_radius[id]  = max(max_radius[id], stage("radius")[id])       binary32; the new value is taken where it is GREATER
+ * The norm is that of the Inria trainer's viewspace_point_tensor.grad, whose dL_dmean2D carries the same 0.5 W and 0.5 H (its
+ * screen position is in NDC): the customary threshold 2e-4 means here what it means there.  One lane per Gaussian, no atomics:
+ * the same bits every call.  An invisible Gaussian's three elements are neither read nor written.  Scene ids, inputs and the
+ * contents of the three arrays COMPLETE before the call, the renderer's own NON-BLOCKING stream, the synchronisation (queued
+ * frames retire, an overflowed frame is re-run, the call returns when the arrays are written), "no frame rendered yet" and
+ * the behaviour after a refused or failed gs_render: all as gs_visible_mask states them.
+ * GS_ERR_INVALID, checked before any device is touched: r or s NULL; a NULL member; d_uv or grad_sum not 8-byte aligned, count
+ * or max_radius not 4-byte aligned (judged by their values alone). */
+typedef struct {
+    const double* d_uv;    /* [N][2]  gs_blend_backward's sum for the last frame                           */
+    double*   grad_sum;    /* [N]     ADDED to                                                              */
+    uint32_t* count;       /* [N]     frames that saw the Gaussian, incremented                             */
+    float*    max_radius;  /* [N]     the largest screen radius (pixels) any of those frames gave it         */
+} gs_densify_stats;
+int gs_accumulate_densify_stats(gs_renderer* r, const gs_densify_stats* s);
+
+/* 2. THE DECISION, per parent i of a model of n rows.  With ls, logit, (grad_sum, count, max_radius) its rows:
+ *     avg   = count != 0 ? grad_sum / (double)count : 0.0                  binary64; grad_sum is not read where count == 0
+ *     sg_k  = gs_scene_from_device_arrays' binary32 activation of ls_k (libm's expf restated), k = 0, 1, 2
+ *     s     = sg_0;  if (sg_1 > s) s = sg_1;  if (sg_2 > s) s = sg_2;      converted exactly to binary64
+ *     o     = 1.0f / (1.0f + expf(-logit))                                 the same ingest's binary32, converted exactly
+ *     grow  = avg >= grad_threshold
+ *     clone = grow && s <= dense_extent        split = grow && s > dense_extent        keep otherwise
+ * (a NaN compares false everywhere: a NaN average keeps, a NaN s neither clones nor splits, a NaN is never pruned).
+ * THE SEMANTICS are the sequence trainers run: append one copy of every clone; append two children of every split and remove
+ * the split parent; then prune over the EXTENDED set, whose statistics are zero for the appended rows (gsplat's default
+ * strategy).  A row is pruned where its o < min_opacity, or max_screen_radius > 0 and its own max_radius > max_screen_radius
+ * (only an original has a radius), or max_world_scale > 0 and its own s > max_world_scale -- for a split child the s of its NEW
+ * log-scales (below).  A clone's copy shares o and s with its original; the two children of a split share o and their new s:
+ * THEY SHARE THEIR PRUNE DECISION, so a split parent yields 0 or 2 rows, a cloned one 0, 1 (the copy, where only the radius
+ * pruned the original) or 2, a kept one 0 or 1.
+ *     row_offset[0 .. n]   = the exclusive prefix sum of those yields              scratch[0 .. n]
+ *     noise_offset[0 .. n] = ... of "is a split parent whose children survive"    scratch[n + 1 .. 2 n + 1]
+ * *n_out = row_offset[n] and *n_noise = noise_offset[n].  The scan is deterministic: a workgroup per GS_DENSIFY_PARTITION
+ * parents reduces, one workgroup scans the partitions' sums in turns of 256 with a carry, a workgroup per partition scans its
+ * own parents from its base (integers: the result has one value).  A model that would grow beyond 2^31 - 1 rows is refused
+ * with GS_ERR_INVALID after the scan (the scratch is then written, nothing else is).
+ * stream: a hipStream_t (NULL: the default stream); the work is enqueued on it behind what the caller has enqueued there and
+ * the call returns after synchronising it.  All pointers are device pointers on `device`.  n == 0: success, both counts 0,
+ * nothing is launched and the scratch is not touched.
+ * GS_ERR_INVALID, checked before any device is touched: in, n_out or n_noise NULL; n >= 2^31; with n != 0: a NULL parameter
+ * array (sh_rest only with sh_rest_coeffs != 0), statistic array or scratch; sh_rest_coeffs not in {0, 3, 8, 15}; a float or
+ * uint32 pointer that is not 4-byte aligned, grad_sum not 8-byte aligned; a rule member that is NaN. */
+#define GS_DENSIFY_PARTITION 2048u   /* parents per workgroup of the plan's scan */
+#define GS_DENSIFY_BLOCK 256u        /* parents per workgroup of the apply     */
+#define GS_DENSIFY_LOG_1_6 0x1.e148a1a2726cep-2   /* the binary64 nearest log(1.6) */
+typedef struct {
+    double grad_threshold;     /* on the average screen-space gradient norm (customarily 2e-4)             */
+    double dense_extent;       /* percent_dense * scene extent: at most this large clones, larger splits   */
+    double min_opacity;        /* prune below                                                              */
+    double max_screen_radius;  /* prune above, pixels; <= 0: off                                           */
+    double max_world_scale;    /* prune above; <= 0: off                                                   */
+} gs_densify_rule;
+typedef struct {
+    gs_device_arrays params;     /* the model, n rows each                                                 */
+    const double*   grad_sum;    /* [n] the three arrays gs_accumulate_densify_stats keeps                 */
+    const uint32_t* count;
+    const float*    max_radius;
+    gs_densify_rule rule;
+    uint32_t* scratch;           /* [2 (n + 1)] written by the plan, read by the apply                     */
+} gs_densify_input;
+int gs_densify_plan(const gs_densify_input* in, uint64_t n, int device, void* stream, uint64_t* n_out, uint64_t* n_noise);
+
+/* 3. THE COMPACTION: the new model and its Adam moments from the old ones and the plan's two offset arrays.  Output rows are
+ * ordered BY PARENT id, a parent's survivors adjacent, the original before its copy, child 0 before child 1 (trainers append:
+ * survivors, then clones, then splits; parent order keeps ids spatially coherent, which k_adam_step's early exit and the
+ * scene's Morton read order profit from).  Each output row:
+ *   - a kept original, a clone's original: every parameter and both moments are copied bit for bit;
+ *   - a clone's copy: parameters copied bit for bit, moments +0.0;
+ *   - child c in {0, 1} of a split parent with ordinal j = noise_offset[i]: quats, opacity_logits, sh_dc, sh_rest copied,
+ *     moments +0.0, and with t = noise[j][c] (binary32 -> binary64 exactly), all binary64:
+ *         ls'_k = fl32(ls_k - GS_DENSIFY_LOG_1_6)
+ *         (w, x, y, z) = q_e * inv, e = 0..3, binary32: inv = 1.0f / sqrtf((q_0 q_0 + q_1 q_1) + (q_2 q_2 + q_3 q_3)), the
+ *                        ingest's normalisation; converted exactly
+ *         R00 = 1 - 2 ((y y) + (z z))   R01 = 2 ((x y) - (w z))       R02 = 2 ((x z) + (w y))
+ *         R10 = 2 ((x y) + (w z))       R11 = 1 - 2 ((x x) + (z z))   R12 = 2 ((y z) - (w x))
+ *         R20 = 2 ((x z) - (w y))       R21 = 2 ((y z) + (w x))       R22 = 1 - 2 ((x x) + (y y))
+ *         d_k = sg_k * t_k              (exact: two binary32 factors)
+ *         m'_r = fl32(m_r + (((R_r0 * d_0) + (R_r1 * d_1)) + (R_r2 * d_2)))
+ *     The kernel holds no random number generator: the result is a pure function of its inputs.
+ * A NaN in a parent's statistic or parameters reaches that parent's rows only.  The inputs keep their bits.
+ * A moment pair of a group may be NULL (both in, both out): that group has no moments to carry.  Every output array has n_out
+ * rows and must not overlap an input.  n_out and n_noise are the plan's: the call reads row_offset[n] and noise_offset[n] back
+ * and refuses with GS_ERR_INVALID, before anything is written, when they differ.  n_out == 0 or n == 0: success, nothing is
+ * launched.  stream and synchronisation: as gs_densify_plan.
+ * GS_ERR_INVALID, checked before any device is touched: in or out NULL; everything gs_densify_plan refuses about `in` and n;
+ * n_out > 2 n or >= 2^31, n_noise > n or 2 n_noise > n_out; noise NULL with n_noise != 0, or not 4-byte aligned; with
+ * n_out != 0: a NULL output parameter array (sh_rest only with sh_rest_coeffs != 0), a group with some but not all of its four
+ * moment pointers; one moment of an input or of an output pair without the other; moments of sh_rest with sh_rest_coeffs == 0;
+ * the output's sh_rest_coeffs not the input's; a pointer that is not 4-byte aligned. */
+typedef struct {
+    const float* exp_avg[6];         /* in, [n][...]: means, log_scales, quats, opacity_logits, sh_dc, sh_rest; nullable */
+    const float* exp_avg_sq[6];
+    const float* noise;              /* [n_noise][2][3] standard-normal draws, the caller's                              */
+    uint64_t n_noise, n_out;         /* what gs_densify_plan returned                                                   */
+    gs_device_arrays_out params;     /* out, [n_out][...]; sh_rest_coeffs must equal the input's                         */
+    float* out_exp_avg[6];           /* out, [n_out][...]: given exactly where the input pair is                         */
+    float* out_exp_avg_sq[6];
+} gs_densify_output;
+int gs_densify_apply(const gs_densify_input* in, uint64_t n, const gs_densify_output* out, int device, void* stream);
 /* Test hook (tests/test_gpu_expf.py): evaluate the blend's exp() implementations ON THE DEVICE over the binary32 values with
  * bit patterns [first_bits, first_bits + count) (the negative floats run from 0x80000000 = -0 to 0xFF800000 = -inf).
  * block_sums[j] = sum over block j of 2^20 consecutive patterns of  bits(expf(x)) * ((bits(x) * 0x9E3779B1) | 1)  mod 2^64,
