@@ -189,7 +189,8 @@ def backward(pos, scale, quat, opacity, sh, uniforms, visible, red_flows, colour
     record.  visible, red_flows: bool [n], the frame's decisions.  colour [n][3], opacity_grad [n], conic [n][3], uv [n][2]:
     float64 input gradients, None = zeros.  Returns dict(means, log_scales, quats, opacity_logits, sh_dc, sh_rest: float64 sums of
     the shapes gs_project_grads documents (culled rows 0); A = {name: magnitudes}; k = {name: the counted roundings};
-    visible; binds = bool [n][2]; det_raw = float64 [n] (NaN where culled); margin = {"clamp": |tx/tz| / lim, "r": rgb0};
+    visible; binds = bool [n][2]; det_raw = float64 [n] (NaN where culled); det_raw_bound = float64 [n], its counted roundings times
+    2^-53 times its magnitude (how far a binary64 evaluation of det_raw may lie from the exact one; NaN where culled); margin = {"clamp": |tx/tz| / lim, "r": rgb0};
     record = {field of RECORD: (value [n][c], magnitude [n][c], counted roundings)}, the forward value of F (NaN where culled): uv,
     the conic's three numbers, the opacity after the antialiased factor, rgb before and after red's clamp -- each within
     count 2^-53 magnitude of exact, by the rules above."""
@@ -262,10 +263,10 @@ def backward(pos, scale, quat, opacity, sh, uniforms, visible, red_flows, colour
     g_det = -(_sum([gc00 * c00, gc01 * c01, gc11 * c11]) / det)
     g_o = V(g_op)
     g_detraw = None
-    det_raw_full = np.full(n, np.nan)
+    det_raw_full, det_raw_bound = np.full(n, np.nan), np.full(n, np.nan)
     if antialiased:
         det_raw = cov00 * cov11 - cov01 * cov01
-        det_raw_full[idx] = det_raw.v
+        det_raw_full[idx], det_raw_bound[idx] = det_raw.v, det_raw.k * U53 * det_raw.m
         pos_raw = det_raw.v > 0.0
         safe = V(np.where(pos_raw, det_raw.v, 1.0), np.where(pos_raw, det_raw.m, 1.0), det_raw.k)
         comp = (safe / det).sqrt()
@@ -379,7 +380,7 @@ def backward(pos, scale, quat, opacity, sh, uniforms, visible, red_flows, colour
         _, _, _, lim = clamp_branches(pos, u)
         lim_ratio[idx] = np.abs(ratio[idx].astype(f64)) / lim.astype(f64)[None, :]
     out.update(A=mags, k=counts, visible=np.asarray(visible, bool), binds=binds_all & np.asarray(visible, bool)[:, None],
-               det_raw=det_raw_full, margin=dict(clamp=lim_ratio, r=rgb0), record=record)
+               det_raw=det_raw_full, det_raw_bound=det_raw_bound, margin=dict(clamp=lim_ratio, r=rgb0), record=record)
     return out
 
 
