@@ -24,7 +24,7 @@ BLOB_PLANES = 59
 
 # the device code of libgs3d_hip.so: one translation unit per stage + the shared device headers
 KERNEL_SOURCES = ("gs_device.h", "gs_bin.h", "gs_tile_cull.h", "gs_scene.hip", "gs_preprocess.hip", "gs_radix.hip", "gs_bin_l1.hip", "gs_bin_l2.hip",
-                  "gs_blend.hip", "gs_contrib.hip", "gs_features.hip", "gs_lift.hip", "gs_backward.hip", "gs_project_backward.hip", "gs_camera_backward.hip", "gs_loss.hip", "gs_optim.hip", "gs_densify.hip", "gs_project_chain.h",
+                  "gs_blend.hip", "gs_contrib.hip", "gs_features.hip", "gs_lift.hip", "gs_backward.hip", "gs_project_backward.hip", "gs_camera_backward.hip", "gs_loss.hip", "gs_optim.hip", "gs_densify.hip", "gs_knn.hip", "gs_knn_rules.h", "gs_project_chain.h",
                   "gs_wave_f64.h", "gs_kernels.h")
 
 
@@ -63,7 +63,7 @@ SYMBOLS = ["gs_last_error", "gs_device_count", "gs_read_ply", "gs_activate_recor
            "gs_deactivate_vertices", "gs_write_ply", "gs_scene_to_device_arrays", "gs_scene_download_records", "gs_scene_save_ply",
            "gs_scene_destroy", "gs_renderer_create", "gs_renderer_destroy", "gs_camera_uniforms",
            "gs_render", "gs_render_host", "gs_synchronize", "gs_set_timing", "gs_set_frames_in_flight", "gs_set_sort_path", "gs_set_exp_mode", "gs_set_graph_mode", "gs_set_blend_lockstep", "gs_get_blend_lockstep", "gs_set_level1_fused", "gs_get_level1_fused", "gs_set_tile_cull", "gs_get_tile_cull", "gs_get_listed_instances", "gs_set_blend_contraction", "gs_set_antialiased", "gs_get_antialiased", "gs_get_timing_totals",
-           "gs_get_frame_intervals", "gs_get_stats", "gs_poll_stats", "gs_debug_download", "gs_accumulate_contributions", "gs_blend_features", "gs_lift_pixels", "gs_blend_backward", "gs_project_backward", "gs_camera_backward", "gs_camera_uniforms_backward", "gs_photometric_loss", "gs_visible_mask", "gs_scene_adam_step", "gs_accumulate_densify_stats", "gs_densify_plan", "gs_densify_apply", "gs_debug_expf_scan", "gs_debug_alpha_cut_scan", "gs_renderer_stream",
+           "gs_get_frame_intervals", "gs_get_stats", "gs_poll_stats", "gs_debug_download", "gs_accumulate_contributions", "gs_blend_features", "gs_lift_pixels", "gs_blend_backward", "gs_project_backward", "gs_camera_backward", "gs_camera_uniforms_backward", "gs_photometric_loss", "gs_visible_mask", "gs_scene_adam_step", "gs_accumulate_densify_stats", "gs_densify_plan", "gs_densify_apply", "gs_knn_scratch_bytes", "gs_knn_dist2", "gs_debug_expf_scan", "gs_debug_alpha_cut_scan", "gs_renderer_stream",
            "gs_dist_unique_id", "gs_dist_create", "gs_dist_rank", "gs_dist_world", "gs_dist_pose_count",
            "gs_dist_broadcast_scene", "gs_dist_broadcast_scene_ex", "gs_dist_verify", "gs_dist_destroy"]
 
@@ -805,6 +805,93 @@ def densify(scene, params, rule, stats, state=None, noise=None, stream=None):
         info["parents_single"] = int((rows_of == 1).sum())
         info["parents_cloned"] = int(((rows_of == 2) & ~split).sum())
     return new_params, new_state, info
+
+
+KNN_MAX_K = 8   # GS_KNN_MAX_K
+KNN_BOX = 256   # GS_KNN_BOX: sorted points per box of the search = rows of box_visits per 256 points
+SH_C0 = 0.28209479177387814  # the DC basis function: colour = 0.5 + SH_C0 sh_dc
+
+
+def _device_index(t):
+    """The GPU a tensor says it is on (0 where it does not say: _tensor_rows then judges the rest)."""
+    index = getattr(getattr(t, "device", None), "index", None)
+    return int(index) if isinstance(index, int) and not isinstance(index, bool) else 0
+
+
+def knn_dist2(points, k=3, mean=True, dist2=False, visits=False, stream=None):
+    """The squared distances of every point of a cloud to its k nearest neighbours, exact in binary32 (gs_knn_dist2;
+    INTEGRATION.md, 3m): what a trainer derives its initial scales from (simple_knn.distCUDA2 for k = 3).
+    points: float32 (n, 3) on a GPU, every coordinate finite (ValueError otherwise: one synchronising check, nothing is launched).
+    Returns a dict of tensors on the points' device, allocated here: 'mean_dist2' float32 (n,) where `mean`, 'dist2' float32 (n, k),
+    ascending, +inf beyond n - 1 neighbours, where `dist2`, 'box_visits' int32 (ceil(n / KNN_BOX),) where `visits` -- how many
+    boxes of KNN_BOX Morton-sorted points each query box had to scan.  The values are those of the brute force over all pairs, bit
+    for bit (tests/knn_reference.py).  Waits for torch's current stream first; runs on `stream` (None: torch's current stream) and
+    returns synchronised."""
+    dev = _device_index(points)
+    n = _tensor_rows("points", points, (3,), dev)
+    if isinstance(k, bool) or not isinstance(k, int):
+        raise TypeError(f"k must be an int, not {type(k).__name__}")
+    if not 1 <= k <= KNN_MAX_K:
+        raise ValueError(f"k = {k} is outside [1, {KNN_MAX_K}]")
+    if not (mean or dist2 or visits):
+        raise ValueError("nothing asked for: mean, dist2 and visits are all false")
+    import torch
+    L = lib()
+    call, scratch_bytes = L.gs_knn_dist2, L.gs_knn_scratch_bytes
+    scratch_bytes.restype, scratch_bytes.argtypes = C.c_uint64, [C.c_uint64]
+    if not bool(torch.isfinite(points).all()):   # (synchronises: the points are complete from here on)
+        raise ValueError("points: a coordinate is NaN or infinite")
+    _complete_callers_work(points)
+    tdev = _torch_device(dev)
+    out = {}
+    if mean:
+        out["mean_dist2"] = torch.empty((n,), dtype=torch.float32, device=tdev)
+    if dist2:
+        out["dist2"] = torch.empty((n, k), dtype=torch.float32, device=tdev)
+    if visits:
+        out["box_visits"] = torch.empty(((n + KNN_BOX - 1) // KNN_BOX,), dtype=torch.int32, device=tdev)
+    if n == 0:
+        return out
+    scratch = torch.empty((int(scratch_bytes(C.c_uint64(n))),), dtype=torch.uint8, device=tdev)
+    pointer = lambda name: C.c_void_p(out[name].data_ptr()) if name in out else None
+    _check(call(C.c_void_p(points.data_ptr()), C.c_uint64(n), C.c_int(k), pointer("mean_dist2"), pointer("dist2"), pointer("box_visits"),
+                C.c_void_p(scratch.data_ptr()), C.c_uint64(scratch.numel()), C.c_int(dev), _stream_handle(stream)))
+    return out
+
+
+def init_from_points(points, colours=None, k=3, opacity=0.1, sh_degree=3, min_dist2=1e-7, stream=None):
+    """A model from a point cloud, as the Inria trainer's create_from_pcd makes it: the six float32 tensors
+    under PARAMETER_NAMES, on the points' device, ready for Scene.from_tensors(**params) and Adam.
+    means = points; log_scales = log(sqrt(clamp_min(mean_dist2, min_dist2))) on all three axes, mean_dist2 = knn_dist2(points, k);
+    quats = (1, 0, 0, 0); opacity_logits = log(opacity / (1 - opacity)); sh_dc = (colours - 0.5) / SH_C0 with colours float32
+    (n, 3) in [0, 1] (None: 0.5, i.e. zeros); sh_rest = zeros of (n, SH_REST_COEFFS[sh_degree], 3).  The distances are the
+    kernels'; the rest is plain float32 torch arithmetic on the device."""
+    if sh_degree not in SH_REST_COEFFS:
+        raise ValueError(f"sh_degree = {sh_degree!r} is not one of {sorted(SH_REST_COEFFS)}")
+    if not 0.0 < float(opacity) < 1.0:
+        raise ValueError(f"opacity = {opacity!r} is not inside (0, 1)")
+    if not float(min_dist2) > 0.0:
+        raise ValueError(f"min_dist2 = {min_dist2!r} is not positive")
+    dev = _device_index(points)
+    n = _tensor_rows("points", points, (3,), dev)
+    if colours is not None and _tensor_rows("colours", colours, (3,), dev) != n:
+        raise ValueError(f"colours have {int(colours.shape[0])} rows, the points {n}")
+    import math
+    import torch
+    mean_dist2 = knn_dist2(points, k=k, stream=stream)["mean_dist2"]
+    tdev = points.device
+    means = points.reshape(n, 3).clone()
+    log_scales = torch.log(torch.sqrt(torch.clamp_min(mean_dist2, float(min_dist2)))).reshape(n, 1).repeat(1, 3)
+    quats = torch.zeros((n, 4), dtype=torch.float32, device=tdev)
+    quats[:, 0] = 1.0
+    logit = math.log(float(opacity) / (1.0 - float(opacity)))
+    opacity_logits = torch.full((n,), logit, dtype=torch.float32, device=tdev)
+    if colours is None:
+        sh_dc = torch.zeros((n, 3), dtype=torch.float32, device=tdev)
+    else:
+        sh_dc = (colours.reshape(n, 3) - 0.5) / SH_C0
+    sh_rest = torch.zeros((n, SH_REST_COEFFS[sh_degree], 3), dtype=torch.float32, device=tdev)
+    return dict(zip(PARAMETER_NAMES, (means, log_scales, quats, opacity_logits, sh_dc, sh_rest)))
 
 
 class Scene:

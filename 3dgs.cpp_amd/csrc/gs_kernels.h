@@ -1,4 +1,4 @@
-// gs_kernels.h -- launch wrappers of the gfx950 kernels (gs_scene / gs_preprocess / gs_radix / gs_bin_l1 / gs_bin_l2 / gs_blend / gs_contrib / gs_features / gs_lift / gs_backward / gs_project_backward / gs_camera_backward / gs_loss / gs_optim .hip).
+// gs_kernels.h -- launch wrappers of the gfx950 kernels (gs_scene / gs_preprocess / gs_radix / gs_bin_l1 / gs_bin_l2 / gs_blend / gs_contrib / gs_features / gs_lift / gs_backward / gs_project_backward / gs_camera_backward / gs_loss / gs_optim / gs_densify / gs_knn .hip).
 // Host-side declarations only; everything takes raw device pointers + a stream.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -361,5 +361,27 @@ void launch_densify_plan(const gs_densify_input& in, uint32_t n, uint32_t* parts
 // gs_densify_apply: the output arrays from the inputs and the offsets the plan left in in.scratch; a workgroup per
 // GS_DENSIFY_BLOCK parents.  The caller has checked that the offsets end in out.n_out and out.n_noise.
 void launch_densify_apply(const gs_densify_input& in, uint32_t n, const gs_densify_output& out, hipStream_t s);
+
+// gs_knn_dist2 (gs3d_hip.h; gs_knn.hip, gs_knn_rules.h): the caller's scratch, cut up.  Every segment starts on 16 bytes of the
+// scratch's first 16-byte boundary (knn_scratch_bytes counts the slack for a scratch that is only 4-byte aligned).
+struct KnnBuffers {
+    float4* sorted;          // [n]  the points in Morton order: x, y, z, bits of the id
+    float4* boxes;           // [2 boxes]  lo.xyz, hi.xyz of every GS_KNN_BOX consecutive sorted points
+    uint32_t* keys[2];       // [n] each: the radix passes' ping-pong (codes)
+    uint32_t* vals[2];       // [n] each: (ids); the order ends in vals[0]
+    uint32_t* block_hist;    // [256][radix blocks]
+    uint32_t* digit_total;   // [256]
+    float* bbox_parts;       // [kKnnBoundParts][8]  stage one of the bounding box
+    float* bbox;             // [8]  lo.xyz, 0, hi.xyz, 0
+    uint32_t* count;         // [1]  n, where the radix passes read it
+};
+constexpr uint32_t kKnnBoundParts = 1024;
+inline uint32_t knn_boxes(uint32_t n) { return (uint32_t)(((uint64_t)n + GS_KNN_BOX - 1) / GS_KNN_BOX); }
+size_t knn_scratch_bytes(uint64_t n);
+KnnBuffers knn_buffers(void* scratch, uint32_t n);
+// Seventeen launches on `s` (bounding box x 2, codes, four radix passes of three kernels, gather + boxes, search); nothing is
+// synchronised here.
+// 1 <= k <= GS_KNN_MAX_K, n != 0; mean, dist2, visits: nullable.
+void launch_knn(const float* points, uint32_t n, int k, float* mean, float* dist2, uint32_t* visits, const KnnBuffers& b, hipStream_t s);
 
 }  // namespace gs

@@ -494,6 +494,33 @@ int gs_densify_apply(const gs_densify_input* in, uint64_t n, const gs_densify_ou
     });
 }
 
+uint64_t gs_knn_scratch_bytes(uint64_t n) { return n == 0 || n >= kMaxGaussians ? 0 : gs::knn_scratch_bytes(n); }
+
+int gs_knn_dist2(const float* points, uint64_t n, int k, float* mean_dist2, float* dist2, uint32_t* box_visits, void* scratch,
+                 uint64_t scratch_bytes, int device, void* stream) {
+    return guarded([&] {
+        if (n >= kMaxGaussians) throw Error(GS_ERR_INVALID, "too many points (limit 2^31)");
+        if (k < 1 || k > GS_KNN_MAX_K) throw Error(GS_ERR_INVALID, "k must be in [1, GS_KNN_MAX_K]");
+        if (!mean_dist2 && !dist2 && !box_visits) throw Error(GS_ERR_INVALID, "no output: mean_dist2, dist2 and box_visits are all null");
+        if (n && !points) throw Error(GS_ERR_INVALID, "null points");
+        if (n && !scratch) throw Error(GS_ERR_INVALID, "null scratch: gs_knn_scratch_bytes(n) bytes are required");
+        if (n && scratch_bytes < gs::knn_scratch_bytes(n)) throw Error(GS_ERR_INVALID, "scratch is smaller than gs_knn_scratch_bytes(n)");
+        const struct {
+            const void* p;
+            const char* name;
+        } members[5] = {{points, "points"}, {mean_dist2, "mean_dist2"}, {dist2, "dist2"}, {box_visits, "box_visits"}, {scratch, "scratch"}};
+        for (const auto& m : members)
+            if (reinterpret_cast<uintptr_t>(m.p) % 4 != 0) throw Error(GS_ERR_INVALID, std::string("`") + m.name + "` is not 4-byte aligned");
+        if (n == 0) return;
+        select_device(device);
+        const hipStream_t st = static_cast<hipStream_t>(stream);
+        const uint32_t rows = static_cast<uint32_t>(n);
+        gs::launch_knn(points, rows, k, mean_dist2, dist2, box_visits, gs::knn_buffers(scratch, rows), st);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipStreamSynchronize(st));
+    });
+}
+
 int gs_activate_records(const float* records, uint64_t n, float* vertices) {
     return guarded([&] {
         if ((!records || !vertices) && n) throw Error(GS_ERR_INVALID, "null argument");

@@ -1050,6 +1050,53 @@ typedef struct {
     float* out_exp_avg_sq[6];
 } gs_densify_output;
 int gs_densify_apply(const gs_densify_input* in, uint64_t n, const gs_densify_output* out, int device, void* stream);
+
+/* ---- initialisation from a point cloud: the mean squared distance to the k nearest neighbours ---------------------------
+ * What a 3DGS trainer derives a point's initial scale from (the Inria trainer's simple_knn.distCUDA2, k = 3).  Scene-less,
+ * like gs_densify_plan; no reference counterpart (the reference has no training).  gs_knn.hip, gs_knn_rules.h.
+ * THE QUANTITY, for points p[0 .. n), binary32 [n][3], every coordinate finite (a precondition: the C entry does not look;
+ * non-finite coordinates give unspecified values, never an access outside the arrays), and 1 <= k <= GS_KNN_MAX_K.
+ * Every operation is binary32, rounded on its own (the library is built with -ffp-contract=off):
+ *     dx = fl(xi - xj), dy = fl(yi - yj), dz = fl(zi - zj)
+ *     d2(i, j) = fl( fl( fl(dx dx) + fl(dy dy) ) + fl(dz dz) )              for every j != i, BY INDEX: a coincident point
+ *                                                                            at another index counts, with distance 0
+ *     ke = min(k, n - 1);  best[0] <= ... <= best[ke - 1] = the ke smallest of those values; a candidate replaces a kept
+ *                          value only where d2 < kept, so a NaN is never kept, nor is a d2 that overflowed to +inf
+ *                          (the slot then stays +inf, which is that value)
+ *     mean_dist2[i] = fl( fl( ... fl(best[0] + best[1]) + ... + best[ke - 1]) / (float)ke ),   +0.0f where ke == 0
+ *     dist2[i][0 .. k) = best, padded with +inf beyond ke
+ * The ke smallest values of a multiset do not depend on the order they are met in: the result has exactly ONE value, and the
+ * contract is a bit pattern, equal to the brute force over all pairs (tests/knn_reference.py), whatever the kernels do to
+ * avoid it.  Neighbour IDS are not returned: among equal distances they would depend on the order of the search.
+ * THE SEARCH: the points are ordered by a 30-bit Morton code over their bounding box (10 bits per axis; an axis without extent
+ * is cell 0; four stable radix passes, ties in id order) and gathered in that order; every GS_KNN_BOX consecutive points
+ * have a box (their min / max per axis).  A workgroup per query box, a lane per query point: it examines its own box, then the
+ * other boxes outward from it in the sorted order (b - 1, b + 1, b - 2, b + 2, ...), and passes a box over when
+ *     bound(A, B) > the largest best[k - 1] of the workgroup's lanes        (+inf while any lane has kept fewer than k)
+ * THE BOUND uses d2's operations in d2's order.  Per axis g = max(fl(loB - hiA), 0, fl(loA - hiB)); then
+ * fl(fl(fl(gx gx) + fl(gy gy)) + fl(gz gz)).  For a in A, b in B: where loB > hiA, b - a >= loB - hiA > 0 in the reals and
+ * rounding is monotonic, so |fl(a - b)| >= g; where the intervals meet g = 0.  Squares of non-negatives, sums of non-negatives
+ * and their roundings are monotonic, so the bound is <= d2(i, j) for EVERY member pair, and a box passed over holds no
+ * candidate with d2 < kept for any lane.  (A lane additionally passes a staged box over by the same bound with A its own point.)
+ * The walk order is fixed and nothing is atomic: two calls give the same bits in all three outputs.
+ * box_visits[b] = the boxes the workgroup of query box b (sorted points [b GS_KNN_BOX, ...)) staged, its own included: how
+ * much the bound saved, and a test's handle on it.  WORST CASE: all points coincident -- every code equal, every bound 0,
+ * nothing passed over, n^2 pairs.  Not special-cased.
+ * scratch: gs_knn_scratch_bytes(n) bytes of the caller's, on `device`, 16-byte aligned where possible (4 is enough); its
+ * content afterwards is unspecified.  stream and synchronisation: as gs_densify_plan.  n == 0: success, nothing launched,
+ * nothing touched.  The outputs must not overlap `points` or the scratch.
+ * GS_ERR_INVALID, checked before any device is touched: points NULL with n != 0; n >= 2^31; k outside [1, GS_KNN_MAX_K];
+ * all three outputs NULL; with n != 0, scratch NULL or scratch_bytes < gs_knn_scratch_bytes(n); a pointer that is not 4-byte
+ * aligned (judged by its value alone). */
+#define GS_KNN_MAX_K 8
+#ifndef GS_KNN_BOX
+#define GS_KNN_BOX 256u            /* sorted points per box = lanes per workgroup of the search */
+#endif
+uint64_t gs_knn_scratch_bytes(uint64_t n);      /* 0 for n == 0 */
+int gs_knn_dist2(const float* points, uint64_t n, int k,
+                 float* mean_dist2 /* [n], nullable */, float* dist2 /* [n][k], nullable */,
+                 uint32_t* box_visits /* [ceil(n / GS_KNN_BOX)], nullable */,
+                 void* scratch, uint64_t scratch_bytes, int device, void* stream);
 /* Test hook (tests/test_gpu_expf.py): evaluate the blend's exp() implementations ON THE DEVICE over the binary32 values with
  * bit patterns [first_bits, first_bits + count) (the negative floats run from 0x80000000 = -0 to 0xFF800000 = -inf).
  * block_sums[j] = sum over block j of 2^20 consecutive patterns of  bits(expf(x)) * ((bits(x) * 0x9E3779B1) | 1)  mod 2^64,

@@ -3,7 +3,7 @@
 # usage: bash tools/resource_usage.sh > profiles/rNN_kernel_resource_usage.txt
 cd "$(dirname "$0")/../3dgs.cpp_amd/csrc"
 printf "%-64s %6s %6s %6s %8s %6s %9s\n" kernel SGPRs VGPRs AGPRs scratch occ "LDS bytes"
-for f in gs_scene.hip gs_preprocess.hip gs_radix.hip gs_bin_l1.hip gs_bin_l2.hip gs_blend.hip gs_contrib.hip gs_features.hip gs_lift.hip gs_backward.hip gs_project_backward.hip gs_camera_backward.hip gs_loss.hip gs_optim.hip gs_densify.hip; do
+for f in gs_scene.hip gs_preprocess.hip gs_radix.hip gs_bin_l1.hip gs_bin_l2.hip gs_blend.hip gs_contrib.hip gs_features.hip gs_lift.hip gs_backward.hip gs_project_backward.hip gs_camera_backward.hip gs_loss.hip gs_optim.hip gs_densify.hip gs_knn.hip; do
   /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC -ffp-contract=off -fno-slp-vectorize --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage -c -x hip $f -o /dev/null 2>&1 |
   python3 -c '
 import re, subprocess, sys
